@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the fused TimeSeriesEnv.step() hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5|1] [--repeats R] [--no-cpu] [--no-extra]
+    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5|1] [--repeats R] [--no-cpu] [--no-extra] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -56,6 +56,9 @@ AUDITION_BUDGET = 48 << 30  # ... and at most this many bytes of them (config 2:
 WATCHDOG_S = float(os.environ.get("FE_BENCH_WATCHDOG_S", "300"))  # N > 1: seconds the strong-scaling leg + DeviceGuard check may take before every rank gives up on them
 TRAJ_BUDGET = 48e9      # bytes of trajectory chunks + gathered copies a rank may hold (N > 1)
 SETTLE_MS = 20.0        # untimed steps before every timed phase: the box's clock transient after an idle period (run_workload.settle)
+BENCH_SEED = 1234         # torch's global generators (main)
+DUMP_BUDGET = 64 * 10**6  # bytes --dump-outputs may write in all (OutputDump)
+DUMP_SEED = 0             # the fixed sample of observation rows --dump-outputs keeps when the whole observation does not fit
 # the reference's own PyTorch-CPU path, measured in the build container
 REFERENCE_CPU_QUOTED = {"value": 40497, "unit": "env-steps/s", "cores": 8,
                         "what": "hmomin/FinEnvs TimeSeriesEnv.step, torch 2.10 CPU, 65536 envs x W64, build container"}
@@ -493,6 +496,60 @@ class KernelTrain:
         return e0.elapsed_time(e1) / k
 
 
+class OutputDump:
+    """--dump-outputs DIR: what the timed path handed its caller in the LAST step of the last timed block of `value` -- the
+    observation, rewards and dones of env.step (the returned info is {} in training mode) -- as DIR/<name>.npy, so that two
+    builds can be compared output for output.
+
+    How many untimed steps precede that block depends on timing (settle steps, kernel trains, the ring audition), so the env's
+    state is put back to what it was at construction before the block's opening fence (outside the timed region): the dumped
+    step is then step `steps` from the initial state with actions[0 .. steps - 1 mod 8], whatever ran before.  The outputs are
+    copied on the device straight after the block's closing fence, before the kernel train that follows it overwrites them.
+
+    Files (at most DUMP_BUDGET bytes in all): rewards.npy (N,) f64, dones.npy (N,) f32 (0 / 1), obs.npy (S, W, 5A) in the
+    observation dtype and obs_rows.npy (S,) f64, the env rows obs.npy holds: all N rows if they fit, else a fixed seeded sample
+    (DUMP_SEED) in ascending order.  N > 1 GPUs: rank 0's shard."""
+
+    STATE = ("_env_indices", "_spot0", "_cash", "_long", "_short", "_margin", "_terminated", "_returns", "_counters")
+
+    def __init__(self, env):
+        import numpy as np
+
+        self.env = env
+        self.state = {k: getattr(env, k).clone() for k in self.STATE}
+        # redraw='torch': the evaluation env's next day comes from torch's generator on the env's device
+        self.rng = torch.cuda.get_rng_state(env._dev) if env.redraw == "torch" else None
+        N, W, A = env.num_envs, env.num_intervals, env.num_assets
+        row = W * 5 * A * torch.finfo(env.obs_dtype).bits // 8
+        S = min(N, (DUMP_BUDGET - 12 * N - 4 * 256) // (row + 8))  # rewards 8 B + dones 4 B per env, four .npy headers
+        if S < 1:
+            raise ValueError(f"--dump-outputs: {N} envs do not fit in {DUMP_BUDGET} bytes")
+        self.rows = np.arange(N) if S == N else np.sort(np.random.default_rng(DUMP_SEED).choice(N, S, replace=False))
+        self.rows_dev = torch.from_numpy(self.rows).to(env._dev)
+        self.out = None
+
+    def restore(self) -> None:
+        for k, t in self.state.items():
+            getattr(self.env, k).copy_(t)
+        if self.rng is not None:
+            torch.cuda.set_rng_state(self.rng, self.env._dev)
+
+    def capture(self, obs, rewards, dones) -> None:
+        self.out = (obs.index_select(0, self.rows_dev), rewards.clone(), dones.clone())
+
+    def write(self, path: str) -> dict:
+        import numpy as np
+
+        obs, rew, done = (t.cpu().numpy() for t in self.out)
+        arrays = {"obs": obs, "obs_rows": self.rows.astype(np.float64), "rewards": rew.astype(np.float64),
+                  "dones": done.astype(np.float32)}
+        os.makedirs(path, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(path, f"{name}.npy"), a)
+        return {"dir": path, "arrays": {name: [list(a.shape), str(a.dtype)] for name, a in arrays.items()},
+                "obs_rows_sampled": len(self.rows) < self.env.num_envs}
+
+
 def launches_per_train(est_step_ms: float, steps: int) -> int:
     """Launches one HIP-event pair brackets: at least 40 (and `steps`), enough for ~10 ms of GPU time, at most 400 -- a short
     train of a 30 us kernel is dominated by its first launches (they start on a GPU whose XCDs wake up staggered, DESIGN.md
@@ -507,9 +564,11 @@ def auto_repeats(repeats: int, steps: int, est_step_s: float) -> int:
     return int(min(40, max(5, round(0.15 / max(steps * est_step_s, 1e-9)))))
 
 
-def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: int, with_cpu: bool, redraw: str = None):
+def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: int, with_cpu: bool, redraw: str = None,
+                 dump_dir: str = None):
     """Build the env of one BASELINE config on this rank, time it, tear it down.  Returns the result dict
-    (on every rank; only rank 0 prints).  `redraw`: the evaluation env's redraw mode (default: --redraw)."""
+    (on every rank; only rank 0 prints).  `redraw`: the evaluation env's redraw mode (default: --redraw).  `dump_dir`: write
+    the outputs of the last timed step there (OutputDump; rank 0)."""
     redraw = redraw or args.redraw
     import finenvs_amd
     from finenvs_amd import _lib as _fl
@@ -555,6 +614,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
         gc.collect()
         torch.cuda.empty_cache()
         return {"workload": name, "config": config, "error": err or "another rank failed to build this workload"}
+    dump = OutputDump(env) if dump_dir else None
 
     gather = [D.multi]  # mutable: the timed legs flip it
     gather_due = [0]    # steps until the deferred collective of the chunk just handed over is started
@@ -572,12 +632,12 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
         # the "policy" hands over its output buffer (a ring of 8 pre-generated action tensors: hot, as a policy's fresh
         # output is); agent.store's fields -- actions, rewards, dones -- are written into slot t by the step kernel itself
         a, r, d = traj.next_slot()
-        obs, rew, done, _ = env.step(actions[i % 8], rewards_out=r, dones_out=d, actions_out=a)
+        out = env.step(actions[i % 8], rewards_out=r, dones_out=d, actions_out=a)
         if gather_due[0]:
             gather_due[0] -= 1
             if gather_due[0] == 0:
                 traj.issue_deferred()
-        return obs
+        return out
 
     roll = None
     if args.graph:
@@ -595,7 +655,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
 
     def run_steps(n):
         launched[0] += n
-        issue(n)
+        return issue(n)
 
     def fence():
         """drain + barrier + synchronize.  N > 1 over RCCL: the barrier is enqueued behind this rank's steps and gathers, so
@@ -611,17 +671,22 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
 
     train = [None, 0]  # KernelTrain of this env (built once its launch rate is known), launches per train
 
-    def timed_blocks(r):
+    def timed_blocks(r, capture=False):
         """r blocks of exactly `steps` steps, each bracketed by a full fence (drain + synchronize + barrier + synchronize) on
         both sides, as the driver's contract says; the block's time is the MAX over ranks.  Straight after each block's
         closing fence ONE kernel train runs (KernelTrain: back-to-back C-ABI launches of the loop's own kernel form between
         a pair of HIP events): block and train alternate, so `roofline.kernel_ms` and `ms_per_step` are medians over the
-        same stretch of time, on the same buffers, in the same clock regime.  Returns (block seconds, train ms per launch)."""
+        same stretch of time, on the same buffers, in the same clock regime.  Returns (block seconds, train ms per launch).
+        `capture` (blocks that may become `value`, with --dump-outputs): the last block starts from the initial state and
+        its last step's outputs are kept (OutputDump)."""
         out, trains = [], []
-        for _ in range(r):
+        for b in range(r):
+            keep = capture and dump is not None and b == r - 1
+            if keep:
+                dump.restore()
             fence()
             t0 = time.perf_counter()
-            run_steps(steps)
+            outs = run_steps(steps)
             if trace:
                 t1 = time.perf_counter()
                 torch.cuda.synchronize()
@@ -632,6 +697,8 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
                 t3 = time.perf_counter()
                 print(f"[trace] issue {(t1 - t0) * 1e6:8.1f} us  drain {(t2 - t1) * 1e6:8.1f} us  fence+max {(t3 - t2) * 1e6:8.1f} us  "
                       f"({steps} steps)", file=sys.stderr, flush=True)
+            if keep:  # (--graph: the replay's static buffers hold its newest step)
+                dump.capture(*(outs[-1][:3] if roll is None else (roll.obs, roll.rewards[-1], roll.dones[-1])))
             if train[0] is not None:
                 trains.append(train[0].run(train[1]))
                 launched[0] += train[1]
@@ -679,7 +746,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
             traj.clear()
             run_steps(T)  # one full chunk: the first timed block has something to gather
         before_value = launched[0]
-        aa_blocks, aa_trains = timed_blocks(R)
+        aa_blocks, aa_trains = timed_blocks(R, capture=True)
         aa_kern = statistics.median(aa_trains)
         ring_before = [t.data_ptr() for t in env._obs_ring]
         env.audition_ring(AUDITION_EXTRA, AUDITION_BUDGET)
@@ -713,7 +780,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
         run_steps(T)  # one full chunk: the first timed block has something to gather
         if reuse_blocks is None:
             before_value = launched[0]
-        legs["with_all_gather"], kern = reuse_blocks if reuse_blocks is not None else timed_blocks(R)
+        legs["with_all_gather"], kern = reuse_blocks if reuse_blocks is not None else timed_blocks(R, capture=True)
         fence()
         gather[0] = False
         traj.clear()
@@ -741,7 +808,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
     else:
         if reuse_blocks is None:
             before_value = launched[0]
-        legs["single_gpu"], kern = reuse_blocks if reuse_blocks is not None else timed_blocks(R)
+        legs["single_gpu"], kern = reuse_blocks if reuse_blocks is not None else timed_blocks(R, capture=True)
         head = legs["single_gpu"]
     block = statistics.median(head)
 
@@ -869,10 +936,12 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
             "predicted_hidden_behind_the_block": bool(pred[1] <= block_ms_no),
             "gather_hbm_share_of_block": (traj._nbytes * (ws + 1)) / max(Bh * N * steps, 1),
         }
+    if dump is not None and rank == 0:
+        res["output_dump"] = dump.write(dump_dir)
     if with_cpu and rank == 0:
         res["cpu_baseline"] = cpu_baseline(A, W)
     fence()
-    del env, traj, actions, roll
+    del env, traj, actions, roll, dump
     gc.collect()
     torch.cuda.empty_cache()
     return res
@@ -1184,8 +1253,12 @@ def main():
     ap.add_argument("--no-audition", action="store_true", help="take the observation ring as allocated (no placement audition)")
     ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 child passes")
     ap.add_argument("--detail", default=None, metavar="PATH", help="also write the full record (everything stderr's [bench-detail] lines carry) as one JSON document")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline's last timed step returned (observation, rewards, dones) as DIR/<name>.npy (OutputDump)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
         pmc_child(args)
         return
@@ -1208,8 +1281,13 @@ def main():
         if D.rank == 0:
             print(f"[bench {time.perf_counter() - t_start:6.1f} s] {msg}", file=sys.stderr, flush=True)
 
+    # torch seeds its global generators anew in every process; the evaluation env's first day (redraw='torch') is drawn from the
+    # device's: a fixed seed makes the inputs of every workload the same from run to run (and on every rank)
+    torch.manual_seed(BENCH_SEED)
+
     # ---- 1. the headline (+ cpu_baseline on the plain N = 1 run): nothing else has touched the GPU yet
-    head = run_workload(args.config, args, D, args.steps, args.warmup, args.repeats, with_cpu=(not args.no_cpu and not D.multi))
+    head = run_workload(args.config, args, D, args.steps, args.warmup, args.repeats, with_cpu=(not args.no_cpu and not D.multi),
+                        dump_dir=args.dump_outputs)
     if "error" in head:
         sys.exit(f"bench.py: headline workload failed: {head['error']}")
     detail = {"n_gpus": D.world, "steps": args.steps, "dtype": "f32" if args.obs_f32 else "f64", "eval_redraw": args.redraw,

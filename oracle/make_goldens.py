@@ -557,6 +557,10 @@ def main():
     for inst, W, fname in (("OIH", 32, "tables_oih.npz"), ("IBM", 390, "tables_ibm.npz"), ("SPY", 390, "tables_spy.npz"),
                            ("IBM", 4, "tables_ibm_w4.npz"), ("SPY", 4, "tables_spy_w4.npz")):
         real_tables_case(inst, W, fname)
+    # the three data files themselves, byte for byte: the native reader's input in tests/test_csv_native.py
+    save_npz(os.path.join(GOLD, "csv_reference_files.npz"),
+             **{inst: np.frombuffer(open(os.path.join(REF, "finenvs", "data", inst, "dummy.csv"), "rb").read(), dtype=np.uint8)
+                for inst in ("OIH", "IBM", "SPY")})
 
     # ---------------- rollouts (a2-a17) ----------------
     write_case_csv("SYN_roll", 7, 40, seed=1234)

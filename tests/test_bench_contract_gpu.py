@@ -82,6 +82,47 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     assert "[bench-detail] {\"headline\"" in out.stderr
 
 
+def test_dump_outputs_is_step_k_of_the_timed_path_and_repeats_across_runs(tmp_path):
+    """`--dump-outputs DIR`: two runs with the same arguments write the same arrays (float32 / float64, under 64 MB), and they are
+    what step `--steps` of the timed loop returns from the initial state -- the oracle stepped with bench.py's own action ring on
+    the same tables, bit for bit (the evaluation env, whose first day is a draw of torch's generator, is left out)."""
+    import numpy as np
+    import torch
+
+    import bench
+    import finenvs_amd
+    from oracle import fe_oracle as fo
+    from tests.helpers import assert_bits
+
+    K = 12
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        out = _run(["--gpus", "1", "--config", "1", "--steps", str(K), "--warmup", "3", "--repeats", "3", "--no-cpu", "--no-extra",
+                    "--no-pmc", "--dump-outputs", str(d)], timeout=600)
+        assert _one_json_line(out)["steps"] == K
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10**6
+        runs.append({n: np.load(d / f"{n}.npy") for n in ("obs", "obs_rows", "rewards", "dones")})
+    for n, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert_bits(a, runs[1][n], n)
+
+    _, N, A, W = bench.CONFIGS[1]
+    prices, day_id, _ = bench.make_series(A)
+    env = finenvs_amd.TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=W, num_envs=N, redraw="device", obs_buffers=1)
+    ref = fo.OracleEnv(env.price_environments.cpu().numpy(), env.log_return_environments.cpu().numpy(), W, num_envs=N)
+    g = torch.Generator(device="cuda:0").manual_seed(7)  # bench.py's action ring (rank 0)
+    actions = [(torch.rand((N, A), generator=g, device="cuda:0") * 2 - 1).float().cpu().numpy() for _ in range(8)]
+    for i in range(K):
+        obs, rew, done, _ = ref.step(actions[i % 8])
+    got = runs[0]
+    rows = got["obs_rows"].astype(np.int64)
+    keep = rows != N - 1
+    assert_bits(got["obs"][keep], obs[rows[keep]], "obs")
+    assert_bits(got["rewards"][:-1], rew[:-1], "rewards")
+    assert_bits(got["dones"][:-1], done[:-1].astype(np.float32), "dones")
+
+
 def test_default_driver_command_every_leg_kernel_below_step_and_both_scaling_readings(tmp_path):
     """The driver's N = 1 command in full (`--steps 20 --warmup 5`, live counter passes included): the line is small and strict;
     for the headline AND every extra_configs leg the kernel interval is at most the wall step (1 % slack) and `roofline.traffic`

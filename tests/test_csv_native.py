@@ -145,18 +145,18 @@ def test_native_reader_reproduces_reference_frames(tmp_path):
     assert_bits(s, g["ref_start_indices"]); assert_bits(e, g["ref_stop_indices"])
 
 
-REF_DATA = "/root/reference/finenvs/data"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference tree exists in the build container only")
 @pytest.mark.parametrize("inst,fixture", [("OIH", "tables_oih.npz"), ("IBM", "tables_ibm.npz"), ("SPY", "tables_spy.npz")])
-def test_native_reader_on_the_references_own_files(inst, fixture):
+def test_native_reader_on_the_references_own_files(inst, fixture, tmp_path):
     """fe_csv_read on the three real files the reference's unit test builds (tests/unit/test_time_series_env.py:
     10-14) -- MM/DD/YYYY + HH:MM (IBM, OIH), YYYY-MM-DD + HH:MM:SS with 04:00 pre-market rows (SPY) -- equals, bit
     for bit, the frame the reference's pandas path kept (stored in the fixture by oracle/make_goldens.py), and the
-    episode bounds at the fixture's window equal the reference's bounds cache."""
+    episode bounds at the fixture's window equal the reference's bounds cache.  The files themselves are stored byte
+    for byte in csv_reference_files.npz and written out here as the reader's input."""
     g = load_golden(fixture)
-    prices, day_id, sec = loader.read_csv_series(os.path.join(REF_DATA, inst, "dummy.csv"))
+    p = tmp_path / inst / "dummy.csv"
+    p.parent.mkdir()
+    p.write_bytes(load_golden("csv_reference_files.npz")[inst].tobytes())
+    prices, day_id, sec = loader.read_csv_series(str(p))
     assert_bits(prices, g["ref_dataset"], "market-hours OHLC rows")
     assert_bits(day_id, g["series_day_id"], "day ids by first appearance")
     assert_bits(sec, g["series_second"], "second of day")

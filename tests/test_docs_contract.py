@@ -30,7 +30,8 @@ def _exists(path):
     if os.path.exists(full):
         return True
     # a cited stem (`profiles/r05_c2` for r05_c2_summary.md / _kernel_stats.csv) or a built artefact that is git-ignored
-    if glob.glob(full + "*") or path.endswith((".so", ".o")) or path.startswith("oracle/_ref"):
+    # (csrc/variants/ holds the experiment builds of finenvs_amd.csrc.build.build_variant: absent from a clean checkout)
+    if glob.glob(full + "*") or path.endswith((".so", ".o")) or path.startswith(("oracle/_ref", "finenvs_amd/csrc/variants")):
         return True
     return False
 
