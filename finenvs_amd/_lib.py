@@ -85,6 +85,27 @@ EXT_SIGNATURES = {
     "fe_env_set_launch": (C.c_int, [_vp, _i32, _i32, _i32]),
 }
 
+# include/finenvs_amd_evo.h: the evolution-strategies population (finenvs_amd/evo.py; same library)
+class FeEvoPopulation(C.Structure):
+    """struct fe_evo_population of include/finenvs_amd_evo.h."""
+
+    _fields_ = [
+        ("num_train", C.c_int64), ("hidden", C.c_int32), ("max_episodes", C.c_int32),
+        ("noise_std", C.c_float), ("action_noise_std", C.c_float), ("seed", C.c_uint64),
+        ("generation", C.c_uint32), ("step", C.c_uint32),
+        ("logret_f32", _vp), ("theta", _vp), ("obs_src", _vp), ("obs_pos", _vp), ("returns", _vp), ("timesteps", _vp),
+        ("episode_returns", _vp), ("episode_counts", _vp), ("counters", _vp), ("scratch_rewards", _vp),
+        ("scratch_dones", _vp),
+    ]
+
+
+EVO_SIGNATURES = {
+    "fe_evo_rollout": (C.c_int, [_vp, C.POINTER(FeEvoPopulation), _i32, _vp, _vp, _vp, _vp, _vp]),
+    "fe_evo_gradient_workspace_doubles": (_i64, [_i64, _i64]),
+    "fe_evo_gradient": (C.c_int, [C.c_uint64, C.c_uint32, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "fe_evo_noise": (C.c_int, [C.c_uint64, C.c_uint32, _vp, _i64, _i64, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -109,7 +130,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                 "finenvs_amd has no CPU fallback"
             ) from exc
     lib = C.CDLL(p)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

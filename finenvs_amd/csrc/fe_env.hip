@@ -25,13 +25,14 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, seven files:
+// One translation unit, eight files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
 //   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA)
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
+//   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_env.hip            (this file) launch geometry, the env object, the C ABI of include/finenvs_amd.h
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
@@ -51,12 +52,14 @@
 
 #include "finenvs_amd.h"
 #include "finenvs_amd_ext.h"
+#include "finenvs_amd_evo.h"
 
 #include "fe_device_common.h"
 #include "fe_step_kernel.h"
 #include "fe_rollout_kernels.h"
 #include "fe_lstm_kernel.h"
 #include "fe_aux_kernels.h"
+#include "fe_evo_kernels.h"
 
 namespace {
 
@@ -1093,6 +1096,101 @@ int fe_traj_returns(const double *rewards, const int32_t *dones, const float *va
                            values, last_values, T, N, (float)gamma, returns, advantages);
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) return hip_fail(he, "fe_traj_returns launch");
+    return FE_OK;
+}
+
+// ---- include/finenvs_amd_evo.h: the evolution-strategies population ----
+
+int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *actions_out, float *means_out,
+                   double *rewards_out, int32_t *dones_out, void *stream) {
+    if (!env || !pop || K < 1 || !pop->logret_f32 || !pop->theta || !pop->obs_src || !pop->obs_pos || !pop->returns ||
+        !pop->timesteps || !pop->episode_returns || !pop->episode_counts || !pop->counters || !pop->scratch_rewards ||
+        !pop->scratch_dones)
+        return fail(FE_ERR_ARG, "fe_evo_rollout: bad argument");
+    if (!env->bound) return fail(FE_ERR_ARG, "fe_evo_rollout: env state not bound");
+    const int32_t H = pop->hidden;
+    if (H != 32 && H != 64) return fail(FE_ERR_ARG, "fe_evo_rollout: H must be 32 or 64 (got %d)", (int)H);
+    Params p = env->p;
+    const int64_t nt = pop->num_train;
+    if (nt <= 0 || nt % 2 != 0 || nt > p.N)
+        return fail(FE_ERR_ARG, "fe_evo_rollout: the %lld training envs must be positive, even and at most N = %lld "
+                    "(mirrored sampling, parallel_mlp.py:24-27)", (long long)nt, (long long)p.N);
+    if (pop->max_episodes < 1) return fail(FE_ERR_ARG, "fe_evo_rollout: max_episodes must be >= 1");
+    if (p.evaluate) return fail(FE_ERR_ARG, "fe_evo_rollout: the population needs a training-mode env (evaluate = 0)");
+    if (p.redraw_mode != 1) return fail(FE_ERR_ARG, "fe_evo_rollout: the population needs redraw mode 1 (device redraws)");
+    if (p.A > 128) return fail(FE_ERR_ARG, "fe_evo_rollout: at most 128 assets per env (got %d)", (int)p.A);
+    DeviceGuard guard(env->device);
+    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    // a tile = PB mirrored pairs (2 PB envs): each wavefront evaluates whole pairs, every z element serves both signs
+    int PB = 128 / p.A;
+    if (PB > 8) PB = 8;
+    if (PB < 1) PB = 1;
+    const int64_t half = nt / 2;
+    const int EB = 2 * PB;
+    const int64_t pair_tiles = (half + PB - 1) / PB;
+    const int64_t eval_tiles = (p.N - nt + EB - 1) / EB;
+    p.EB = EB;
+    p.num_tiles = pair_tiles + eval_tiles;
+    const int64_t P = evo_num_params(p.W, H);
+    const size_t lds = evo_lds_bytes(EB, p.A, P);
+    if (lds > 160 * 1024)
+        return fail(FE_ERR_ARG, "fe_evo_rollout: theta (%lld floats) does not fit the 160 KiB LDS (%zu bytes needed)",
+                    (long long)P, lds);
+    EvoArgs r;
+    r.lr32 = pop->logret_f32; r.theta = pop->theta; r.obs_src = pop->obs_src; r.obs_pos = pop->obs_pos;
+    r.ret = pop->returns; r.ts = pop->timesteps; r.ep_ret = pop->episode_returns; r.ep_cnt = pop->episode_counts;
+    r.counters = reinterpret_cast<unsigned long long *>(pop->counters);
+    r.actions_out = actions_out; r.means_out = means_out; r.rew_out = rewards_out; r.done_out = dones_out;
+    r.rew_scratch = pop->scratch_rewards; r.done_scratch = pop->scratch_dones;
+    r.n_train = nt; r.half = half; r.K = K; r.max_ep = pop->max_episodes; r.PB = PB; r.pair_tiles = (int32_t)pair_tiles;
+    r.sigma = pop->noise_std; r.nu = pop->action_noise_std; r.seed = pop->seed; r.g = pop->generation; r.step0 = pop->step;
+    const bool single = p.A == 1;
+#define FE_EVO(HH) (single ? (const void *)fe_evo_rollout_kernel<true, HH> : (const void *)fe_evo_rollout_kernel<false, HH>)
+    const void *kern = H == 32 ? FE_EVO(32) : FE_EVO(64);
+#undef FE_EVO
+    hipError_t he = prepare_kernel(env->device, kern, kBlock, lds, nullptr);
+    if (he != hipSuccess) return hip_fail(he, "fe_evo_rollout: hipFuncSetAttribute");
+    const int64_t grid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
+    void *args[] = {&p, &r};
+    he = hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), args, lds, (hipStream_t)stream);
+    if (he != hipSuccess) return hip_fail(he, "fe_evo_rollout launch");
+    return FE_OK;
+}
+
+int64_t fe_evo_gradient_workspace_doubles(int64_t num_pairs, int64_t num_params) {
+    if (num_pairs < 1 || num_params < 1) return 0;
+    return (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs * num_params;
+}
+
+int fe_evo_gradient(uint64_t seed, uint32_t generation, int64_t num_pairs, int64_t num_params, const float *diffed,
+                    double *workspace, double *out, void *stream) {
+    if (!diffed || !workspace || !out || num_pairs < 1 || num_params < 1 || num_pairs > 0xffffffffll ||
+        num_params > 4 * 0xffffffffll)
+        return fail(FE_ERR_ARG, "fe_evo_gradient: bad argument");
+    DeviceGuard guard(device_of(out));
+    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_evo_gradient: out is not device memory");
+    const int64_t blocks = (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs;
+    const int64_t threads = blocks * ((num_params + 3) / 4);
+    hipLaunchKernelGGL(fe_evo_gradient_partial_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, seed, generation, num_pairs, num_params, diffed, workspace);
+    hipLaunchKernelGGL(fe_evo_gradient_reduce_kernel, dim3((unsigned)((num_params + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, blocks, num_params, (const double *)workspace, out);
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "fe_evo_gradient launch");
+    return FE_OK;
+}
+
+int fe_evo_noise(uint64_t seed, uint32_t generation, const int64_t *pairs, int64_t count, int64_t num_params, float *out,
+                 void *stream) {
+    if (!pairs || !out || count < 1 || num_params < 1 || num_params > 4 * 0xffffffffll)
+        return fail(FE_ERR_ARG, "fe_evo_noise: bad argument");
+    DeviceGuard guard(device_of(out));
+    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_evo_noise: out is not device memory");
+    const int64_t threads = count * ((num_params + 3) / 4);
+    hipLaunchKernelGGL(fe_evo_noise_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, seed, generation, pairs, count, num_params, out);
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "fe_evo_noise launch");
     return FE_OK;
 }
 

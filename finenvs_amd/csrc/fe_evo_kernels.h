@@ -1,0 +1,349 @@
+// fe_evo_kernels.h -- part of fe_env.hip (one translation unit; see the overview there): the evolution-strategies
+// population -- a K-step rollout in which every env acts with ITS OWN perturbed one-hidden-layer perceptron, generated
+// inside the kernel from a counter-based normal stream -- plus the gradient and noise-render kernels of the ES update
+// (finenvs/agents/ES/evo_agent.py, finenvs/agents/networks/parallel_mlp.py; C ABI: include/finenvs_amd_evo.h).
+#pragma once
+#include "fe_device_common.h"
+#include "fe_rollout_kernels.h"
+#include "fe_activations.h"
+
+namespace {
+
+// Counter domains (word c3 of the Philox counter).  The redraw stream of redraw_mode 1 uses c2 = 0x46454e56, c3 = 0, so a
+// non-zero c3 keeps both streams below apart from it and from each other.
+constexpr uint32_t kEvoDomainZ = 0x45565a00u;    // "EVZ": parameter perturbations, counter (j / 4, pair, generation)
+constexpr uint32_t kEvoDomainAct = 0x45564100u;  // "EVA" | asset / 4: action noise, counter (env, step, generation)
+constexpr int kEvoGradPairs = 64;                // pairs per partial sum of the gradient's first pass
+
+// Philox4x32-10 with all four output words (philox_u32 of fe_device_common.h returns the first only).
+__device__ __forceinline__ uint4 evo_philox4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        uint32_t n1 = (uint32_t)p1;
+        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return make_uint4(c0, c1, c2, c3);
+}
+
+// f32 Box-Muller on the four words: (w0, w1) -> normals 0, 1 and (w2, w3) -> normals 2, 3.  u = ((w >> 8) + 1) / 2^24 in
+// (0, 1], the angle (w >> 8) / 2^24 in revolutions (what v_sin_f32 / v_cos_f32 take), ln u = ln 2 * log2 u (v_log_f32).
+// This device function IS the definition of the stream: the host never restates it, tests read it through fe_evo_noise.
+__device__ __forceinline__ float4 evo_normal4(uint4 w) {
+    const float k = 5.9604644775390625e-8f;  // 2^-24
+    const float u0 = (float)((w.x >> 8) + 1u) * k, t0 = (float)(w.y >> 8) * k;
+    const float u1 = (float)((w.z >> 8) + 1u) * k, t1 = (float)(w.w >> 8) * k;
+    const float r0 = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u0));
+    const float r1 = __builtin_amdgcn_sqrtf(-1.38629436f * __builtin_amdgcn_logf(u1));
+    return make_float4(r0 * __builtin_amdgcn_cosf(t0), r0 * __builtin_amdgcn_sinf(t0), r1 * __builtin_amdgcn_cosf(t1),
+                       r1 * __builtin_amdgcn_sinf(t1));
+}
+
+// z_{g,p,4q..4q+3}
+__device__ __forceinline__ float4 evo_z4(uint64_t seed, uint32_t g, int64_t pair, uint32_t q) {
+    return evo_normal4(evo_philox4(seed, q, (uint32_t)pair, g, kEvoDomainZ));
+}
+
+__device__ __forceinline__ float evo_action_noise(uint64_t seed, uint32_t g, uint32_t step, int64_t n, int a) {
+    const float4 v = evo_normal4(evo_philox4(seed, (uint32_t)n, step, g, kEvoDomainAct | (uint32_t)(a >> 2)));
+    const int m = a & 3;
+    return m == 0 ? v.x : (m == 1 ? v.y : (m == 2 ? v.z : v.w));
+}
+
+__device__ __forceinline__ float f4get(const float4 &v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+
+struct EvoArgs {
+    const float *lr32;   // (D, L, 4A) f32 copy of the log-return table
+    const float *theta;  // (P) W1 (5W, H), b1 (H), W2 (H), b2, each row-major
+    int64_t *obs_src;
+    double *obs_pos;
+    float *ret;          // (N) running return
+    float *ts;           // (N) running timestep count
+    float *ep_ret;       // (N, max_ep) finished episodes' returns
+    int32_t *ep_cnt;     // (N)
+    unsigned long long *counters;  // [0] timesteps of finished episodes, [1] slot-table overflow flag
+    float *actions_out;  // (K, N, A) or null
+    float *means_out;    // (K, N, A) or null: the network's output before the action noise
+    double *rew_out;     // (K, N) or null (then rew_scratch (N) takes every step)
+    int32_t *done_out;
+    double *rew_scratch;
+    int32_t *done_scratch;
+    int64_t n_train, half;
+    int32_t K, max_ep, PB, pair_tiles;
+    float sigma, nu;
+    uint64_t seed;
+    uint32_t g, step0;
+};
+
+__host__ __device__ inline int64_t evo_num_params(int W, int H) { return (int64_t)5 * W * H + 2 * (int64_t)H + 1; }
+
+__host__ __device__ inline size_t evo_lds_bytes(int EB, int A, int64_t P) {
+    size_t S = (size_t)EB * A;
+    size_t b = (size_t)EB * 8 + S * 8 + S * 8 + S * 4 + S * 4 + (size_t)EB * 4;  // TileLds
+    b = (b + 7) & ~(size_t)7;
+    b += (size_t)EB * 8;  // redrawn day per env
+    b += S * 4;           // actions
+    b = (b + 15) & ~(size_t)15;
+    b += (size_t)P * 4;   // theta
+    return (b + 15) & ~(size_t)15;
+}
+
+// The policy of one unit = two env slots of the tile, by one wavefront.  Pair tiles: slot u is env p (sign +1), slot PB + u
+// env p + n_train/2 (sign -1) of the same pair p, so every z element is generated once and serves both signs.  Eval tiles:
+// slots 2u, 2u + 1, both unperturbed.  Lane l owns hidden units 4q..4q+3 (q = l % G, G = H / 4: one Philox call per row)
+// for the rows r = rg, rg + R, ... (rg = l / G, R = 64 / G) of W1; a butterfly over the row groups completes the first
+// layer, one over q the second.  Assets are evaluated one after the other with the env's weights (z regenerated per asset).
+template <bool SINGLE, int H>
+__device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &r, const TileLds &l, float *s_act,
+                                                const float *s_theta, bool pair_tile, int64_t base, int u, int k,
+                                                int lane) {
+    constexpr int G = H / 4, R = 64 / G;
+    const int A = SINGLE ? 1 : p.A;
+    const int R5 = 5 * p.W;
+    const int PB = r.PB;
+    int eA, eB;
+    int64_t nA, nB, pair = 0;
+    bool vA, vB;
+    if (pair_tile) {
+        pair = base + u;
+        eA = u; eB = PB + u;
+        nA = pair; nB = r.half + pair;
+        vA = vB = pair < r.half;
+    } else {
+        eA = 2 * u; eB = 2 * u + 1;
+        nA = base + eA; nB = base + eB;
+        vA = nA < p.N; vB = nB < p.N;
+    }
+    if (!vA) return;          // wave-uniform
+    if (!vB) eB = eA;         // (an eval tile's last odd env: computed twice, stored once)
+    const int q = lane % G, rg = lane / G;
+    const float sigma = r.sigma;
+    const int64_t rstride = 4 * (int64_t)A;
+    const int64_t NA = p.N * A;
+    const uint32_t qb = (uint32_t)R5 * G;  // Philox counter of b1[0..3]
+    for (int a = 0; a < A; ++a) {
+        const float *xa = r.lr32 + l.src[eA] + 4 * a;
+        const float *xb = r.lr32 + l.src[eB] + 4 * a;
+        const float posA = (float)l.pos[eA * A + a], posB = (float)l.pos[eB * A + a];
+        float accA[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accB[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int row = rg; row < R5; row += R) {
+            const int jw = row / 5, c = row - 5 * jw;
+            const float xA = c < 4 ? xa[jw * rstride + c] : posA;
+            const float xB = c < 4 ? xb[jw * rstride + c] : posB;
+            const float4 th = *reinterpret_cast<const float4 *>(s_theta + (size_t)row * H + 4 * q);
+            if (pair_tile) {
+                const float4 z = evo_z4(r.seed, r.g, pair, (uint32_t)row * G + q);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float e = sigma * f4get(z, i);
+                    accA[i] = fmaf(xA, f4get(th, i) + e, accA[i]);
+                    accB[i] = fmaf(xB, f4get(th, i) - e, accB[i]);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    accA[i] = fmaf(xA, f4get(th, i), accA[i]);
+                    accB[i] = fmaf(xB, f4get(th, i), accB[i]);
+                }
+            }
+        }
+#pragma unroll
+        for (int m = G; m < 64; m <<= 1)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                accA[i] = accA[i] + __shfl_xor(accA[i], m, 64);
+                accB[i] = accB[i] + __shfl_xor(accB[i], m, 64);
+            }
+        const float *tb = s_theta + (size_t)R5 * H;
+        const float4 b1 = *reinterpret_cast<const float4 *>(tb + 4 * q);
+        const float4 w2 = *reinterpret_cast<const float4 *>(tb + H + 4 * q);
+        float b2A = tb[2 * H], b2B = b2A;
+        float4 zb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), zw = zb;
+        if (pair_tile) {
+            zb = evo_z4(r.seed, r.g, pair, qb + q);
+            zw = evo_z4(r.seed, r.g, pair, qb + G + q);
+            const float e = sigma * evo_z4(r.seed, r.g, pair, qb + 2 * G).x;
+            b2A = b2A + e;
+            b2B = b2B - e;
+        }
+        float partA = 0.0f, partB = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float eb = sigma * f4get(zb, i), ew = sigma * f4get(zw, i);
+            const float hA = lstm_tanh(accA[i] + (f4get(b1, i) + eb));
+            const float hB = lstm_tanh(accB[i] + (f4get(b1, i) - eb));
+            partA = fmaf(f4get(w2, i) + ew, hA, partA);
+            partB = fmaf(f4get(w2, i) - ew, hB, partB);
+        }
+#pragma unroll
+        for (int m = 1; m < G; m <<= 1) {
+            partA = partA + __shfl_xor(partA, m, 64);
+            partB = partB + __shfl_xor(partB, m, 64);
+        }
+        const float outA = lstm_tanh(partA + b2A), outB = lstm_tanh(partB + b2B);
+        float actA = outA, actB = outB;
+        if (pair_tile && r.nu != 0.0f) {  // parallel_mlp.py:95,106-110: training members only
+            const uint32_t step = r.step0 + (uint32_t)k;
+            actA = outA + r.nu * evo_action_noise(r.seed, r.g, step, nA, a);
+            actB = outB + r.nu * evo_action_noise(r.seed, r.g, step, nB, a);
+        }
+        if (lane == 0) {
+            s_act[eA * A + a] = actA;
+            if (r.means_out) r.means_out[(int64_t)k * NA + nA * A + a] = outA;
+            if (vB) {
+                s_act[eB * A + a] = actB;
+                if (r.means_out) r.means_out[(int64_t)k * NA + nB * A + a] = outB;
+            }
+        }
+    }
+}
+
+// K steps of the whole population per launch: the loop of fe_rollout_mlp_kernel (account state in registers, descriptors
+// in LDS, account_keep), with the per-env policy above and EvoAgent.store's bookkeeping (evo_agent.py:96-112) where the
+// done flag is known.  Tiles: pair tiles [0, pair_tiles) hold PB mirrored pairs (2 PB envs), the rest EB = 2 PB
+// consecutive eval envs.
+template <bool SINGLE, int H>
+__global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params p, const EvoArgs r) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int A = SINGLE ? 1 : p.A;
+    const int EB = p.EB;
+    const int S = EB * A;
+    const TileLds l = carve_lds(smem, EB, S);
+    size_t off = (size_t)EB * 8 + (size_t)S * 8 + (size_t)S * 8 + (size_t)S * 4 + (size_t)S * 4 + (size_t)EB * 4;
+    off = (off + 7) & ~(size_t)7;
+    int64_t *l_idx = reinterpret_cast<int64_t *>(smem + off);
+    off += (size_t)EB * 8;
+    float *s_act = reinterpret_cast<float *>(smem + off);
+    off = (off + (size_t)S * 4 + 15) & ~(size_t)15;
+    float *s_theta = reinterpret_cast<float *>(smem + off);
+    const int64_t P = evo_num_params(p.W, H);
+    const int tid = threadIdx.x;
+    const int e = SINGLE ? tid : (int)fdiv((uint32_t)tid, p.div_A);
+    const int a = SINGLE ? 0 : tid - e * A;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int64_t NA = p.N * A;
+    const int PB = r.PB;
+    for (int64_t i = tid; i < P; i += kBlock) s_theta[i] = r.theta[i];
+
+    for (int64_t tile = blockIdx.x; tile < p.num_tiles; tile += gridDim.x) {
+        const bool pair_tile = tile < r.pair_tiles;
+        int64_t base, n;
+        bool valid;
+        if (pair_tile) {
+            base = tile * PB;
+            const int64_t np = r.half - base < PB ? r.half - base : PB;
+            n = e < PB ? base + e : r.half + base + (e - PB);
+            valid = (e < PB ? e : e - PB) < np;
+        } else {
+            base = r.n_train + (tile - r.pair_tiles) * EB;
+            n = base + e;
+            valid = n < p.N;
+        }
+        const bool active = e < EB && valid;
+        if (!active) n = 0;
+        const int64_t sl = n * A + a;
+        SleeveReg st = rollout_load_state(p, active, n, sl);
+        float ret = 0.0f, ts = 0.0f;
+        if (active) {
+            if (a == 0) {
+                l.src[e] = r.obs_src[n];
+                ret = r.ret[n];
+                ts = r.ts[n];
+            }
+            l.pos[e * A + a] = r.obs_pos[sl];
+        }
+        __syncthreads();  // also covers theta on the first tile
+        for (int k = 0; k < r.K; ++k) {
+            for (int u = wave; u < PB; u += kBlock / 64)
+                evo_policy_unit<SINGLE, H>(p, r, l, s_act, s_theta, pair_tile, base, u, k, lane);
+            lds_barrier();
+            const float act = active ? s_act[e * A + a] : 0.0f;
+            if (active && r.actions_out) r.actions_out[(int64_t)k * NA + sl] = act;
+            double *rew = r.rew_out ? r.rew_out + (int64_t)k * p.N : r.rew_scratch;
+            int32_t *done = r.done_out ? r.done_out + (int64_t)k * p.N : r.done_scratch;
+            account_keep<SINGLE>(p, l, l_idx, A, e, a, active, n, st, act, rew, done);
+            if (active && a == 0) {  // evo_agent.py:96-112 (current_returns is f32, the rewards f64)
+                ret = (float)((double)ret + rew[n]);
+                ts = ts + 1.0f;
+                if (done[n]) {
+                    const int32_t c = r.ep_cnt[n];
+                    if (c < r.max_ep) {
+                        r.ep_ret[n * r.max_ep + c] = ret;
+                        r.ep_cnt[n] = c + 1;
+                    } else {
+                        r.counters[1] = 1ull;  // train() refuses: an episode would be lost
+                    }
+                    atomicAdd(&r.counters[0], (unsigned long long)ts);
+                    ret = 0.0f;
+                    ts = 0.0f;
+                }
+            }
+            lds_barrier();  // the new observation's descriptors are complete
+        }
+        rollout_store_state(p, active, a, n, sl, st);
+        if (active) {
+            r.obs_pos[sl] = l.pos[e * A + a];
+            if (a == 0) {
+                r.obs_src[n] = l.src[e];
+                r.ret[n] = ret;
+                r.ts[n] = ts;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// First pass of the gradient: partial[b][j] = sum over the pairs of block b (ascending) of diffed[p] * z_{g,p,j}, in f64.
+// One thread per (block, Philox counter q = j / 4).
+__global__ __launch_bounds__(kBlock) void fe_evo_gradient_partial_kernel(uint64_t seed, uint32_t g, int64_t num_pairs,
+                                                                         int64_t P, const float *diffed, double *partial) {
+    const int64_t nq = (P + 3) / 4;
+    const int64_t blocks = (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= nq * blocks) return;
+    const int64_t b = t / nq, q = t - b * nq;
+    const int64_t p0 = b * kEvoGradPairs;
+    const int64_t p1 = p0 + kEvoGradPairs < num_pairs ? p0 + kEvoGradPairs : num_pairs;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t pp = p0; pp < p1; ++pp) {
+        const float4 z = evo_z4(seed, g, pp, (uint32_t)q);
+        const double d = (double)diffed[pp];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fma(d, (double)f4get(z, i), acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (4 * q + i < P) partial[b * P + 4 * q + i] = acc[i];
+}
+
+// Second pass: out[j] = sum over the blocks (ascending) of partial[b][j].
+__global__ __launch_bounds__(kBlock) void fe_evo_gradient_reduce_kernel(int64_t blocks, int64_t P, const double *partial,
+                                                                        double *out) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= P) return;
+    double acc = 0.0;
+    for (int64_t b = 0; b < blocks; ++b) acc += partial[b * P + j];
+    out[j] = acc;
+}
+
+// out[i][j] = z_{g, pairs[i], j} for j < P: the noise as the rollout and the gradient see it.
+__global__ __launch_bounds__(kBlock) void fe_evo_noise_kernel(uint64_t seed, uint32_t g, const int64_t *pairs, int64_t count,
+                                                              int64_t P, float *out) {
+    const int64_t nq = (P + 3) / 4;
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= nq * count) return;
+    const int64_t i = t / nq, q = t - i * nq;
+    const float4 z = evo_z4(seed, g, pairs[i], (uint32_t)q);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * q + k < P) out[i * P + 4 * q + k] = f4get(z, k);
+}
+
+}  // namespace

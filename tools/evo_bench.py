@@ -1,0 +1,126 @@
+"""GPU box: env-steps/s of the fused ES population (finenvs_amd.evo, one launch per K steps, noise generated in the
+kernel) against a torch restatement of the reference's loop on the same GPU: ParallelMLP's per-env weight copies and
+batched matmul (parallel_mlp.py:84-156) + env.step, with and without EvoAgent.store's per-step nonzero() / .item()
+(evo_agent.py:96-112).
+
+    timeout -k 10 600 python tools/evo_bench.py [--envs 16384] [--window 16] [--hidden 64] [--steps 32] [--assets 1]
+
+Prints one line per arm and a final JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import finenvs_amd  # noqa: E402
+from bench import make_series  # noqa: E402
+from finenvs_amd.evo import FusedEvoAgent  # noqa: E402
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--window", type=int, default=16)
+    ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--assets", type=int, default=1)
+    ap.add_argument("--eval-envs", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    N, W, H, K, A, E = a.envs, a.window, a.hidden, a.steps, a.assets, a.eval_envs
+    prices, day_id, _ = make_series(A)
+
+    def make_env():
+        return finenvs_amd.TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=W, num_envs=N, redraw="device",
+                                         obs_buffers=2)
+
+    out = {"envs": N, "window": W, "hidden": H, "steps_per_launch": K, "assets": A}
+    # ---- fused
+    env = make_env()
+    agent = FusedEvoAgent(env, hidden_dim=H, num_eval_envs=E, max_episodes=64)
+    pop = agent.population
+    fused_ms = timed(lambda: pop.run(K), a.reps) / K
+    out["fused_us_per_step"] = 1e3 * fused_ms
+    out["fused_env_steps_per_s"] = N / (fused_ms * 1e-3)
+    print(f"fused population     : {1e3 * fused_ms:9.1f} us/step  {out['fused_env_steps_per_s']:.3e} env-steps/s")
+    gz = torch.randn((pop.num_pairs,), device=env._dev)
+    out["gradient_ms"] = timed(lambda: pop.gradient(gz), 3)
+    print(f"gradient kernel      : {out['gradient_ms']:9.3f} ms per generation")
+    del agent, pop, env
+    torch.cuda.empty_cache()
+
+    # ---- torch restatement of ParallelMLP + env.step (+ EvoAgent.store)
+    env = make_env()
+    dev = env._dev
+    n_train, half = N - E, (N - E) // 2
+    torch.manual_seed(0)
+    shapes = [(5 * W, H), (H, 1)]
+    layers = [(torch.randn(s, device=dev) * (2 / s[0]) ** 0.5, torch.randn((1, s[1]), device=dev) * (2 / s[0]) ** 0.5) for s in shapes]
+
+    def perturb():
+        pw = []
+        for w, b in layers:
+            eps_w = torch.normal(0, 0.02, (half, *w.shape), device=dev)
+            eps_b = torch.normal(0, 0.02, (half, *b.shape), device=dev)
+            zw, zb = torch.zeros((E, *w.shape), device=dev), torch.zeros((E, *b.shape), device=dev)
+            pw.append((w.repeat((N, 1, 1)) + torch.cat([eps_w, -eps_w, zw]), b.repeat((N, 1, 1)) + torch.cat([eps_b, -eps_b, zb])))
+        return pw
+
+    pw = perturb()
+    state = {"obs": env.reset()}
+    cur_ret = torch.zeros((N,), device=dev)
+    cur_ts = torch.zeros((N,), device=dev)
+
+    def torch_steps(store):
+        with torch.no_grad():
+            for _ in range(K):
+                x = state["obs"].float()
+                acts = []
+                for aa in range(A):
+                    c = x[:, :, 5 * aa:5 * aa + 5].reshape(N, 1, 5 * W)
+                    for (w, b) in pw:
+                        c = torch.tanh(torch.matmul(c, w) + b)
+                    acts.append(c.reshape(N))
+                act = torch.stack(acts, 1)
+                noise = torch.normal(0, 0.01, act.shape, device=dev)
+                noise[-E:, :] = 0
+                act.add_(noise)
+                state["obs"], rew, done, _ = env.step(act)
+                if store:
+                    cur_ts.add_(1)
+                    cur_ret.add_(rew)
+                    idx = torch.squeeze(done.nonzero(), 1)
+                    _ = cur_ts[idx].sum().item()
+                    cur_ret[idx] = 0
+                    cur_ts[idx] = 0
+
+    t_ms = timed(lambda: torch_steps(False), max(1, a.reps // 2)) / K
+    out["torch_us_per_step"] = 1e3 * t_ms
+    print(f"torch ParallelMLP    : {1e3 * t_ms:9.1f} us/step  {N / (t_ms * 1e-3):.3e} env-steps/s")
+    ts_ms = timed(lambda: torch_steps(True), max(1, a.reps // 2)) / K
+    out["torch_store_us_per_step"] = 1e3 * ts_ms
+    print(f"torch + agent.store  : {1e3 * ts_ms:9.1f} us/step  {N / (ts_ms * 1e-3):.3e} env-steps/s")
+    out["perturb_ms"] = timed(perturb, 3)
+    print(f"torch perturb (once per generation): {out['perturb_ms']:.3f} ms")
+    out["speedup_vs_torch"] = t_ms / fused_ms
+    out["speedup_vs_torch_store"] = ts_ms / fused_ms
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
