@@ -106,6 +106,24 @@ EVO_SIGNATURES = {
     "fe_evo_noise": (C.c_int, [C.c_uint64, C.c_uint32, _vp, _i64, _i64, _vp, _vp]),
 }
 
+
+# include/finenvs_amd_replay.h: the off-policy replay ring (finenvs_amd/replay.py; same library)
+class FeReplayRing(C.Structure):
+    """struct fe_replay_ring of include/finenvs_amd_replay.h."""
+
+    _fields_ = [
+        ("capacity", C.c_int64), ("num_assets", C.c_int32), ("reserved", C.c_int32),
+        ("state_src", _vp), ("state_pos", _vp), ("next_src", _vp), ("next_pos", _vp), ("actions", _vp),
+        ("rewards", _vp), ("dones", _vp), ("errors", _vp),
+    ]
+
+
+REPLAY_SIGNATURES = {
+    "fe_replay_append": (C.c_int, [C.POINTER(FeReplayRing), _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _i32, _vp, _vp, _vp]),
+    "fe_replay_sample": (C.c_int, [_vp, C.POINTER(FeReplayRing), _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -130,7 +148,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                 "finenvs_amd has no CPU fallback"
             ) from exc
     lib = C.CDLL(p)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -25,7 +25,7 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, eight files:
+// One translation unit, nine files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
@@ -33,6 +33,7 @@
 //   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA)
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
+//   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_env.hip            (this file) launch geometry, the env object, the C ABI of include/finenvs_amd.h
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
@@ -53,6 +54,7 @@
 #include "finenvs_amd.h"
 #include "finenvs_amd_ext.h"
 #include "finenvs_amd_evo.h"
+#include "finenvs_amd_replay.h"
 
 #include "fe_device_common.h"
 #include "fe_step_kernel.h"
@@ -60,6 +62,7 @@
 #include "fe_lstm_kernel.h"
 #include "fe_aux_kernels.h"
 #include "fe_evo_kernels.h"
+#include "fe_replay_kernels.h"
 
 namespace {
 
@@ -1191,6 +1194,116 @@ int fe_evo_noise(uint64_t seed, uint32_t generation, const int64_t *pairs, int64
                        (hipStream_t)stream, seed, generation, pairs, count, num_params, out);
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) return hip_fail(he, "fe_evo_noise launch");
+    return FE_OK;
+}
+
+// ---- include/finenvs_amd_replay.h: the off-policy replay ring ----
+
+static bool replay_ring_ok(const fe_replay_ring *ring) {
+    return ring && ring->capacity >= 1 && ring->num_assets >= 1 && ring->state_src && ring->state_pos &&
+           ring->next_src && ring->next_pos && ring->actions && ring->rewards && ring->dones && ring->errors;
+}
+
+static ReplayRing replay_view(const fe_replay_ring *ring) {
+    ReplayRing r;
+    r.s_src = ring->state_src; r.s_pos = ring->state_pos; r.n_src = ring->next_src; r.n_pos = ring->next_pos;
+    r.act = ring->actions; r.rew = ring->rewards; r.done = ring->dones;
+    r.C = ring->capacity; r.A = ring->num_assets;
+    return r;
+}
+
+int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, int64_t num_envs, int64_t row_stride,
+                     int64_t first, int64_t count, const int64_t *state_src, const double *state_pos,
+                     const int64_t *next_src, const double *next_pos, const void *actions, int32_t actions_are_f64,
+                     const double *rewards, const int32_t *dones, void *stream) {
+    if (!replay_ring_ok(ring) || !state_src || !state_pos || !next_src || !next_pos || !actions || !rewards || !dones)
+        return fail(FE_ERR_ARG, "fe_replay_append: null argument");
+    const int64_t C = ring->capacity;
+    if (steps < 1 || num_envs < 1 || row_stride < num_envs || first < 0 || count < 1 || count > C || head < 0 ||
+        head >= C || first + count > steps * num_envs)
+        return fail(FE_ERR_ARG, "fe_replay_append: bad range (steps %lld, num_envs %lld, row_stride %lld, first %lld, "
+                    "count %lld, head %lld, capacity %lld)", (long long)steps, (long long)num_envs, (long long)row_stride,
+                    (long long)first, (long long)count, (long long)head, (long long)C);
+    DeviceGuard guard(device_of(ring->rewards));
+    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_replay_append: the ring is not device memory");
+    const ReplayRing r = replay_view(ring);
+    const bool single = r.A == 1;
+    dim3 g(grid_for(count * r.A)), b(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+#define FE_APPEND(S, F) \
+    hipLaunchKernelGGL((fe_replay_append_kernel<S, F>), g, b, 0, st, r, head, first, count, num_envs, row_stride, \
+                       state_src, state_pos, next_src, next_pos, actions, rewards, dones)
+    if (single) {
+        if (actions_are_f64) FE_APPEND(true, true);
+        else FE_APPEND(true, false);
+    } else {
+        if (actions_are_f64) FE_APPEND(false, true);
+        else FE_APPEND(false, false);
+    }
+#undef FE_APPEND
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "fe_replay_append launch");
+    return FE_OK;
+}
+
+int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
+                     int64_t count, float *states, float *next_states, float *actions, float *rewards, float *dones,
+                     void *stream) {
+    if (!env || !replay_ring_ok(ring) || !indices || !states || !next_states || !actions || !rewards || !dones || count < 0)
+        return fail(FE_ERR_ARG, "fe_replay_sample: bad argument");
+    const int64_t C = ring->capacity;
+    if (size < 1 || size > C || head < 0 || head >= C)
+        return fail(FE_ERR_ARG, "fe_replay_sample: size %lld / head %lld do not describe a non-empty ring of %lld slots",
+                    (long long)size, (long long)head, (long long)C);
+    if (ring->num_assets != env->p.A)
+        return fail(FE_ERR_ARG, "fe_replay_sample: the ring holds %d assets, the env %d", (int)ring->num_assets,
+                    (int)env->p.A);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    Params p = env->p;
+    const int A = p.A;
+    const int64_t WA = (int64_t)p.W * A;
+    // Tile = EB samples.  A workgroup iteration of stream_tile<float> turns 4 x 256 tuples: a tile is a whole number of
+    // them where the LDS allows (two descriptor tiles of EB (8 + 8A) bytes each, kept within 32 KiB), and there are
+    // about four tiles per CU.
+    int64_t cap = 2048 / (1 + A);
+    if (cap < 1) cap = 1;
+    int64_t gcd = 4 * (kStageBytes / 20), w = WA;
+    while (w) { const int64_t t = gcd % w; gcd = w; w = t; }
+    const int64_t unit = 4 * (kStageBytes / 20) / gcd;  // samples per whole workgroup iteration
+    int64_t EB = (count + 4 * (int64_t)env->cus - 1) / (4 * (int64_t)env->cus);
+    if (unit <= cap) EB = EB <= unit ? unit : EB - EB % unit;
+    if (EB > cap) EB = cap;
+    if (EB < 1) EB = 1;
+    p.N = count;
+    p.EB = (int32_t)EB;
+    p.num_tiles = (count + EB - 1) / EB;
+    p.obs_stream = 0;  // a minibatch is read by the learner right away: keep it in the Infinity Cache
+    const int64_t grid = p.num_tiles < 8 * (int64_t)env->cus ? p.num_tiles : 8 * (int64_t)env->cus;
+    const size_t lds = replay_lds_bytes((int)EB, A);
+    const ReplayRing r = replay_view(ring);
+    const int64_t start = ((head - size) % C + C) % C;
+    const int env_elems = (int)p.env_elems;
+    const int vec = env_elems % 4 == 0 ? 4 : (env_elems % 2 == 0 ? 2 : 1);
+    const bool single = A == 1;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long *err = reinterpret_cast<unsigned long long *>(ring->errors);
+#define FE_SAMPLE(V, S)                                                                                               \
+    hipLaunchKernelGGL((fe_replay_sample_kernel<V, S>), dim3((unsigned)grid), dim3(kBlock), lds, st, p, r, indices,    \
+                       start, size, states, next_states, actions, rewards, dones, err)
+    if (single) {
+        if (vec == 4) FE_SAMPLE(4, true);
+        else if (vec == 2) FE_SAMPLE(2, true);
+        else FE_SAMPLE(1, true);
+    } else {
+        if (vec == 4) FE_SAMPLE(4, false);
+        else if (vec == 2) FE_SAMPLE(2, false);
+        else FE_SAMPLE(1, false);
+    }
+#undef FE_SAMPLE
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return hip_fail(he, "fe_replay_sample launch");
     return FE_OK;
 }
 
