@@ -53,13 +53,21 @@ constexpr bool kHoistFirst = FE_HOIST_FIRST != 0 && (sizeof(OT) == 8 || FE_F32_W
 
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...) {
+}  // namespace
+
+// Records the message fe_last_error returns and passes `code` through.  fe_csv.cpp calls it by this name: hidden
+// visibility keeps it internal to the library, not an exported symbol.
+extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
 }
+
+namespace {
+
+constexpr auto &fail = fe_set_error;
 
 int hip_fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));

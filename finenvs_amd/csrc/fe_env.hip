@@ -34,7 +34,9 @@
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
-//   fe_env.hip            (this file) launch geometry, the env object, the C ABI of include/finenvs_amd.h
+//   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
+//                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
+//                         four headers in include/
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
 // reference's mixed f32/f64 tensor arithmetic; this file
@@ -49,6 +51,7 @@
 
 #include <atomic>
 #include <new>
+#include <numeric>
 #include <type_traits>
 
 #include "finenvs_amd.h"
@@ -66,12 +69,49 @@
 
 namespace {
 
+// Largest grid of the grid-strided element-wise launches and of the tile-looping rollouts.
+constexpr int64_t kMaxGrid = 8 * 256;
+// Dynamic LDS a workgroup can have: the MLP, evo and split-LSTM launches refuse more, each with its own message.
+constexpr size_t kMaxLds = 160 * 1024;
+
+int64_t capped_grid(int64_t tiles) { return tiles < kMaxGrid ? tiles : kMaxGrid; }
+
 int grid_for(int64_t work_items) {
-    int64_t g = (work_items + kBlock - 1) / kBlock;
-    if (g < 1) g = 1;
-    if (g > 256 * 8) g = 256 * 8;
-    return (int)g;
+    const int64_t g = (work_items + kBlock - 1) / kBlock;
+    return (int)(g < 1 ? 1 : capped_grid(g));
 }
+
+// Observation elements per 16-byte store: the widest that divides an env's observation (1 when its size is odd).
+int vec_width(int64_t env_elems, int elem_bytes) {
+    int vec = 16 / elem_bytes;
+    while (vec > 1 && env_elems % vec != 0) vec /= 2;
+    return vec;
+}
+
+// Compile-time dispatch.  with_bool calls f(std::true_type) or f(std::false_type); with_layout calls f(OT{}, VEC) for the
+// observation layouts that exist (float x 4 / 2 / 1, double x 2 / 1), VEC a std::integral_constant.  Callers name the
+// instantiation as kernel<decltype(ot), decltype(V)::value, decltype(S)::value>: only the templates a call site names get
+// instantiated.
+template <class F>
+auto with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+auto with_layout(bool f32, int vec, F &&f) {
+    using V1 = std::integral_constant<int, 1>;
+    using V2 = std::integral_constant<int, 2>;
+    if (f32) return vec == 4 ? f(float{}, std::integral_constant<int, 4>{}) : (vec == 2 ? f(float{}, V2{}) : f(float{}, V1{}));
+    return vec == 2 ? f(double{}, V2{}) : f(double{}, V1{});
+}
+
+// The launch epilogue: FE_OK, or FE_ERR_HIP with "<who> launch: <HIP error>".  `he` is what hipLaunchKernel returned; after
+// hipLaunchKernelGGL, which returns nothing, the one-argument form asks hipGetLastError.
+int launched(const char *who, hipError_t he) {
+    return he == hipSuccess ? FE_OK : fail(FE_ERR_HIP, "%s launch: %s", who, hipGetErrorString(he));
+}
+
+int launched(const char *who) { return launched(who, hipGetLastError()); }
 
 }  // namespace
 
@@ -115,6 +155,8 @@ struct DeviceGuard {
     ~DeviceGuard() {
         if (switched) (void)hipSetDevice(prev);
     }
+    // The device prologue of an entry point: `if (int rc = guard.status()) return rc;`
+    int status(const char *what = "hipSetDevice") const { return err == hipSuccess ? FE_OK : hip_fail(err, what); }
     DeviceGuard(const DeviceGuard &) = delete;
     DeviceGuard &operator=(const DeviceGuard &) = delete;
 };
@@ -128,6 +170,17 @@ static int device_of(const void *ptr) {
     }
     if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged) return -1;
     return attr.device;
+}
+
+static int require_bound(const fe_env *env, const char *who) {
+    return env->bound ? FE_OK : fail(FE_ERR_STATE, "%s: state not bound", who);
+}
+
+// Frees what fe_env_create allocated, and the env; the env's device is current.
+static void release_env(fe_env *env) {
+    if (env->owned_logret) (void)hipFree(env->owned_logret);
+    if (env->ticket) (void)hipFree(env->ticket);
+    delete env;
 }
 
 // Host-side preparation of kernels with more than the default 64 KiB of dynamic LDS, done once instead of per call:
@@ -180,17 +233,48 @@ static hipError_t prepare_kernel(int device, const void *kern, int block, size_t
     return he;
 }
 
+// The big-LDS path of the MLP, evo and split-LSTM rollouts (the caller has refused lds > kMaxLds in its own words):
+// prepare_kernel for a kBlock-thread launch, its failure reported as "<who>: hipFuncSetAttribute: <HIP error>" ...
+static int prepare_big_lds(int device, const void *kern, size_t lds, const char *who) {
+    const hipError_t he = prepare_kernel(device, kern, kBlock, lds, nullptr);
+    return he == hipSuccess ? FE_OK : fail(FE_ERR_HIP, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(he));
+}
+
+// ... then the launch of a kernel that takes (Params, its argument block).
+template <class Args>
+static int launch_big_lds(int device, const void *kern, int64_t grid, size_t lds, Params &p, Args &r, void *stream,
+                          const char *who) {
+    if (int rc = prepare_big_lds(device, kern, lds, who)) return rc;
+    void *args[] = {&p, &r};
+    return launched(who, hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), args, lds, (hipStream_t)stream));
+}
+
+// Tile geometry of the fused rollouts that keep one workgroup per tile (linear, table, MLP, split-LSTM accounting): state
+// lives in HBM between steps but every tile is revisited by the same workgroup, so a grid of one workgroup per tile
+// (capped) keeps the K-step loop entirely inside the launch.  `eb` is the rollout's own tile, at most kBlock / A sleeves.
+// fe_env_set_launch(rollout_tile_envs) either replaces it (`replace`: linear, MLP) or may only shrink it (table, split
+// LSTM).  Sets p.EB and p.num_tiles and returns the grid.
+static int64_t rollout_geometry(const fe_env *env, Params &p, int64_t eb, bool replace) {
+    const int64_t cap = kBlock / p.A > 0 ? kBlock / p.A : 1;
+    if (eb > cap) eb = cap;
+    const int64_t tile_override = env->rollout_tile_override;
+    if (tile_override > 0 && (replace || tile_override < eb)) eb = tile_override < cap ? tile_override : cap;
+    p.EB = (int)eb;
+    p.num_tiles = (p.N + eb - 1) / eb;
+    return capped_grid(p.num_tiles);
+}
+
 // The kernel instantiation a given env dispatches to (shared by launch and occupancy query).  FORM (fe_step_kernel.h):
 // kFull = the launch has optional outputs (evaluate-mode bookkeeping, episode statistics, trajectory descriptors), kLean =
 // none of them (the action copy of fe_env_step_traj is written by every form), kNotify = lean + the host flag of
 // fe_env_step_notify; same launch bounds, same LDS.
 template <bool RESET_ONLY, int FORM>
 static const void *kernel_for(bool f32, int vec, bool single) {
-#define FE_PICK(OT, VEC) \
-    (single ? (const void *)fe_env_kernel<OT, VEC, true, RESET_ONLY, FORM> : (const void *)fe_env_kernel<OT, VEC, false, RESET_ONLY, FORM>)
-    if (f32) return vec == 4 ? FE_PICK(float, 4) : (vec == 2 ? FE_PICK(float, 2) : FE_PICK(float, 1));
-    return vec == 2 ? FE_PICK(double, 2) : FE_PICK(double, 1);
-#undef FE_PICK
+    return with_layout(f32, vec, [=](auto ot, auto V) {
+        return with_bool(single, [](auto S) {
+            return (const void *)fe_env_kernel<decltype(ot), decltype(V)::value, decltype(S)::value, RESET_ONLY, FORM>;
+        });
+    });
 }
 
 // fe_env_step_promoted: the step kernel with the promoted arithmetic, full forms only.  `pipelined`: the single-asset
@@ -199,12 +283,13 @@ static const void *kernel_for(bool f32, int vec, bool single) {
 // wavefronts per SIMD: it spilled).
 template <int FORM>
 static const void *promoted_kernel_for(bool f32, int vec, bool pipelined) {
-#define FE_LOOP(OT, VEC) ((const void *)fe_env_promoted_kernel<OT, VEC, false, FORM>)
-    if (f32) return vec == 4 ? FE_LOOP(float, 4) : (vec == 2 ? FE_LOOP(float, 2) : FE_LOOP(float, 1));
-    if (pipelined)
-        return vec == 2 ? (const void *)fe_env_promoted_kernel<double, 2, true, FORM> : (const void *)fe_env_promoted_kernel<double, 1, true, FORM>;
-    return vec == 2 ? FE_LOOP(double, 2) : FE_LOOP(double, 1);
-#undef FE_LOOP
+    return with_layout(f32, vec, [=](auto ot, auto V) {
+        using OT = decltype(ot);
+        if constexpr (std::is_same<OT, double>::value) {
+            if (pipelined) return (const void *)fe_env_promoted_kernel<double, decltype(V)::value, true, FORM>;
+        }
+        return (const void *)fe_env_promoted_kernel<OT, decltype(V)::value, false, FORM>;
+    });
 }
 
 // Per-call pointers go into a local copy of the parameter block: the env object itself is not
@@ -227,7 +312,7 @@ static int launch_env(const fe_env *env, const float *actions, void *obs, double
     p.has_stats = p.run_ret != nullptr ? 1 : 0;
     void *args[] = {&p};
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     const bool f32 = env->cfg.obs_is_f32 != 0, single = p.A == 1;
     // (the action copy alone does not need the full form: every form writes it)
     const bool full = !RESET_ONLY && (p.evaluate || p.run_ret || desc_src);
@@ -250,9 +335,28 @@ static int launch_env(const fe_env *env, const float *actions, void *obs, double
         const void *prev = env->last_obs.exchange(obs, std::memory_order_relaxed);
         if (p.obs_stream && prev == obs && (size_t)p.N * p.env_elems * (f32 ? 4 : 8) <= (256ull << 20)) p.obs_stream = 0;
     }
-    hipError_t he = hipLaunchKernel(kern, dim3(env->grid), dim3(kBlock), args, lds, st);
-    if (he != hipSuccess) return hip_fail(he, RESET_ONLY ? "fe_env_reset_obs launch" : "fe_env_step launch");
-    return FE_OK;
+    return launched(RESET_ONLY ? "fe_env_reset_obs" : "fe_env_step", hipLaunchKernel(kern, dim3(env->grid), dim3(kBlock), args, lds, st));
+}
+
+// The step entry points: their shared checks, then the launch.  `who` names the entry point.  Every form is
+// fe_env_step_promoted with f32 actions (actions_are_f64 = 0: its two f64 checks pass) except for the kernel choice,
+// `promoted`.  host_flag != null (a notify form) needs the eval env on this shard.
+static int step_checked(fe_env *env, const char *who, bool promoted, const void *actions, int32_t actions_are_f64, void *obs,
+                        double *rewards, int32_t *dones, float *actions_store_out, int64_t *obs_src_out, double *obs_pos_out,
+                        uint64_t *host_flag, uint64_t seq, void *stream) {
+    if (!env || !actions || !obs || !rewards || !dones) return fail(FE_ERR_ARG, "%s: null argument", who);
+    if (actions_are_f64 != 0 && actions_are_f64 != 1) return fail(FE_ERR_ARG, "%s: actions_are_f64 must be 0 or 1", who);
+    if ((obs_src_out == nullptr) != (obs_pos_out == nullptr))
+        return fail(FE_ERR_ARG, "%s: obs_src_out and obs_pos_out go together", who);
+    if (actions_store_out && actions_are_f64)
+        return fail(FE_ERR_ARG, "%s: actions_store_out is an f32 copy; f64 actions have none", who);
+    if (actions_store_out == actions) actions_store_out = nullptr;  // already where they belong
+    if (int rc = require_bound(env, who)) return rc;
+    if (host_flag && env->p.eval_env < 0 && !env->cfg.evaluate)
+        return fail(FE_ERR_ARG, "%s: this training-mode env has no evaluation env (a shard that does not own it)", who);
+    if (promoted) env->promoted_used = true;
+    return launch_env<false>(env, reinterpret_cast<const float *>(actions), obs, rewards, dones, (hipStream_t)stream, obs_src_out,
+                             obs_pos_out, actions_store_out, host_flag, seq, promoted ? actions_are_f64 : -1);
 }
 
 // Launch geometry of the step / reset kernels: tile size EB, tile count, grid, dynamic LDS.
@@ -286,9 +390,7 @@ static int configure_launch(fe_env *env) {
         // geometry), f32 observations (half the bytes, a 17-19 us launch) with 6 per CU and 1-2 longer tiles each
         // (17.4 us vs 19.4 us).
         const int64_t wg_tuples = 4 * (kStageBytes / (5 * (cfg.obs_is_f32 ? 4 : 8)));
-        int64_t g = wg_tuples, w = cfg.W;
-        while (w) { const int64_t t = g % w; g = w; w = t; }  // gcd(wg_tuples, W)
-        const int64_t unit = wg_tuples / g;                  // envs per whole workgroup iteration
+        const int64_t unit = wg_tuples / std::gcd(wg_tuples, (int64_t)cfg.W);  // envs per whole workgroup iteration
         if (unit <= cap) {
             wgs_per_cu = cfg.obs_is_f32 ? (env->vec == 4 ? kF32StepWaves<float, 4> : kF32StepWaves<float, 1>) : 4;
             const int64_t res = (int64_t)env->cus * wgs_per_cu;
@@ -338,112 +440,35 @@ static int configure_launch(fe_env *env) {
     return FE_OK;
 }
 
-extern "C" {
 
-// shared with fe_csv.cpp: internal to the library (hidden visibility, not an exported symbol)
-__attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int fe_version(void) { return FE_ABI_VERSION; }
-
-const char *fe_last_error(void) { return g_err; }
-
-int fe_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    return n;
-}
-
-int fe_env_create(const fe_config *cfg, const double *prices, const double *logret, fe_env **out) {
-    if (!cfg || !out) return fail(FE_ERR_ARG, "fe_env_create: null argument");
-    if (!prices) return fail(FE_ERR_ARG, "fe_env_create: the price table is required");
-    if (cfg->N < 1 || cfg->D < 1) return fail(FE_ERR_ARG, "fe_env_create: N=%lld D=%lld must be >= 1", (long long)cfg->N, (long long)cfg->D);
-    if (cfg->W < 1 || cfg->L <= cfg->W)
-        return fail(FE_ERR_ARG, "fe_env_create: need 1 <= W < L (W=%lld, L=%lld)", (long long)cfg->W, (long long)cfg->L);
-    if (cfg->A < 1 || cfg->A > FE_MAX_ASSETS)
-        return fail(FE_ERR_ARG, "fe_env_create: A=%lld outside 1..%lld", (long long)cfg->A, (long long)FE_MAX_ASSETS);
-    if (cfg->max_shares < 0) return fail(FE_ERR_ARG, "fe_env_create: max_shares < 0");
-    if (cfg->redraw_mode != 0 && cfg->redraw_mode != 1) return fail(FE_ERR_ARG, "fe_env_create: redraw_mode must be 0 or 1");
-    if (cfg->eval_env >= cfg->N) return fail(FE_ERR_ARG, "fe_env_create: eval_env out of range");
-    const int64_t env_elems = (int64_t)cfg->W * 5 * cfg->A;
-    if (env_elems > (1ll << 24)) return fail(FE_ERR_ARG, "fe_env_create: W*5*A too large");
-    int ndev = 0;
-    hipError_t he = hipGetDeviceCount(&ndev);
-    if (he != hipSuccess || ndev < 1) {
-        (void)hipGetLastError();
-        return fail(FE_ERR_HIP, "fe_env_create: no HIP device (this library has no CPU path)");
-    }
-    // the env lives where its tables live, whatever the caller's current device is
-    const int dev = device_of(prices);
-    if (dev < 0 || dev >= ndev) return fail(FE_ERR_ARG, "fe_env_create: prices is not a device pointer");
-    if (logret && device_of(logret) != dev)
-        return fail(FE_ERR_ARG, "fe_env_create: prices and logret live on different devices");
-    DeviceGuard guard(dev);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
-    hipDeviceProp_t prop;
-    if ((he = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return hip_fail(he, "hipGetDeviceProperties");
-
-    fe_env *env = new (std::nothrow) fe_env();
-    if (!env) return fail(FE_ERR_ARG, "fe_env_create: out of host memory");
-    env->cfg = *cfg;
-    env->bound = false;
-    env->device = dev;
-    env->owned_logret = nullptr;
-    env->ticket = nullptr;
+// fe_env_create past its argument checks, with the env's device current: the device allocations, the launch geometry and
+// the parameter block.  On failure the caller releases the env.
+static int init_env(fe_env *env, const double *prices, const double *logret, int cus) {
+    const fe_config *cfg = &env->cfg;
+    hipError_t he;
     if (cfg->evaluate) {
-        if ((he = hipMalloc(&env->ticket, sizeof(unsigned int))) != hipSuccess || (he = hipMemset(env->ticket, 0, sizeof(unsigned int))) != hipSuccess) {
-            if (env->ticket) (void)hipFree(env->ticket);
-            delete env;
+        if ((he = hipMalloc(&env->ticket, sizeof(unsigned int))) != hipSuccess || (he = hipMemset(env->ticket, 0, sizeof(unsigned int))) != hipSuccess)
             return hip_fail(he, "fe_env_create: hipMalloc(ticket)");
-        }
     }
     if (!logret) {
         // logret = NULL: compute the table from the prices (the one allocation this library owns)
         const int64_t tuples = cfg->D * cfg->L * (int64_t)cfg->A;
-        if ((he = hipMalloc(&env->owned_logret, (size_t)tuples * 32)) != hipSuccess) {
-            if (env->ticket) (void)hipFree(env->ticket);
-            delete env;
-            return hip_fail(he, "fe_env_create: hipMalloc(logret)");
-        }
+        if ((he = hipMalloc(&env->owned_logret, (size_t)tuples * 32)) != hipSuccess) return hip_fail(he, "fe_env_create: hipMalloc(logret)");
         hipLaunchKernelGGL(fe_logret_tables_kernel, dim3(grid_for(tuples)), dim3(kBlock), 0, (hipStream_t) nullptr,
                            prices, env->owned_logret, cfg->D, cfg->L, cfg->A);
         he = hipGetLastError();
         if (he == hipSuccess) he = hipStreamSynchronize(nullptr);
-        if (he != hipSuccess) {
-            (void)hipFree(env->owned_logret);
-            if (env->ticket) (void)hipFree(env->ticket);
-            delete env;
-            return hip_fail(he, "fe_env_create: log-return table");
-        }
+        if (he != hipSuccess) return hip_fail(he, "fe_env_create: log-return table");
         logret = env->owned_logret;
     }
     const int A = cfg->A;
-    const int elem_bytes = cfg->obs_is_f32 ? 4 : 8;
-    int vec = 16 / elem_bytes;
-    while (vec > 1 && env_elems % vec != 0) vec /= 2;
-    env->vec = vec;
-    env->cus = prop.multiProcessorCount;
-    env->tile_override = 0;
-    env->grid_override = 0;
-    env->rollout_tile_override = 0;
+    const int64_t env_elems = (int64_t)cfg->W * 5 * cfg->A;
+    env->vec = vec_width(env_elems, cfg->obs_is_f32 ? 4 : 8);
+    env->cus = cus;
     Params &p = env->p;
-    memset(&p, 0, sizeof(p));
     p.N = cfg->N;
     p.A = A;
-    if (int rc = configure_launch(env)) {
-        if (env->owned_logret) (void)hipFree(env->owned_logret);
-        if (env->ticket) (void)hipFree(env->ticket);
-        delete env;
-        return rc;
-    }
+    if (int rc = configure_launch(env)) return rc;
     p.ticket = env->ticket;
     p.P = prices;
     p.LR = logret;
@@ -470,6 +495,60 @@ int fe_env_create(const fe_config *cfg, const double *prices, const double *logr
     p.imr = cfg->init_margin;
     p.one_mmr = 1.0 + cfg->maint_margin;
     p.S = cfg->starting_balance;
+    return FE_OK;
+}
+
+extern "C" {
+
+int fe_version(void) { return FE_ABI_VERSION; }
+
+const char *fe_last_error(void) { return g_err; }
+
+int fe_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return n;
+}
+
+int fe_env_create(const fe_config *cfg, const double *prices, const double *logret, fe_env **out) {
+    if (!cfg || !out) return fail(FE_ERR_ARG, "fe_env_create: null argument");
+    if (!prices) return fail(FE_ERR_ARG, "fe_env_create: the price table is required");
+    if (cfg->N < 1 || cfg->D < 1) return fail(FE_ERR_ARG, "fe_env_create: N=%lld D=%lld must be >= 1", (long long)cfg->N, (long long)cfg->D);
+    if (cfg->W < 1 || cfg->L <= cfg->W)
+        return fail(FE_ERR_ARG, "fe_env_create: need 1 <= W < L (W=%lld, L=%lld)", (long long)cfg->W, (long long)cfg->L);
+    if (cfg->A < 1 || cfg->A > FE_MAX_ASSETS)
+        return fail(FE_ERR_ARG, "fe_env_create: A=%lld outside 1..%lld", (long long)cfg->A, (long long)FE_MAX_ASSETS);
+    if (cfg->max_shares < 0) return fail(FE_ERR_ARG, "fe_env_create: max_shares < 0");
+    if (cfg->redraw_mode != 0 && cfg->redraw_mode != 1) return fail(FE_ERR_ARG, "fe_env_create: redraw_mode must be 0 or 1");
+    if (cfg->eval_env >= cfg->N) return fail(FE_ERR_ARG, "fe_env_create: eval_env out of range");
+    if ((int64_t)cfg->W * 5 * cfg->A > (1ll << 24)) return fail(FE_ERR_ARG, "fe_env_create: W*5*A too large");
+    int ndev = 0;
+    hipError_t he = hipGetDeviceCount(&ndev);
+    if (he != hipSuccess || ndev < 1) {
+        (void)hipGetLastError();
+        return fail(FE_ERR_HIP, "fe_env_create: no HIP device (this library has no CPU path)");
+    }
+    // the env lives where its tables live, whatever the caller's current device is
+    const int dev = device_of(prices);
+    if (dev < 0 || dev >= ndev) return fail(FE_ERR_ARG, "fe_env_create: prices is not a device pointer");
+    if (logret && device_of(logret) != dev)
+        return fail(FE_ERR_ARG, "fe_env_create: prices and logret live on different devices");
+    DeviceGuard guard(dev);
+    if (int rc = guard.status()) return rc;
+    hipDeviceProp_t prop;
+    if ((he = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return hip_fail(he, "hipGetDeviceProperties");
+
+    fe_env *env = new (std::nothrow) fe_env();  // value-initialized: every field starts zero / null
+    if (!env) return fail(FE_ERR_ARG, "fe_env_create: out of host memory");
+    env->cfg = *cfg;
+    env->device = dev;
+    if (int rc = init_env(env, prices, logret, prop.multiProcessorCount)) {
+        release_env(env);
+        return rc;
+    }
     *out = env;
     return FE_OK;
 }
@@ -517,60 +596,41 @@ int fe_env_stats_reduce(fe_env *env, double *out, void *stream) {
     if (!env || !out) return fail(FE_ERR_ARG, "fe_env_stats_reduce: null argument");
     if (!env->p.stat_acc) return fail(FE_ERR_STATE, "fe_env_stats_reduce: no statistics bound (fe_env_bind_stats)");
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     hipLaunchKernelGGL(fe_stats_reduce_kernel, dim3(1), dim3(kStatsLanes), 0, (hipStream_t)stream, env->p.stat_acc, env->p.N, out);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_stats_reduce launch");
-    return FE_OK;
+    return launched("fe_env_stats_reduce");
 }
 
 int fe_env_reset_obs(fe_env *env, void *obs, void *stream) {
     if (!env || !obs) return fail(FE_ERR_ARG, "fe_env_reset_obs: null argument");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_reset_obs: state not bound");
+    if (int rc = require_bound(env, "fe_env_reset_obs")) return rc;
     return launch_env<true>(env, nullptr, obs, nullptr, nullptr, (hipStream_t)stream);
 }
 
 int fe_env_step(fe_env *env, const float *actions, void *obs, double *rewards, int32_t *dones, void *stream) {
-    if (!env || !actions || !obs || !rewards || !dones) return fail(FE_ERR_ARG, "fe_env_step: null argument");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_step: state not bound");
-    return launch_env<false>(env, actions, obs, rewards, dones, (hipStream_t)stream);
+    return step_checked(env, "fe_env_step", false, actions, 0, obs, rewards, dones, nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
 
 int fe_env_step_notify(fe_env *env, const float *actions, void *obs, double *rewards, int32_t *dones,
                        uint64_t *host_flag, uint64_t seq, void *stream) {
-    return fe_env_step_traj_notify(env, actions, obs, rewards, dones, nullptr, nullptr, nullptr, host_flag, seq, stream);
+    if (!host_flag) return fail(FE_ERR_ARG, "fe_env_step_notify: null argument");
+    return step_checked(env, "fe_env_step_notify", false, actions, 0, obs, rewards, dones, nullptr, nullptr, nullptr, host_flag, seq,
+                        stream);
 }
 
 int fe_env_step_traj_notify(fe_env *env, const float *actions, void *obs, double *rewards, int32_t *dones,
                             float *actions_store_out, int64_t *obs_src_out, double *obs_pos_out, uint64_t *host_flag,
                             uint64_t seq, void *stream) {
-    if (!env || !actions || !obs || !rewards || !dones || !host_flag) return fail(FE_ERR_ARG, "fe_env_step_notify: null argument");
-    if ((obs_src_out == nullptr) != (obs_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "fe_env_step_traj_notify: obs_src_out and obs_pos_out go together");
-    if (actions_store_out == actions) actions_store_out = nullptr;
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_step_notify: state not bound");
-    if (env->p.eval_env < 0 && !env->cfg.evaluate)
-        return fail(FE_ERR_ARG, "fe_env_step_notify: this training-mode env has no evaluation env (a shard that does not own it)");
-    return launch_env<false>(env, actions, obs, rewards, dones, (hipStream_t)stream, obs_src_out, obs_pos_out, actions_store_out,
-                             host_flag, seq);
+    if (!host_flag) return fail(FE_ERR_ARG, "fe_env_step_traj_notify: null argument");
+    return step_checked(env, "fe_env_step_traj_notify", false, actions, 0, obs, rewards, dones, actions_store_out, obs_src_out,
+                        obs_pos_out, host_flag, seq, stream);
 }
 
 int fe_env_step_promoted(fe_env *env, const void *actions, int32_t actions_are_f64, void *obs, double *rewards,
                          int32_t *dones, float *actions_store_out, int64_t *obs_src_out, double *obs_pos_out,
                          uint64_t *host_flag, uint64_t seq, void *stream) {
-    if (!env || !actions || !obs || !rewards || !dones) return fail(FE_ERR_ARG, "fe_env_step_promoted: null argument");
-    if (actions_are_f64 != 0 && actions_are_f64 != 1) return fail(FE_ERR_ARG, "fe_env_step_promoted: actions_are_f64 must be 0 or 1");
-    if ((obs_src_out == nullptr) != (obs_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "fe_env_step_promoted: obs_src_out and obs_pos_out go together");
-    if (actions_store_out && actions_are_f64)
-        return fail(FE_ERR_ARG, "fe_env_step_promoted: actions_store_out is an f32 copy; f64 actions have none");
-    if (actions_store_out == actions) actions_store_out = nullptr;
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_step_promoted: state not bound");
-    if (host_flag && env->p.eval_env < 0 && !env->cfg.evaluate)
-        return fail(FE_ERR_ARG, "fe_env_step_promoted: this training-mode env has no evaluation env (a shard that does not own it)");
-    env->promoted_used = true;
-    return launch_env<false>(env, reinterpret_cast<const float *>(actions), obs, rewards, dones, (hipStream_t)stream, obs_src_out,
-                             obs_pos_out, actions_store_out, host_flag, seq, actions_are_f64);
+    return step_checked(env, "fe_env_step_promoted", true, actions, actions_are_f64, obs, rewards, dones, actions_store_out,
+                        obs_src_out, obs_pos_out, host_flag, seq, stream);
 }
 
 int fe_host_flag_create(uint64_t **host_flag) {
@@ -591,28 +651,21 @@ int fe_host_flag_destroy(uint64_t *host_flag) {
 
 int fe_env_step_traj(fe_env *env, const float *actions, void *obs, double *rewards, int32_t *dones,
                      float *actions_store_out, int64_t *obs_src_out, double *obs_pos_out, void *stream) {
-    if (!env || !actions || !obs || !rewards || !dones) return fail(FE_ERR_ARG, "fe_env_step_traj: null argument");
-    if ((obs_src_out == nullptr) != (obs_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "fe_env_step_traj: obs_src_out and obs_pos_out go together");
-    if (actions_store_out == actions) actions_store_out = nullptr;  // already where they belong
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_step_traj: state not bound");
-    return launch_env<false>(env, actions, obs, rewards, dones, (hipStream_t)stream, obs_src_out, obs_pos_out, actions_store_out);
+    return step_checked(env, "fe_env_step_traj", false, actions, 0, obs, rewards, dones, actions_store_out, obs_src_out,
+                        obs_pos_out, nullptr, 0, stream);
 }
 
 int fe_env_describe(fe_env *env, int64_t *obs_src, double *obs_pos, void *stream) {
     if (!env || !obs_src || !obs_pos) return fail(FE_ERR_ARG, "fe_env_describe: null argument");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_describe: state not bound");
+    if (int rc = require_bound(env, "fe_env_describe")) return rc;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     const Params &p = env->p;
     dim3 g(grid_for(p.N * p.A)), b(kBlock);
-    if (p.A == 1)
-        hipLaunchKernelGGL(fe_describe_kernel<true>, g, b, 0, (hipStream_t)stream, p, obs_src, obs_pos);
-    else
-        hipLaunchKernelGGL(fe_describe_kernel<false>, g, b, 0, (hipStream_t)stream, p, obs_src, obs_pos);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_describe launch");
-    return FE_OK;
+    with_bool(p.A == 1, [&](auto S) {
+        hipLaunchKernelGGL(fe_describe_kernel<decltype(S)::value>, g, b, 0, (hipStream_t)stream, p, obs_src, obs_pos);
+    });
+    return launched("fe_env_describe");
 }
 
 int fe_env_render(fe_env *env, const int64_t *obs_src, const double *obs_pos, void *obs, void *stream) {
@@ -624,32 +677,19 @@ int fe_env_render_n(fe_env *env, const int64_t *obs_src, const double *obs_pos, 
     if (!env || !obs_src || !obs_pos || !obs || count < 0) return fail(FE_ERR_ARG, "fe_env_render_n: bad argument");
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     p.obs = obs;
     p.N = count;  // any number of descriptors, e.g. a minibatch drawn from a trajectory of them
     p.num_tiles = (count + p.EB - 1) / p.EB;
-    const bool f32 = env->cfg.obs_is_f32 != 0, single = p.A == 1;
     dim3 g((unsigned)(p.num_tiles < (int64_t)env->grid ? p.num_tiles : (int64_t)env->grid)), b(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = env->lds;
-#define FE_RENDER(OT, VEC)                                                                                 \
-    do {                                                                                                   \
-        if (single) hipLaunchKernelGGL((fe_render_kernel<OT, VEC, true>), g, b, lds, st, p, obs_src, obs_pos);  \
-        else hipLaunchKernelGGL((fe_render_kernel<OT, VEC, false>), g, b, lds, st, p, obs_src, obs_pos);        \
-    } while (0)
-    if (f32) {
-        if (env->vec == 4) FE_RENDER(float, 4);
-        else if (env->vec == 2) FE_RENDER(float, 2);
-        else FE_RENDER(float, 1);
-    } else {
-        if (env->vec == 2) FE_RENDER(double, 2);
-        else FE_RENDER(double, 1);
-    }
-#undef FE_RENDER
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_render_n launch");
-    return FE_OK;
+    with_layout(env->cfg.obs_is_f32 != 0, env->vec, [&](auto ot, auto V) {
+        with_bool(p.A == 1, [&](auto S) {
+            hipLaunchKernelGGL((fe_render_kernel<decltype(ot), decltype(V)::value, decltype(S)::value>), g, b, env->lds,
+                               (hipStream_t)stream, p, obs_src, obs_pos);
+        });
+    });
+    return launched("fe_env_render_n");
 }
 
 int fe_env_check_descriptors(fe_env *env, const int64_t *obs_src, int64_t count, int64_t *first_bad, void *stream) {
@@ -657,7 +697,7 @@ int fe_env_check_descriptors(fe_env *env, const int64_t *obs_src, int64_t count,
     *first_bad = -1;
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned long long *d = nullptr, h[2] = {0ull, (unsigned long long)count};
     hipError_t he = hipMalloc(&d, sizeof(h));
@@ -692,40 +732,29 @@ int fe_env_rollout_linear(fe_env *env, const double *weights, double bias, int32
                           void *stream) {
     if (!env || !weights || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_linear: bad argument");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_rollout_linear: state not bound");
+    if (int rc = require_bound(env, "fe_env_rollout_linear")) return rc;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     // the rollout is latency-bound (policy -> accounting -> policy ...): 64 sleeves per workgroup measured
-    // best at 64k envs (tools/fused_bench.py), independent of the tile the streaming step kernel uses
-    int64_t cap = kBlock / p.A > 0 ? kBlock / p.A : 1;
-    int64_t eb = 64 / p.A;
-    if (eb < 8) eb = 8;  // but never fewer than 8 envs per workgroup when they fit
-    if (eb > cap) eb = cap;
-    if (env->rollout_tile_override > 0) eb = env->rollout_tile_override < cap ? env->rollout_tile_override : cap;
-    p.EB = (int)eb;
-    p.num_tiles = (p.N + eb - 1) / eb;
+    // best at 64k envs (tools/fused_bench.py), independent of the tile the streaming step kernel uses --
+    // but never fewer than 8 envs per workgroup when they fit
+    const int64_t grid = rollout_geometry(env, p, 64 / p.A > 8 ? 64 / p.A : 8, /*replace=*/true);
     const size_t lds = rollout_lds_bytes(p.EB, p.A, p.W);
     RolloutArgs r;
     r.weights = weights; r.bias = bias; r.K = K; r.obs_src = obs_src; r.obs_pos = obs_pos;
     r.actions_out = actions_out; r.rew_out = rewards_out; r.done_out = dones_out;
-    // state lives in HBM between steps but every tile is revisited by the same workgroup, so a
-    // grid of one workgroup per tile (capped) keeps the K-step loop entirely inside the launch
-    int64_t grid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
-    dim3 g((unsigned)grid), b(kBlock);
-    if (p.A == 1)
-        hipLaunchKernelGGL(fe_rollout_linear_kernel<true>, g, b, lds, (hipStream_t)stream, p, r);
-    else
-        hipLaunchKernelGGL(fe_rollout_linear_kernel<false>, g, b, lds, (hipStream_t)stream, p, r);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_rollout_linear launch");
-    return FE_OK;
+    with_bool(p.A == 1, [&](auto S) {
+        hipLaunchKernelGGL(fe_rollout_linear_kernel<decltype(S)::value>, dim3((unsigned)grid), dim3(kBlock), lds,
+                           (hipStream_t)stream, p, r);
+    });
+    return launched("fe_env_rollout_linear");
 }
 
 int fe_policy_table(fe_env *env, const double *weights, double *table, double *wsum, void *stream) {
     if (!env || !weights || !table || !wsum) return fail(FE_ERR_ARG, "fe_policy_table: null argument");
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     const Params &p = env->p;
     const int64_t entries = p.D * p.L * p.A;
     int64_t blocks = (entries * 64 + kBlock - 1) / kBlock;
@@ -733,9 +762,7 @@ int fe_policy_table(fe_env *env, const double *weights, double *table, double *w
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(fe_policy_table_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, p, weights,
                        table, wsum);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_policy_table launch");
-    return FE_OK;
+    return launched("fe_policy_table");
 }
 
 int fe_env_rollout_table(fe_env *env, const double *table, const double *wsum, double bias, int32_t K,
@@ -743,28 +770,21 @@ int fe_env_rollout_table(fe_env *env, const double *table, const double *wsum, d
                          int32_t *dones_out, void *stream) {
     if (!env || !table || !wsum || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_table: bad argument");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_rollout_table: state not bound");
+    if (int rc = require_bound(env, "fe_env_rollout_table")) return rc;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     // lane-private loop (no LDS traffic at one asset): full workgroups of sleeves
-    int64_t eb = kBlock / p.A > 0 ? kBlock / p.A : 1;
-    if (env->rollout_tile_override > 0 && env->rollout_tile_override < eb) eb = env->rollout_tile_override;
-    p.EB = (int)eb;
-    p.num_tiles = (p.N + eb - 1) / eb;
+    const int64_t grid = rollout_geometry(env, p, kBlock, /*replace=*/false);
     TableRolloutArgs r;
     r.table = table; r.wsum = wsum; r.bias = bias; r.K = K; r.obs_src = obs_src; r.obs_pos = obs_pos;
     r.actions_out = actions_out; r.rew_out = rewards_out; r.done_out = dones_out;
-    int64_t grid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
     const size_t lds = table_rollout_lds_bytes(p.EB, p.A);
-    dim3 g((unsigned)grid), b(kBlock);
-    if (p.A == 1)
-        hipLaunchKernelGGL(fe_rollout_table_kernel<true>, g, b, lds, (hipStream_t)stream, p, r);
-    else
-        hipLaunchKernelGGL(fe_rollout_table_kernel<false>, g, b, lds, (hipStream_t)stream, p, r);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_rollout_table launch");
-    return FE_OK;
+    with_bool(p.A == 1, [&](auto S) {
+        hipLaunchKernelGGL(fe_rollout_table_kernel<decltype(S)::value>, dim3((unsigned)grid), dim3(kBlock), lds,
+                           (hipStream_t)stream, p, r);
+    });
+    return launched("fe_env_rollout_table");
 }
 
 int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, const float *wpos, const float *b1,
@@ -774,9 +794,9 @@ int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, c
         return fail(FE_ERR_ARG, "fe_env_rollout_mlp: bad argument");
     if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "fe_env_rollout_mlp: H must be 32, 64 or 128 (got %d)", (int)H);
     if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "fe_env_rollout_mlp: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_rollout_mlp: state not bound");
+    if (int rc = require_bound(env, "fe_env_rollout_mlp")) return rc;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     MlpArgs r;
     r.lr32 = logret_f32; r.w1t = w1t; r.wpos = wpos; r.b1 = b1; r.w2 = w2; r.b2 = b2; r.H = H; r.act = activation; r.K = K;
@@ -785,28 +805,16 @@ int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, c
     // (A 512-thread form running policy and accounting of two sub-tiles in antiphase was tried and dropped: on
     // gfx950 the f32-input MFMA executes on the vector ALUs -- SQ_VALU_MFMA_COEXEC_CYCLES = 0 -- so there is
     // nothing for the accounting to hide behind; profiles/r02_microbench/mlp_prof.txt.)
-    int64_t cap = kBlock / p.A > 0 ? kBlock / p.A : 1;
-    int64_t eb = 128 / p.A;
-    if (eb < 1) eb = 1;
-    if (eb > cap) eb = cap;
-    if (env->rollout_tile_override > 0) eb = env->rollout_tile_override < cap ? env->rollout_tile_override : cap;
-    p.EB = (int)eb;
-    p.num_tiles = (p.N + eb - 1) / eb;
+    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
     const size_t lds = mlp_lds_bytes(p.EB, p.A, p.W, H);
-    const bool single = p.A == 1;
-#define FE_MLP(NT) (single ? (const void *)fe_rollout_mlp_kernel<true, NT> : (const void *)fe_rollout_mlp_kernel<false, NT>)
-    const void *kern = H == 32 ? FE_MLP(1) : (H == 64 ? FE_MLP(2) : FE_MLP(4));
-#undef FE_MLP
-    const int64_t grid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
-    const int block = kBlock;
-    if (lds > 160 * 1024)
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_rollout_mlp_kernel<single, 1>
+                       : (H == 64 ? (const void *)fe_rollout_mlp_kernel<single, 2> : (const void *)fe_rollout_mlp_kernel<single, 4>);
+    });
+    if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "fe_env_rollout_mlp: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", (int)H, 4 * p.W, lds);
-    hipError_t he = prepare_kernel(env->device, kern, block, lds, nullptr);
-    if (he != hipSuccess) return hip_fail(he, "fe_env_rollout_mlp: hipFuncSetAttribute");
-    void *args[] = {&p, &r};
-    he = hipLaunchKernel(kern, dim3((unsigned)grid), dim3(block), args, lds, (hipStream_t)stream);
-    if (he != hipSuccess) return hip_fail(he, "fe_env_rollout_mlp launch");
-    return FE_OK;
+    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, "fe_env_rollout_mlp");
 }
 
 // Shared by fe_env_rollout_lstm and fe_lstm_forward: geometry, kernel choice, launch.  `count` = envs (rollout) or
@@ -817,7 +825,7 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
     if (H != 32 && H != 64 && H != 128 && !big)
         return fail(FE_ERR_ARG, "%s: H must be 32, 64, 128, 256, 512 or 1024 (got %d)", who, (int)H);
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     p.N = count;
     // SP (env, asset) pairs per workgroup: 1 (H >= 256), 2 (H = 128) or 4 column tiles of 32; an env's sleeves stay together
@@ -833,22 +841,24 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
     p.EB = (int)eb;
     p.num_tiles = (p.N + eb - 1) / eb;
     const size_t lds = big ? lstm_big_lds_bytes(p.EB, p.A, H) : lstm_lds_bytes(p.EB, p.A, H, SP);
-    const bool single = p.A == 1;
-#define FE_LSTM(NT) (single ? (const void *)fe_rollout_lstm_kernel<true, NT> : (const void *)fe_rollout_lstm_kernel<false, NT>)
-#define FE_LSTM_BIG(RTW) (single ? (const void *)fe_rollout_lstm_big_kernel<true, RTW> : (const void *)fe_rollout_lstm_big_kernel<false, RTW>)
-    const void *kern = H == 32 ? FE_LSTM(1) : (H == 64 ? FE_LSTM(2) : (H == 128 ? FE_LSTM(4) :
-                       (H == 256 ? FE_LSTM_BIG(4) : (H == 512 ? FE_LSTM_BIG(8) : FE_LSTM_BIG(16)))));
-#undef FE_LSTM
-#undef FE_LSTM_BIG
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        switch (H) {
+        case 32: return (const void *)fe_rollout_lstm_kernel<single, 1>;
+        case 64: return (const void *)fe_rollout_lstm_kernel<single, 2>;
+        case 128: return (const void *)fe_rollout_lstm_kernel<single, 4>;
+        case 256: return (const void *)fe_rollout_lstm_big_kernel<single, 4>;
+        case 512: return (const void *)fe_rollout_lstm_big_kernel<single, 8>;
+        default: return (const void *)fe_rollout_lstm_big_kernel<single, 16>;
+        }
+    });
     int per_cu = 0;
     hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
     if (he != hipSuccess) return hip_fail(he, "LSTM kernel: hipFuncSetAttribute / occupancy query");
     const int64_t resident = (int64_t)env->cus * per_cu;  // one pass of resident workgroups, each looping over its tiles
     const int64_t grid = p.num_tiles < resident ? p.num_tiles : resident;
     void *args[] = {&p, &r};
-    he = hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kLstmBlock), args, lds, (hipStream_t)stream);
-    if (he != hipSuccess) return hip_fail(he, "LSTM kernel launch");
-    return FE_OK;
+    return launched("LSTM kernel", hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kLstmBlock), args, lds, (hipStream_t)stream));
 }
 
 int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
@@ -861,7 +871,7 @@ int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, 
     if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm: bad argument");
     if (out_activation < 0 || out_activation > 1) return fail(FE_ERR_ARG, "fe_env_rollout_lstm: out_activation must be 0 (tanh) or 1 (clamp)");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_rollout_lstm: state not bound");
+    if (int rc = require_bound(env, "fe_env_rollout_lstm")) return rc;
     LstmArgs r;
     r.lr32 = logret_f32; r.whh = whh; r.wx = wx; r.wout = wout; r.bout = bout; r.H = H; r.out_act = out_activation; r.K = K;
     r.obs_src = obs_src; r.obs_pos = obs_pos; r.actions_out = actions_out; r.rew_out = rewards_out; r.done_out = dones_out;
@@ -889,26 +899,20 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: H must be 256, 512 or 1024 (got %d)", (int)H);
     if (out_activation < 0 || out_activation > 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: out_activation must be 0 (tanh) or 1 (clamp)");
-    if (!env->bound) return fail(FE_ERR_STATE, "fe_env_rollout_lstm_split: state not bound");
+    if (int rc = require_bound(env, "fe_env_rollout_lstm_split")) return rc;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     const int64_t NA = p.N * p.A, CT = (NA + 31) / 32;
     // the accounting launch: few sleeves per workgroup, so that a handful of envs still spreads over the CUs
-    int64_t eb = 16 / p.A > 1 ? 16 / p.A : 1;  // (and their h_W rows, 4 H bytes per pair, are staged in LDS)
-    if (env->rollout_tile_override > 0 && env->rollout_tile_override < eb) eb = env->rollout_tile_override;
-    p.EB = (int)eb;
-    p.num_tiles = (p.N + eb - 1) / eb;
+    // (and their h_W rows, 4 H bytes per pair, are staged in LDS)
+    const int64_t fgrid = rollout_geometry(env, p, 16 / p.A > 1 ? 16 / p.A : 1, /*replace=*/false);
     const size_t lds = ((table_rollout_lds_bytes(p.EB, p.A) + 15) & ~(size_t)15) + (size_t)p.EB * p.A * H * 4;
-    if (lds > 160 * 1024)
+    if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: %d sleeves per env x H = %d do not fit the LDS of the accounting launch", (int)p.A, (int)H);
-    {
-        const void *fk = p.A == 1 ? (const void *)fe_lstm_split_finish_kernel<true> : (const void *)fe_lstm_split_finish_kernel<false>;
-        hipError_t ha = prepare_kernel(env->device, fk, kBlock, lds, nullptr);
-        if (ha != hipSuccess) return hip_fail(ha, "fe_env_rollout_lstm_split: hipFuncSetAttribute");
-    }
-    const int64_t fgrid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
     const bool single = p.A == 1;
+    const void *fk = with_bool(single, [](auto S) { return (const void *)fe_lstm_split_finish_kernel<decltype(S)::value>; });
+    if (int rc = prepare_big_lds(env->device, fk, lds, "fe_env_rollout_lstm_split")) return rc;
     LstmSplitArgs s;
     s.a.lr32 = logret_f32; s.a.whh = whh; s.a.wx = wx; s.a.wout = wout; s.a.bout = bout; s.a.H = H; s.a.out_act = out_activation;
     s.a.K = 1; s.a.obs_src = obs_src; s.a.obs_pos = obs_pos; s.a.std = std; s.a.traj_src = states_src_out; s.a.traj_pos = states_pos_out;
@@ -916,11 +920,9 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
     s.hbuf = workspace; s.cbuf = workspace + 2 * CT * (int64_t)H * 32; s.pairs = NA;
     const dim3 ggrid((unsigned)(H / 8), (unsigned)((CT + kBlock / 64 - 1) / (kBlock / 64)));
     const size_t glds = (size_t)(H / 8) * 64 * 16;  // one gate-row tile of weights: H / 8 KiB (128 KiB at H = 1024)
-    {
-        const void *gk = single ? (const void *)fe_lstm_split_gates_kernel<true> : (const void *)fe_lstm_split_gates_kernel<false>;
-        hipError_t ha = prepare_kernel(env->device, gk, kBlock, glds, nullptr);
-        if (ha != hipSuccess) return hip_fail(ha, "fe_env_rollout_lstm_split: hipFuncSetAttribute");
-    }
+    const void *gk = with_bool(single, [](auto S) { return (const void *)fe_lstm_split_gates_kernel<decltype(S)::value>; });
+    if (int rc = prepare_big_lds(env->device, gk, glds, "fe_env_rollout_lstm_split")) return rc;
+    hipStream_t st = (hipStream_t)stream;
     for (int k = 0; k < K; ++k) {
         s.k = k;
         s.a.noise = noise ? noise + (int64_t)k * NA : nullptr;
@@ -930,25 +932,23 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
         s.a.done_out = dones_out + (int64_t)k * p.N;
         for (int t = 0; t < p.W; ++t) {
             s.t = t;
-            if (single) hipLaunchKernelGGL(fe_lstm_split_gates_kernel<true>, ggrid, dim3(kBlock), glds, (hipStream_t)stream, p, s);
-            else hipLaunchKernelGGL(fe_lstm_split_gates_kernel<false>, ggrid, dim3(kBlock), glds, (hipStream_t)stream, p, s);
+            with_bool(single, [&](auto S) {
+                hipLaunchKernelGGL(fe_lstm_split_gates_kernel<decltype(S)::value>, ggrid, dim3(kBlock), glds, st, p, s);
+            });
             // a launch that fails (bad geometry, LDS) fails the first time: stop before queueing W * K launches on
             // half-written h / c state
             if (k == 0 && t == 0) {
-                hipError_t hl = hipGetLastError();
-                if (hl != hipSuccess) return hip_fail(hl, "fe_env_rollout_lstm_split: gates launch");
+                if (int rc = launched("fe_env_rollout_lstm_split: gates")) return rc;
             }
         }
-        if (single) hipLaunchKernelGGL(fe_lstm_split_finish_kernel<true>, dim3((unsigned)fgrid), dim3(kBlock), lds, (hipStream_t)stream, p, s);
-        else hipLaunchKernelGGL(fe_lstm_split_finish_kernel<false>, dim3((unsigned)fgrid), dim3(kBlock), lds, (hipStream_t)stream, p, s);
+        with_bool(single, [&](auto S) {
+            hipLaunchKernelGGL(fe_lstm_split_finish_kernel<decltype(S)::value>, dim3((unsigned)fgrid), dim3(kBlock), lds, st, p, s);
+        });
         if (k == 0) {
-            hipError_t hl = hipGetLastError();
-            if (hl != hipSuccess) return hip_fail(hl, "fe_env_rollout_lstm_split: accounting launch");
+            if (int rc = launched("fe_env_rollout_lstm_split: accounting")) return rc;
         }
     }
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_rollout_lstm_split launch");
-    return FE_OK;
+    return launched("fe_env_rollout_lstm_split");
 }
 
 int fe_lstm_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout, float bout,
@@ -972,14 +972,11 @@ int fe_lstm_activations(const float *x, float *sigmoid_out, float *tanh_out, int
     if (!x || !sigmoid_out || !tanh_out || n < 0) return fail(FE_ERR_ARG, "fe_lstm_activations: bad argument");
     if (n == 0) return FE_OK;
     DeviceGuard guard(device_of(x));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
-    hipError_t he;
+    if (int rc = guard.status()) return rc;
     int64_t grid = (n + kBlock - 1) / kBlock;
     if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(fe_lstm_activations_kernel, dim3((unsigned)grid), dim3(kBlock), 0, (hipStream_t)stream, x, sigmoid_out, tanh_out, n);
-    he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_lstm_activations launch");
-    return FE_OK;
+    return launched("fe_lstm_activations");
 }
 
 int fe_env_set_day(fe_env *env, int64_t env_index, int64_t day, void *stream) {
@@ -987,13 +984,11 @@ int fe_env_set_day(fe_env *env, int64_t env_index, int64_t day, void *stream) {
     if (env_index < 0 || env_index >= env->cfg.N || day < 0 || day >= env->cfg.D)
         return fail(FE_ERR_ARG, "fe_env_set_day: env %lld / day %lld out of range", (long long)env_index, (long long)day);
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     // a one-lane launch with the day as a kernel argument: stream-ordered behind the step that finished the episode and
     // ahead of the next one, WITHOUT a host synchronisation (round 3 copied a stack variable and had to wait for it)
     hipLaunchKernelGGL(fe_set_day_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, env->p.env_idx, env_index, day);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_env_set_day launch");
-    return FE_OK;
+    return launched("fe_env_set_day");
 }
 
 int fe_env_launch_info(const fe_env *env, int32_t *grid, int32_t *block, int32_t *tile_envs, int32_t *lds) {
@@ -1010,7 +1005,7 @@ int fe_env_set_launch(fe_env *env, int32_t tile_envs, int32_t grid, int32_t roll
     if (!env) return fail(FE_ERR_ARG, "fe_env_set_launch: null env");
     if (tile_envs < 0 || grid < 0 || rollout_tile_envs < 0) return fail(FE_ERR_ARG, "fe_env_set_launch: negative value");
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     env->tile_override = tile_envs;
     env->grid_override = grid;
     env->rollout_tile_override = rollout_tile_envs;
@@ -1022,10 +1017,10 @@ const char *fe_build_tag(void) { return FE_BUILD_TAG; }
 int fe_env_destroy(fe_env *env) {
     if (env && (env->owned_logret || env->ticket)) {
         DeviceGuard guard(env->device);
-        if (env->owned_logret) (void)hipFree(env->owned_logret);
-        if (env->ticket) (void)hipFree(env->ticket);
+        release_env(env);
+    } else {
+        delete env;
     }
-    delete env;
     return FE_OK;
 }
 
@@ -1039,22 +1034,18 @@ const double *fe_env_logret(const fe_env *env) { return env ? env->p.LR : nullpt
 int fe_build_logret(const double *prices, double *out, int64_t T, int32_t A, void *stream) {
     if (!prices || !out || T < 1 || A < 1) return fail(FE_ERR_ARG, "fe_build_logret: bad argument");
     DeviceGuard guard(device_of(prices));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     hipLaunchKernelGGL(fe_logret_kernel, dim3(grid_for(T * A)), dim3(kBlock), 0, (hipStream_t)stream, prices, out, T, A);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_build_logret launch");
-    return FE_OK;
+    return launched("fe_build_logret");
 }
 
 int fe_build_logret_tables(const double *prices, double *out, int64_t D, int64_t L, int32_t A, void *stream) {
     if (!prices || !out || D < 1 || L < 1 || A < 1) return fail(FE_ERR_ARG, "fe_build_logret_tables: bad argument");
     DeviceGuard guard(device_of(prices));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     hipLaunchKernelGGL(fe_logret_tables_kernel, dim3(grid_for(D * L * A)), dim3(kBlock), 0, (hipStream_t)stream, prices,
                        out, D, L, A);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_build_logret_tables launch");
-    return FE_OK;
+    return launched("fe_build_logret_tables");
 }
 
 int fe_build_tables(const double *series, const int64_t *starts, const int64_t *stops, int64_t D, int64_t L,
@@ -1062,12 +1053,10 @@ int fe_build_tables(const double *series, const int64_t *starts, const int64_t *
     if (!series || !starts || !stops || !out || D < 1 || L < 1 || A < 1)
         return fail(FE_ERR_ARG, "fe_build_tables: bad argument");
     DeviceGuard guard(device_of(series));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     hipLaunchKernelGGL(fe_tables_kernel, dim3(grid_for(D * L * 4 * A)), dim3(kBlock), 0, (hipStream_t)stream, series,
                        starts, stops, D, L, A, out);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_build_tables launch");
-    return FE_OK;
+    return launched("fe_build_tables");
 }
 
 int fe_traj_store(int64_t t, int64_t N, int32_t A, const float *actions, const double *rewards,
@@ -1076,13 +1065,11 @@ int fe_traj_store(int64_t t, int64_t N, int32_t A, const float *actions, const d
     if (t < 0 || N < 1 || A < 1 || !actions || !rewards || !dones || !traj_actions || !traj_rewards || !traj_dones)
         return fail(FE_ERR_ARG, "fe_traj_store: bad argument");
     DeviceGuard guard(device_of(traj_rewards));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     const int64_t NA = N * A;
     hipLaunchKernelGGL(fe_traj_store_kernel, dim3(grid_for(NA)), dim3(kBlock), 0, (hipStream_t)stream, N, NA, actions,
                        rewards, dones, traj_actions + t * NA, traj_rewards + t * N, traj_dones + t * N);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_traj_store launch");
-    return FE_OK;
+    return launched("fe_traj_store");
 }
 
 int fe_traj_returns(const double *rewards, const int32_t *dones, const float *values, const float *last_values,
@@ -1090,16 +1077,13 @@ int fe_traj_returns(const double *rewards, const int32_t *dones, const float *va
     if (!rewards || !dones || !last_values || !returns || T < 1 || N < 1 || (advantages && !values))
         return fail(FE_ERR_ARG, "fe_traj_returns: bad argument");
     DeviceGuard guard(device_of(rewards));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
-    if (N >= (1 << 19))
-        hipLaunchKernelGGL(fe_traj_returns_kernel<1>, dim3(grid_for(N)), dim3(kBlock), 0, (hipStream_t)stream, rewards, dones,
-                           values, last_values, T, N, (float)gamma, returns, advantages);
-    else
-        hipLaunchKernelGGL(fe_traj_returns_kernel<4>, dim3(grid_for(N)), dim3(kBlock), 0, (hipStream_t)stream, rewards, dones,
-                           values, last_values, T, N, (float)gamma, returns, advantages);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_traj_returns launch");
-    return FE_OK;
+    if (int rc = guard.status()) return rc;
+    // loads U steps ahead: U = 1 once the envs fill the chip on their own (fe_aux_kernels.h)
+    with_bool(N >= (1 << 19), [&](auto full) {
+        hipLaunchKernelGGL(fe_traj_returns_kernel<decltype(full)::value ? 1 : 4>, dim3(grid_for(N)), dim3(kBlock), 0,
+                           (hipStream_t)stream, rewards, dones, values, last_values, T, N, (float)gamma, returns, advantages);
+    });
+    return launched("fe_traj_returns");
 }
 
 // ---- include/finenvs_amd_evo.h: the evolution-strategies population ----
@@ -1123,7 +1107,7 @@ int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *
     if (p.redraw_mode != 1) return fail(FE_ERR_ARG, "fe_evo_rollout: the population needs redraw mode 1 (device redraws)");
     if (p.A > 128) return fail(FE_ERR_ARG, "fe_evo_rollout: at most 128 assets per env (got %d)", (int)p.A);
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     // a tile = PB mirrored pairs (2 PB envs): each wavefront evaluates whole pairs, every z element serves both signs
     int PB = 128 / p.A;
     if (PB > 8) PB = 8;
@@ -1136,7 +1120,7 @@ int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *
     p.num_tiles = pair_tiles + eval_tiles;
     const int64_t P = evo_num_params(p.W, H);
     const size_t lds = evo_lds_bytes(EB, p.A, P);
-    if (lds > 160 * 1024)
+    if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "fe_evo_rollout: theta (%lld floats) does not fit the 160 KiB LDS (%zu bytes needed)",
                     (long long)P, lds);
     EvoArgs r;
@@ -1147,17 +1131,12 @@ int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *
     r.rew_scratch = pop->scratch_rewards; r.done_scratch = pop->scratch_dones;
     r.n_train = nt; r.half = half; r.K = K; r.max_ep = pop->max_episodes; r.PB = PB; r.pair_tiles = (int32_t)pair_tiles;
     r.sigma = pop->noise_std; r.nu = pop->action_noise_std; r.seed = pop->seed; r.g = pop->generation; r.step0 = pop->step;
-    const bool single = p.A == 1;
-#define FE_EVO(HH) (single ? (const void *)fe_evo_rollout_kernel<true, HH> : (const void *)fe_evo_rollout_kernel<false, HH>)
-    const void *kern = H == 32 ? FE_EVO(32) : FE_EVO(64);
-#undef FE_EVO
-    hipError_t he = prepare_kernel(env->device, kern, kBlock, lds, nullptr);
-    if (he != hipSuccess) return hip_fail(he, "fe_evo_rollout: hipFuncSetAttribute");
-    const int64_t grid = p.num_tiles < 8 * 256 ? p.num_tiles : 8 * 256;
-    void *args[] = {&p, &r};
-    he = hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), args, lds, (hipStream_t)stream);
-    if (he != hipSuccess) return hip_fail(he, "fe_evo_rollout launch");
-    return FE_OK;
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_evo_rollout_kernel<single, 32> : (const void *)fe_evo_rollout_kernel<single, 64>;
+    });
+    // one workgroup per tile (capped); the tile is fixed by the pair layout above, without fe_env_set_launch's override
+    return launch_big_lds(env->device, kern, capped_grid(p.num_tiles), lds, p, r, stream, "fe_evo_rollout");
 }
 
 int64_t fe_evo_gradient_workspace_doubles(int64_t num_pairs, int64_t num_params) {
@@ -1171,16 +1150,14 @@ int fe_evo_gradient(uint64_t seed, uint32_t generation, int64_t num_pairs, int64
         num_params > 4 * 0xffffffffll)
         return fail(FE_ERR_ARG, "fe_evo_gradient: bad argument");
     DeviceGuard guard(device_of(out));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_evo_gradient: out is not device memory");
+    if (int rc = guard.status("fe_evo_gradient: out is not device memory")) return rc;
     const int64_t blocks = (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs;
     const int64_t threads = blocks * ((num_params + 3) / 4);
     hipLaunchKernelGGL(fe_evo_gradient_partial_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, seed, generation, num_pairs, num_params, diffed, workspace);
     hipLaunchKernelGGL(fe_evo_gradient_reduce_kernel, dim3((unsigned)((num_params + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, blocks, num_params, (const double *)workspace, out);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_evo_gradient launch");
-    return FE_OK;
+    return launched("fe_evo_gradient");
 }
 
 int fe_evo_noise(uint64_t seed, uint32_t generation, const int64_t *pairs, int64_t count, int64_t num_params, float *out,
@@ -1188,13 +1165,11 @@ int fe_evo_noise(uint64_t seed, uint32_t generation, const int64_t *pairs, int64
     if (!pairs || !out || count < 1 || num_params < 1 || num_params > 4 * 0xffffffffll)
         return fail(FE_ERR_ARG, "fe_evo_noise: bad argument");
     DeviceGuard guard(device_of(out));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_evo_noise: out is not device memory");
+    if (int rc = guard.status("fe_evo_noise: out is not device memory")) return rc;
     const int64_t threads = count * ((num_params + 3) / 4);
     hipLaunchKernelGGL(fe_evo_noise_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        (hipStream_t)stream, seed, generation, pairs, count, num_params, out);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_evo_noise launch");
-    return FE_OK;
+    return launched("fe_evo_noise");
 }
 
 // ---- include/finenvs_amd_replay.h: the off-policy replay ring ----
@@ -1225,25 +1200,16 @@ int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, in
                     "count %lld, head %lld, capacity %lld)", (long long)steps, (long long)num_envs, (long long)row_stride,
                     (long long)first, (long long)count, (long long)head, (long long)C);
     DeviceGuard guard(device_of(ring->rewards));
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "fe_replay_append: the ring is not device memory");
+    if (int rc = guard.status("fe_replay_append: the ring is not device memory")) return rc;
     const ReplayRing r = replay_view(ring);
-    const bool single = r.A == 1;
-    dim3 g(grid_for(count * r.A)), b(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-#define FE_APPEND(S, F) \
-    hipLaunchKernelGGL((fe_replay_append_kernel<S, F>), g, b, 0, st, r, head, first, count, num_envs, row_stride, \
-                       state_src, state_pos, next_src, next_pos, actions, rewards, dones)
-    if (single) {
-        if (actions_are_f64) FE_APPEND(true, true);
-        else FE_APPEND(true, false);
-    } else {
-        if (actions_are_f64) FE_APPEND(false, true);
-        else FE_APPEND(false, false);
-    }
-#undef FE_APPEND
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_replay_append launch");
-    return FE_OK;
+    with_bool(r.A == 1, [&](auto S) {
+        with_bool(actions_are_f64 != 0, [&](auto F) {
+            hipLaunchKernelGGL((fe_replay_append_kernel<decltype(S)::value, decltype(F)::value>), dim3(grid_for(count * r.A)),
+                               dim3(kBlock), 0, (hipStream_t)stream, r, head, first, count, num_envs, row_stride, state_src,
+                               state_pos, next_src, next_pos, actions, rewards, dones);
+        });
+    });
+    return launched("fe_replay_append");
 }
 
 int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
@@ -1260,18 +1226,16 @@ int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int6
                     (int)env->p.A);
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
-    if (guard.err != hipSuccess) return hip_fail(guard.err, "hipSetDevice");
+    if (int rc = guard.status()) return rc;
     Params p = env->p;
     const int A = p.A;
-    const int64_t WA = (int64_t)p.W * A;
     // Tile = EB samples.  A workgroup iteration of stream_tile<float> turns 4 x 256 tuples: a tile is a whole number of
     // them where the LDS allows (two descriptor tiles of EB (8 + 8A) bytes each, kept within 32 KiB), and there are
     // about four tiles per CU.
     int64_t cap = 2048 / (1 + A);
     if (cap < 1) cap = 1;
-    int64_t gcd = 4 * (kStageBytes / 20), w = WA;
-    while (w) { const int64_t t = gcd % w; gcd = w; w = t; }
-    const int64_t unit = 4 * (kStageBytes / 20) / gcd;  // samples per whole workgroup iteration
+    const int64_t wg_tuples = 4 * (kStageBytes / 20);
+    const int64_t unit = wg_tuples / std::gcd(wg_tuples, (int64_t)p.W * A);  // samples per whole workgroup iteration
     int64_t EB = (count + 4 * (int64_t)env->cus - 1) / (4 * (int64_t)env->cus);
     if (unit <= cap) EB = EB <= unit ? unit : EB - EB % unit;
     if (EB > cap) EB = cap;
@@ -1284,27 +1248,16 @@ int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int6
     const size_t lds = replay_lds_bytes((int)EB, A);
     const ReplayRing r = replay_view(ring);
     const int64_t start = ((head - size) % C + C) % C;
-    const int env_elems = (int)p.env_elems;
-    const int vec = env_elems % 4 == 0 ? 4 : (env_elems % 2 == 0 ? 2 : 1);
-    const bool single = A == 1;
-    hipStream_t st = (hipStream_t)stream;
     unsigned long long *err = reinterpret_cast<unsigned long long *>(ring->errors);
-#define FE_SAMPLE(V, S)                                                                                               \
-    hipLaunchKernelGGL((fe_replay_sample_kernel<V, S>), dim3((unsigned)grid), dim3(kBlock), lds, st, p, r, indices,    \
-                       start, size, states, next_states, actions, rewards, dones, err)
-    if (single) {
-        if (vec == 4) FE_SAMPLE(4, true);
-        else if (vec == 2) FE_SAMPLE(2, true);
-        else FE_SAMPLE(1, true);
-    } else {
-        if (vec == 4) FE_SAMPLE(4, false);
-        else if (vec == 2) FE_SAMPLE(2, false);
-        else FE_SAMPLE(1, false);
-    }
-#undef FE_SAMPLE
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return hip_fail(he, "fe_replay_sample launch");
-    return FE_OK;
+    // the sampled states are f32 observations
+    with_layout(/*f32=*/true, vec_width(p.env_elems, 4), [&](auto, auto V) {
+        with_bool(A == 1, [&](auto S) {
+            hipLaunchKernelGGL((fe_replay_sample_kernel<decltype(V)::value, decltype(S)::value>), dim3((unsigned)grid),
+                               dim3(kBlock), lds, (hipStream_t)stream, p, r, indices, start, size, states, next_states,
+                               actions, rewards, dones, err);
+        });
+    });
+    return launched("fe_replay_sample");
 }
 
 }  // extern "C"
