@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""SAC (Haarnoja et al., "Soft Actor-Critic", 2018: twin critics, entropy-regularised targets, learned temperature) on
+the time-series env with synthetic bars, in the structure of the reference's SACAgentLSTM: actor
+``SACActorLSTM(H=128, W=4)``, twin LSTM critics on ``[states | actions repeated over the window]``
+(finenvs/agents/agent_utils.py:5-14), target critics with soft updates.
+
+Rollout chunks come from ``FusedSACRollout.run(K, noise, trajectory=)`` -- K env steps with the actor in the kernel --
+and go into the device replay ring with one ``ReplayBuffer.extend``; every training step samples a mini-batch whose
+states and next states are rendered in one launch.  The last env is the evaluation env: it acts on the mean.
+
+    python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256]
+"""
+import argparse
+import copy
+import os
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from finenvs_amd import TimeSeriesEnv  # noqa: E402
+from finenvs_amd.data import synthetic  # noqa: E402
+from finenvs_amd.replay import ReplayBuffer  # noqa: E402
+from finenvs_amd.sac import FusedSACRollout, SACActorLSTM  # noqa: E402
+from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
+
+
+class CriticLSTM(nn.Module):
+    """The reference's CriticLSTM: LSTM over [state row | action] per window row, Linear(H, 1) on the last step."""
+
+    def __init__(self, H, W):
+        super().__init__()
+        self.lstm = nn.LSTM(5 + 1, H, num_layers=1, batch_first=True)
+        self.out = nn.Linear(H, 1)
+
+    def forward(self, states, actions):
+        x = torch.cat([states, actions.unsqueeze(1).repeat(1, states.shape[1], 1)], dim=2)  # match_actions_dim_with_states
+        return self.out(self.lstm(x)[0][:, -1, :])
+
+
+def soft_update(target, source, rho):
+    with torch.no_grad():
+        for t, s in zip(target.parameters(), source.parameters()):
+            t.mul_(1.0 - rho).add_(s, alpha=rho)
+
+
+def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
+         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False):
+    torch.manual_seed(seed)
+    prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
+    env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
+    dev, N, A = env.device, num_envs, 1
+    buffer = ReplayBuffer(env, max_size=max(max_size, chunk * N))
+    actor = SACActorLSTM(H=hidden, W=window).to(dev)
+    critic_1, critic_2 = CriticLSTM(hidden, window).to(dev), CriticLSTM(hidden, window).to(dev)
+    critic_1t, critic_2t = copy.deepcopy(critic_1), copy.deepcopy(critic_2)
+    actor_opt = torch.optim.Adam(actor.parameters(), lr=lr)
+    alpha_opt = torch.optim.Adam([actor.log_alpha], lr=lr)
+    critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
+    roll = FusedSACRollout(env, actor)  # re-packs the actor's weights at every run: updates are seen right away
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    history = []
+    for it in range(iterations):
+        traj = TrajectoryBuffer(chunk, N, A, device=dev, states=True)
+        noise = torch.randn((chunk, N, A), generator=gen, device=dev)
+        roll.run(chunk, noise=noise, trajectory=traj)
+        buffer.extend(traj)
+        if buffer.size() < batch:
+            continue
+        for _ in range(updates_per_chunk):
+            b = buffer.get_mini_batch(batch)
+            s, a, s2 = b["states"], b["actions"], b["next_states"]
+            r, d = b["rewards"] * reward_scale, b["dones"]
+            with torch.no_grad():  # compute_targets (SAC_agent.py:200-225)
+                a2, lp2 = actor.get_actions_and_log_probs(s2)
+                q2 = torch.min(critic_1t(s2, a2), critic_2t(s2, a2))
+                y = r + gamma * (1.0 - d) * (q2 - actor.log_alpha.exp() * lp2.mean(dim=1, keepdim=True))
+            critic_loss = F.mse_loss(critic_1(s, a), y) + F.mse_loss(critic_2(s, a), y)
+            critic_opt.zero_grad()
+            critic_loss.backward()
+            critic_opt.step()
+            a_new, lp = actor.get_actions_and_log_probs(s)  # SAC/actor.py:63-85
+            mean_lp = lp.mean(dim=1, keepdim=True)
+            q = torch.min(critic_1(s, a_new), critic_2(s, a_new))
+            actor_loss = -(q - actor.log_alpha.exp().detach() * mean_lp).mean()
+            actor_opt.zero_grad()
+            actor_loss.backward()
+            actor_opt.step()
+            alpha_loss = (-actor.log_alpha.exp() * (mean_lp + actor.target_entropy).detach()).mean()
+            alpha_opt.zero_grad()
+            alpha_loss.backward()
+            alpha_opt.step()
+            soft_update(critic_1t, critic_1, rho)
+            soft_update(critic_2t, critic_2, rho)
+        entry = {"iteration": it, "critic_loss": critic_loss.item(), "actor_loss": actor_loss.item(),
+                 "alpha_loss": alpha_loss.item(), "alpha": float(actor.log_alpha.detach().exp()), "buffer_size": buffer.size()}
+        history.append(entry)
+        if not quiet and it % 10 == 0:
+            print(f"iter {it:5d}  buffer {buffer.size():8d}  critic {entry['critic_loss']:.4g}  actor {entry['actor_loss']:.4g}  "
+                  f"alpha {entry['alpha']:.4g}")
+    return history
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--iterations", type=int, default=100)
+    ap.add_argument("--chunk", type=int, default=8)
+    ap.add_argument("--batch", type=int, default=256)
+    a = ap.parse_args()
+    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch)

@@ -124,6 +124,14 @@ REPLAY_SIGNATURES = {
     "fe_replay_sample": (C.c_int, [_vp, C.POINTER(FeReplayRing), _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/finenvs_amd_sac.h: the SAC actor's head on the fused LSTM rollout (finenvs_amd/sac.py; same library)
+SAC_SIGNATURES = {
+    "fe_env_rollout_sac": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_float, _i32, _i32, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_sac_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_float, _i32, _vp, _vp, _i64, _vp,
+                                 _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -148,7 +156,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                 "finenvs_amd has no CPU fallback"
             ) from exc
     lib = C.CDLL(p)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -25,18 +25,19 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, nine files:
+// One translation unit, ten files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
-//   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA)
+//   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA), and with the SAC actor's head
+//   fe_lstm_rollout_body.h  the register-resident rollout's body, included by both of those kernels
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
-//                         four headers in include/
+//                         five headers in include/
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
 // reference's mixed f32/f64 tensor arithmetic; this file
@@ -58,6 +59,7 @@
 #include "finenvs_amd_ext.h"
 #include "finenvs_amd_evo.h"
 #include "finenvs_amd_replay.h"
+#include "finenvs_amd_sac.h"
 
 #include "fe_device_common.h"
 #include "fe_step_kernel.h"
@@ -817,6 +819,44 @@ int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, c
     return launch_big_lds(env->device, kern, grid, lds, p, r, stream, "fe_env_rollout_mlp");
 }
 
+// Tile geometry of the fused LSTM kernels (LSTM and SAC heads) for `count` envs (rollout) or descriptors (forward): sets
+// p.N, p.EB, p.num_tiles; returns the workgroup tile's (env, asset) pairs SP, or 0 after fail() when an env's sleeves do
+// not fit one tile.
+static int lstm_geometry(const fe_env *env, Params &p, int64_t count, int32_t H, bool big, const char *who) {
+    p.N = count;
+    // SP (env, asset) pairs per workgroup: 1 (H >= 256), 2 (H = 128) or 4 column tiles of 32; an env's sleeves stay together
+    const int SP = big ? 32 : (H == 128 ? LstmGeom<4>::SP : LstmGeom<2>::SP);
+    if (p.A > SP) {
+        fail(FE_ERR_ARG, "%s: %d assets per env exceed the %d pairs of a workgroup tile (H = %d)", who, (int)p.A, SP, (int)H);
+        return 0;
+    }
+    int64_t eb = SP / p.A;
+    // few envs: a tile lives on one CU for a whole step, so spread them over the CUs -- halve the tile (down to one
+    // 32-pair column tile) while that fills otherwise idle CUs; a wavefront then runs fewer column tiles per time step
+    const int64_t min_eb = 32 / p.A > 1 ? 32 / p.A : 1;
+    while (!big && eb > min_eb && (p.N + eb - 1) / eb < env->cus) eb = eb / 2 > min_eb ? eb / 2 : min_eb;
+    if (env->rollout_tile_override > 0 && env->rollout_tile_override < eb) eb = env->rollout_tile_override;
+    p.EB = (int)eb;
+    p.num_tiles = (p.N + eb - 1) / eb;
+    return SP;
+}
+
+// One pass of resident kLstmBlock-thread workgroups, each looping over its tiles; `r` is the kernel's argument block after
+// the Params.  `what` names the kernel in errors.
+static int launch_resident(const fe_env *env, const void *kern, size_t lds, Params &p, void *r, const char *what, void *stream) {
+    int per_cu = 0;
+    hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
+    if (he != hipSuccess) {
+        char msg[64];
+        snprintf(msg, sizeof(msg), "%s: hipFuncSetAttribute / occupancy query", what);
+        return hip_fail(he, msg);
+    }
+    const int64_t resident = (int64_t)env->cus * per_cu;
+    const int64_t grid = p.num_tiles < resident ? p.num_tiles : resident;
+    void *args[] = {&p, r};
+    return launched(what, hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kLstmBlock), args, lds, (hipStream_t)stream));
+}
+
 // Shared by fe_env_rollout_lstm and fe_lstm_forward: geometry, kernel choice, launch.  `count` = envs (rollout) or
 // descriptors (forward).
 static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who, void *stream) {
@@ -827,19 +867,8 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     Params p = env->p;
-    p.N = count;
-    // SP (env, asset) pairs per workgroup: 1 (H >= 256), 2 (H = 128) or 4 column tiles of 32; an env's sleeves stay together
-    const int SP = big ? 32 : (H == 128 ? LstmGeom<4>::SP : LstmGeom<2>::SP);
-    if (p.A > SP)
-        return fail(FE_ERR_ARG, "%s: %d assets per env exceed the %d pairs of a workgroup tile (H = %d)", who, (int)p.A, SP, (int)H);
-    int64_t eb = SP / p.A;
-    // few envs: a tile lives on one CU for a whole step, so spread them over the CUs -- halve the tile (down to one
-    // 32-pair column tile) while that fills otherwise idle CUs; a wavefront then runs fewer column tiles per time step
-    const int64_t min_eb = 32 / p.A > 1 ? 32 / p.A : 1;
-    while (!big && eb > min_eb && (p.N + eb - 1) / eb < env->cus) eb = eb / 2 > min_eb ? eb / 2 : min_eb;
-    if (env->rollout_tile_override > 0 && env->rollout_tile_override < eb) eb = env->rollout_tile_override;
-    p.EB = (int)eb;
-    p.num_tiles = (p.N + eb - 1) / eb;
+    const int SP = lstm_geometry(env, p, count, H, big, who);
+    if (SP == 0) return FE_ERR_ARG;
     const size_t lds = big ? lstm_big_lds_bytes(p.EB, p.A, H) : lstm_lds_bytes(p.EB, p.A, H, SP);
     const void *kern = with_bool(p.A == 1, [H](auto S) {
         constexpr bool single = decltype(S)::value;
@@ -852,13 +881,31 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
         default: return (const void *)fe_rollout_lstm_big_kernel<single, 16>;
         }
     });
-    int per_cu = 0;
-    hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "LSTM kernel: hipFuncSetAttribute / occupancy query");
-    const int64_t resident = (int64_t)env->cus * per_cu;  // one pass of resident workgroups, each looping over its tiles
-    const int64_t grid = p.num_tiles < resident ? p.num_tiles : resident;
-    void *args[] = {&p, &r};
-    return launched("LSTM kernel", hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kLstmBlock), args, lds, (hipStream_t)stream));
+    return launch_resident(env, kern, lds, p, &r, "LSTM kernel", stream);
+}
+
+// Shared by fe_env_rollout_sac and fe_sac_forward.  The forward form has no evaluation env: every descriptor with noise
+// samples.
+static int launch_sac(fe_env *env, SacArgs &s, int64_t count, const char *who, void *stream) {
+    const int32_t H = s.l.H;
+    if (H != 32 && H != 64 && H != 128)
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the SAC head has no streamed or split kernel", who, (int)H);
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    if (s.l.forward_only) p.eval_env = -1;
+    const int SP = lstm_geometry(env, p, count, H, false, who);
+    if (SP == 0) return FE_ERR_ARG;
+    const size_t lds = sac_lds_bytes(p.EB, p.A, H, SP);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        switch (H) {
+        case 32: return (const void *)fe_rollout_sac_kernel<single, 1>;
+        case 64: return (const void *)fe_rollout_sac_kernel<single, 2>;
+        default: return (const void *)fe_rollout_sac_kernel<single, 4>;
+        }
+    });
+    return launch_resident(env, kern, lds, p, &s, "SAC kernel", stream);
 }
 
 int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
@@ -1258,6 +1305,53 @@ int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int6
         });
     });
     return launched("fe_replay_sample");
+}
+
+// ---- include/finenvs_amd_sac.h: the SAC actor's head on the LSTM recurrence ----
+static void sac_args(SacArgs &s, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
+                     const float *wmu, float bmu, const float *wstd, float bstd, int32_t H) {
+    s.l.lr32 = logret_f32; s.l.whh = whh; s.l.wx = wx; s.l.wout = nullptr; s.l.bout = 0.0f; s.l.H = H; s.l.out_act = 0;
+    s.l.std = 0.0f;
+    s.wl = wl; s.bl = bl; s.wmu = wmu; s.bmu = bmu; s.wstd = wstd; s.bstd = bstd;
+}
+
+int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                       const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, int32_t K,
+                       int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out, float *means_out,
+                       float *stds_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
+                       double *states_pos_out, void *stream) {
+    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
+        return fail(FE_ERR_ARG, "fe_env_rollout_sac: states_src_out and states_pos_out go together");
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || !rewards_out ||
+        !dones_out || K < 1)
+        return fail(FE_ERR_ARG, "fe_env_rollout_sac: bad argument");
+    if (int rc = require_bound(env, "fe_env_rollout_sac")) return rc;
+    SacArgs s;
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, H);
+    s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
+    s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
+    s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
+    s.stds_out = stds_out; s.logp_out = nullptr;
+    return launch_sac(env, s, env->cfg.N, "fe_env_rollout_sac", stream);
+}
+
+int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
+                   const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, const int64_t *obs_src,
+                   const double *obs_pos, int64_t count, const float *noise, float *actions_out, float *log_probs_out,
+                   float *means_out, float *stds_out, void *stream) {
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0)
+        return fail(FE_ERR_ARG, "fe_sac_forward: bad argument");
+    if (!noise && (actions_out || log_probs_out))
+        return fail(FE_ERR_ARG, "fe_sac_forward: actions_out and log_probs_out need noise");
+    if (count == 0) return FE_OK;
+    SacArgs s;
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, H);
+    s.l.K = 1;
+    s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
+    s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
+    s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
+    s.stds_out = stds_out; s.logp_out = log_probs_out;
+    return launch_sac(env, s, count, "fe_sac_forward", stream);
 }
 
 }  // extern "C"

@@ -450,6 +450,19 @@ def lstm_row_order(H: int) -> torch.Tensor:
     return gate * H + 8 * mt + 4 * half + b
 
 
+def lstm_pack(weight_ih, weight_hh, bias_ih, bias_hh, H: int):
+    """``nn.LSTM``'s parameters as the register-resident kernels read them: (whh (4H, H), wx (4H, 8)) f32 on the
+    parameters' device, rows in ``lstm_row_order``; wx = [w_ih (5) | b_ih + b_hh | 0 | 0]."""
+    dev = weight_hh.device
+    order = lstm_row_order(H).to(dev)
+    w_ih, w_hh = weight_ih.detach().float(), weight_hh.detach().float()
+    bias = bias_ih.detach().float().reshape(4 * H) + bias_hh.detach().float().reshape(4 * H)  # one f32 add
+    wx = torch.zeros((4 * H, 8), dtype=torch.float32, device=dev)
+    wx[:, :5] = w_ih[order]
+    wx[:, 5] = bias[order]
+    return w_hh[order].contiguous(), wx
+
+
 class FusedLSTMRollout(_FusedEvaluation):
     """K env steps per launch with the LSTM actor of the reference's time-series scripts evaluated in the kernel
     (C ABI ``fe_env_rollout_lstm``):
@@ -507,16 +520,11 @@ class FusedLSTMRollout(_FusedEvaluation):
     def set_weights(self, weight_ih, weight_hh, bias_ih, bias_hh, weight_out, bias_out: float) -> None:
         H, dev = self.H, self.env._dev
         f32 = dict(dtype=torch.float32, device="cpu")
-        order = lstm_row_order(H)
         w_ih, w_hh = weight_ih.detach().to(**f32), weight_hh.detach().to(**f32)
         for name, t in (("weight_ih", w_ih), ("weight_hh", w_hh), ("bias_ih", bias_ih), ("bias_hh", bias_hh), ("weight_out", weight_out)):
             if not bool(torch.isfinite(t.detach()).all()):  # the kernel's activations do not propagate NaN
                 raise ValueError(f"{name} has non-finite entries")
-        bias = bias_ih.detach().to(**f32).reshape(4 * H) + bias_hh.detach().to(**f32).reshape(4 * H)  # one f32 add
-        wx = torch.zeros((4 * H, 8), dtype=torch.float32)
-        wx[:, :5] = w_ih[order]
-        wx[:, 5] = bias[order]
-        whh = w_hh[order].contiguous()  # packed row order
+        whh, wx = lstm_pack(w_ih, w_hh, bias_ih.detach().to(**f32), bias_hh.detach().to(**f32), H)  # packed row order
         if H > 128:  # fragment-major for the streaming kernel: [row tile][k group][lane = (row & 31) + 32 * k half][4]
             whh = whh.reshape(4 * H // 32, 32, H // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(4 * H, H)
         self.whh = whh.to(dev)

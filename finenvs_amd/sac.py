@@ -1,0 +1,240 @@
+"""SAC's LSTM actor: the torch module a learner trains, and the fused rollout that acts with it in the kernel.
+
+``SACActorLSTM`` restates the reference's ``finenvs/agents/SAC/actor.py:ActorLSTM`` with shape ``(5, H, A)``:
+``nn.LSTM(5, H)`` over the observation window, ``last_layer = Linear(H, H)`` + Identity on the last hidden state
+(``LSTMNetwork`` duplicates the last size of ``(5, H)``, networks/lstm.py:21-23, 36-39), then ``mu_layer`` and
+``std_layer = Linear(H, A)`` with ``softplus`` on the std (SAC/actor.py:44-49) and the tanh-squashed sample with its
+log-probability (SAC/actor.py:51-61).  It runs per (env, asset) pair on ``(B, W, 5)`` windows; ``pair_states`` cuts a
+multi-asset observation ``(B, W, 5A)`` into those.
+
+``FusedSACRollout`` runs ``SACAgent.step`` -> ``env.step`` (SAC_agent.py:110-121) for K steps in one launch of
+``fe_env_rollout_sac`` (include/finenvs_amd_sac.h): the LSTM recurrence of ``FusedLSTMRollout`` plus the SAC head,
+with ``mu_layer`` / ``std_layer`` of one output per pair (``A = 1``).  Its ``forward`` is the no-grad actor half of
+``compute_targets`` (SAC_agent.py:200-225) on observation descriptors, e.g. replayed next states.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+from torch.distributions import Normal
+
+from . import _lib
+from .rollout import _FusedEvaluation, lstm_pack
+
+SAC_HIDDEN_SIZES = (32, 64, 128)
+
+
+class SACActorLSTM(nn.Module):
+    """The reference's SAC ``ActorLSTM((5, H, A), sequence_length=W)`` as a plain module (no optimizer inside):
+    submodules ``lstm``, ``last_layer``, ``mu_layer``, ``std_layer``; ``log_alpha`` the entropy temperature (a leaf
+    tensor outside ``parameters()``, as the reference keeps it with its own optimizer) and ``target_entropy = -A``."""
+
+    def __init__(self, H: int = 128, W: int = 4, A: int = 1, starting_alpha: float = 1.0, device=None):
+        super().__init__()
+        self.input_size, self.hidden_size, self.sequence_length, self.num_actions = 5, int(H), int(W), int(A)
+        self.lstm = nn.LSTM(5, self.hidden_size, num_layers=1, batch_first=True, device=device)
+        self.last_layer = nn.Sequential(nn.Linear(self.hidden_size, self.hidden_size, device=device), nn.Identity())
+        self.mu_layer = nn.Linear(self.hidden_size, self.num_actions, device=device)
+        self.std_layer = nn.Linear(self.hidden_size, self.num_actions, device=device)
+        self.log_alpha = torch.tensor(math.log(starting_alpha), device=device, requires_grad=True)
+        self.target_entropy = -float(self.num_actions)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self.log_alpha = fn(self.log_alpha.detach()).requires_grad_(True)  # .to(device) moves the temperature too
+        return self
+
+    def forward(self, states: torch.Tensor) -> torch.Tensor:
+        """(B, W, 5) -> the last layer's output z (B, H)."""
+        if states.dim() != 3 or states.shape[1] != self.sequence_length or states.shape[2] != self.input_size:
+            raise ValueError(f"states must be (B, {self.sequence_length}, {self.input_size}), got {tuple(states.shape)}")
+        out, _ = self.lstm(states)
+        return self.last_layer(out[:, -1, :])
+
+    def get_distribution(self, states: torch.Tensor) -> Normal:
+        hiddens = self.forward(states)
+        return Normal(self.mu_layer(hiddens), F.softplus(self.std_layer(hiddens)))
+
+    def get_actions_and_log_probs(self, states: torch.Tensor, eps: Optional[torch.Tensor] = None):
+        """(tanh(u), log_prob) with u = dist.rsample(), or u = loc + eps * scale for given standard normals ``eps``
+        (the same reparameterisation, with the caller's draws: what the fused path takes as ``noise``)."""
+        dist = self.get_distribution(states)
+        u = dist.rsample() if eps is None else dist.loc + eps * dist.scale
+        actions = torch.tanh(u)
+        log_probs = dist.log_prob(u) - torch.log(1 - torch.tanh(u).pow(2) + 1e-7)
+        return actions, log_probs
+
+    def step_actions(self, states: torch.Tensor, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``SACAgent.step`` (SAC_agent.py:110-121): tanh of the sample, the LAST row acting on the un-squashed mean."""
+        with torch.no_grad():
+            dist = self.get_distribution(states)
+            u = dist.rsample() if eps is None else dist.loc + eps * dist.scale
+            actions = torch.tanh(u)
+            actions[-1, :] = dist.loc[-1, :]
+        return actions
+
+
+def pair_states(states: torch.Tensor, A: int) -> torch.Tensor:
+    """(B, W, 5A) observations -> (B * A, W, 5) per-pair windows, row b * A + a (the fused heads' pair order)."""
+    B, W, F5 = states.shape
+    if F5 != 5 * A:
+        raise ValueError(f"states have {F5} features per row, expected 5 * {A}")
+    return states.reshape(B, W, A, 5).permute(0, 2, 1, 3).reshape(B * A, W, 5)
+
+
+def check_actor(actor: nn.Module) -> int:
+    """The hidden size of an actor the fused SAC head can run; ValueError otherwise."""
+    lstm = actor.lstm
+    if lstm.num_layers != 1 or lstm.bidirectional or lstm.input_size != 5 or not lstm.batch_first or lstm.proj_size:
+        raise ValueError("the fused SAC head needs nn.LSTM(5, H, num_layers=1, batch_first=True)")
+    H = int(lstm.hidden_size)
+    if H not in SAC_HIDDEN_SIZES:
+        raise ValueError(f"the fused SAC head supports H in {SAC_HIDDEN_SIZES} (got {H})")
+    last = actor.last_layer[0]
+    if last.in_features != H or last.out_features != H:
+        raise ValueError(f"last_layer must be Linear({H}, {H})")
+    for name in ("mu_layer", "std_layer"):
+        layer = getattr(actor, name)
+        if layer.in_features != H or layer.out_features != 1:
+            raise ValueError(f"{name} must be Linear({H}, 1): the fused head has one output per (env, asset) pair")
+    return H
+
+
+def pack_sac_weights(actor: nn.Module) -> Dict[str, torch.Tensor]:
+    """The actor's current parameters as fe_env_rollout_sac reads them (f32, on the parameters' device, no host sync):
+    whh / wx as ``lstm_pack``, ``wl`` the last layer fragment-major ([row tile][k group][lane = r + 32 h][4] =
+    W_l[32 t + r][8 g + 4 h + m]), ``bl``, ``wmu``, ``wstd`` (H), ``bmu`` / ``bstd`` (1)."""
+    H = check_actor(actor)
+    lstm = actor.lstm
+    whh, wx = lstm_pack(lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, H)
+    last = actor.last_layer[0]
+    wl = last.weight.detach().float().reshape(H // 32, 32, H // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(H, H)
+    return {
+        "whh": whh, "wx": wx, "wl": wl,
+        "bl": last.bias.detach().float().reshape(H).contiguous(),
+        "wmu": actor.mu_layer.weight.detach().float().reshape(H).contiguous(),
+        "bmu": actor.mu_layer.bias.detach().float().reshape(1).clone(),
+        "wstd": actor.std_layer.weight.detach().float().reshape(H).contiguous(),
+        "bstd": actor.std_layer.bias.detach().float().reshape(1).clone(),
+    }
+
+
+def unpack_last_layer(wl: torch.Tensor) -> torch.Tensor:
+    """Inverse of the fragment-major packing of ``pack_sac_weights``: (H, H) in torch's [out, in] order."""
+    H = int(wl.shape[0])
+    return wl.reshape(H // 32, H // 8, 2, 32, 4).permute(0, 3, 1, 2, 4).reshape(H, H)
+
+
+class FusedSACRollout(_FusedEvaluation):
+    """K env steps per launch with the SAC actor's head in the kernel (C ABI ``fe_env_rollout_sac``).
+
+    The actor's parameters are re-packed on the device at every ``run`` / ``forward`` (a few small launches and one
+    8-byte copy of the two output biases to the host, which the C ABI takes by value), so an optimizer step on ``actor``
+    is seen by the next call.  The actor must live on the env's device."""
+
+    def __init__(self, env, actor: nn.Module):
+        self.H = check_actor(actor)
+        if env.redraw != "device" and not env.evaluate:
+            raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
+        if actor.lstm.weight_hh_l0.device != torch.device(env._dev):
+            raise ValueError(f"the actor's parameters must live on the env's device {env._dev}")
+        self.env, self.actor = env, actor
+        dev = env._dev
+        self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
+        self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
+        self._lr32 = getattr(env, "_log_return_f32", None)
+        if self._lr32 is None:
+            self._lr32 = env.log_return_environments.float().contiguous()
+        self.means = self.stds = None
+        self.sync_from_env()
+
+    def _weights(self):
+        w = pack_sac_weights(self.actor)
+        if w["whh"].device != torch.device(self.env._dev):
+            raise ValueError(f"the actor's parameters must live on the env's device {self.env._dev}")
+        # the two output biases are kernel arguments: one small copy to the host, ordered after any pending update
+        bmu, bstd = torch.cat([w["bmu"], w["bstd"]]).cpu().tolist()
+        self._packed = w  # kept alive until the launch has been queued
+        return (self._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(), w["bl"].data_ptr(),
+                w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, self.H)
+
+    def _check_noise(self, noise, shape):
+        if noise is None:
+            return None
+        if not isinstance(noise, torch.Tensor) or noise.dtype is not torch.float32 or tuple(noise.shape) != shape \
+                or noise.device != torch.device(self.env._dev):
+            raise ValueError(f"noise must be a {shape} float32 tensor of standard normals on {self.env._dev}, got "
+                             f"{getattr(noise, 'dtype', type(noise))} {tuple(getattr(noise, 'shape', ()))} on "
+                             f"{getattr(noise, 'device', None)}")
+        return noise.contiguous()
+
+    def run(self, num_steps: int, noise: Optional[torch.Tensor] = None, record_means: bool = False,
+            record_stds: bool = False, trajectory=None):
+        """Returns (actions (K, N, A) f32, rewards (K, N) f64, dones (K, N) int32).
+
+        With ``noise`` -- (K, N, A) f32 standard normals from the caller's generator -- every env acts with
+        ``tanh(mu + eps * std)`` except the training-mode env's evaluation env, which acts on ``mu`` (SACAgent.step,
+        SAC_agent.py:110-121); the env scales, rounds and clamps the action as ``env.step`` does, so a mean beyond
+        [-1, 1] trades the clamped amount.  Without noise every env acts on ``mu``: the deterministic evaluation form.
+        (An evaluate-mode env has no evaluation env, so there every env samples, while the reference's ``agent.step``
+        overwrites the LAST row with the mean whatever the env's mode; a caller who wants deterministic evaluation
+        passes no noise.)  ``record_means`` / ``record_stds`` keep mu / std in ``self.means`` / ``self.stds``
+        ((K, N, A)).  ``trajectory``: an empty ``TrajectoryBuffer(K, N, A, states=True)`` without capacity padding,
+        filled as ``FusedLSTMRollout.run`` fills it (``ReplayBuffer.extend(trajectory)`` then stores the chunk)."""
+        env, K = self.env, int(num_steps)
+        N, A, dev = env.num_envs, env.num_assets, env._dev
+        if K < 1:
+            raise ValueError("num_steps must be >= 1")
+        noise = self._check_noise(noise, (K, N, A))
+        src_out = pos_out = None
+        if trajectory is not None:
+            tr = trajectory
+            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
+                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
+                                 "without capacity padding")
+            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
+            src_out, pos_out = tr.obs_src, tr.obs_pos
+        else:
+            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev)
+            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
+            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
+        self._begin_run()
+        w = self._weights()
+        self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
+        self.stds = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_stds else None
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _lib.check(env._lib.fe_env_rollout_sac(
+            env._handle, *w, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(), ptr(noise), actions.data_ptr(),
+            ptr(self.means), ptr(self.stds), rewards.data_ptr(), dones.data_ptr(), ptr(src_out), ptr(pos_out),
+            env._stream()))
+        self._end_run()
+        if trajectory is not None:
+            trajectory.mark_filled(K)
+        return actions, rewards, dones
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, noise: Optional[torch.Tensor] = None):
+        """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` f64 -- rows of a
+        ``TrajectoryBuffer(states=True)`` or of the replay ring) without stepping the env: (actions, log_probs, means,
+        stds), each (B, A) f32.  ``actions = tanh(mu + eps * std)`` and ``log_probs`` (SAC/actor.py:51-61) need
+        ``noise`` (B, A) and are None without it; every descriptor samples (no evaluation env here)."""
+        env, A = self.env, self.env.num_assets
+        B = int(obs_src.numel())
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
+        noise = self._check_noise(noise, (B, A))
+        dev = env._dev
+        means = torch.empty((B, A), dtype=torch.float32, device=dev)
+        stds = torch.empty((B, A), dtype=torch.float32, device=dev)
+        actions = torch.empty((B, A), dtype=torch.float32, device=dev) if noise is not None else None
+        log_probs = torch.empty((B, A), dtype=torch.float32, device=dev) if noise is not None else None
+        if B:
+            self._check_epoch()
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            _lib.check(env._lib.fe_sac_forward(
+                env._handle, *self._weights(), src.data_ptr(), pos.data_ptr(), B, ptr(noise), ptr(actions),
+                ptr(log_probs), means.data_ptr(), stds.data_ptr(), env._stream()))
+        return actions, log_probs, means, stds

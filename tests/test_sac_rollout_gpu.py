@@ -1,0 +1,301 @@
+"""GPU: the SAC actor's head on the fused LSTM rollout (fe_env_rollout_sac / fe_sac_forward, finenvs_amd/sac.py).
+
+* numerics: ``forward()`` on observation descriptors against ``SACActorLSTM`` in fp32 on the rendered observations --
+  mu, std and tanh(u) within 1e-5 absolute, log_probs within 1e-3 where |u| <= 4 (the squash term amplifies tanh's
+  last-ulp error near saturation) and finite everywhere;
+* env parity: the actions ``run(K, noise)`` recorded, stepped through the oracle's env one step at a time, give the same
+  rewards, dones, end state and trajectory descriptors bit for bit; lock-step, the actions are within 1e-5 of the torch
+  actor on the oracle's observations;
+* internal consistency bit for bit: ``forward`` on the trajectory rows equals ``run``'s actions, run(16); run(16) equals
+  run(32); the replay ring filled by ``extend`` equals per-step ``store``.
+"""
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import assert_bits
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def fe():
+    import finenvs_amd
+
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    return finenvs_amd
+
+
+@pytest.fixture(scope="module")
+def fo():
+    from oracle import fe_oracle
+
+    fe_oracle.build()
+    return fe_oracle
+
+
+def t2n(t):
+    return t.detach().cpu().numpy()
+
+
+def _make(fe, fo, N, A, W, days, bars, drop, evaluate, seed, obs_dtype=torch.float64):
+    from finenvs_amd.data import synthetic
+
+    prices, day_id, _ = synthetic.synthetic_series(days, A, bars, seed, drop)
+    P, LR, *_ = fo.tables_from_series(prices, day_id, W)
+    D = P.shape[0]
+    idx = (np.arange(N) * 7 + 1) % D
+    kw = dict(num_intervals=W, evaluate=evaluate, starting_balance=2000)
+    ref = fo.OracleEnv(P, LR, env_indices=idx, redraw_mode=1, seed=9, auto_emit=False, **kw)
+    ref.redraw_counter[0] = 1
+    env = fe.TimeSeriesEnv(tables=(P, LR), env_indices=idx, redraw="device", seed=9, obs_dtype=obs_dtype, **kw)
+    return ref, env
+
+
+def _actor(H, W, seed, mu_bias=0.0):
+    """SACActorLSTM with the input weights scaled up so that log-returns of ~1e-3 move the gates, and means / stds
+    spread over a trading range."""
+    from finenvs_amd.sac import SACActorLSTM
+
+    torch.manual_seed(seed)
+    actor = SACActorLSTM(H=H, W=W)
+    with torch.no_grad():
+        actor.lstm.weight_ih_l0[:, :4].mul_(6.0 * np.sqrt(H))
+        actor.lstm.weight_ih_l0[:, 4].mul_(4.0)
+        actor.mu_layer.weight.mul_(8.0)
+        actor.mu_layer.bias.add_(mu_bias)
+        actor.std_layer.weight.mul_(4.0)
+    return actor.cuda()
+
+
+def _torch_head(actor, obs, A, eps=None):
+    """(mu, std, tanh(u), log_prob, u) of the torch actor per pair on a rendered observation (N, W, 5A): (N, A) each."""
+    from finenvs_amd.sac import pair_states
+
+    N = obs.shape[0]
+    with torch.no_grad():
+        dist = actor.get_distribution(pair_states(obs.float(), A))
+        mu, sd = dist.loc.reshape(N, A), dist.scale.reshape(N, A)
+        if eps is None:
+            return mu, sd, None, None, None
+        act, lp = actor.get_actions_and_log_probs(pair_states(obs.float(), A), eps.reshape(N * A, 1))
+        return mu, sd, act.reshape(N, A), lp.reshape(N, A), (mu + eps * sd)
+
+
+@pytest.mark.parametrize("N,A,W,H,obs_dtype,evaluate,drop", [
+    (300, 1, 4, 32, torch.float64, False, 0.0),
+    (260, 1, 16, 64, torch.float32, False, 0.1),    # ragged days, N = 2 x 128 + 4 (a partial tile)
+    (131, 3, 4, 128, torch.float64, True, 0.05),    # evaluate mode, several sleeves
+    (77, 3, 16, 32, torch.float32, True, 0.0),
+    (500, 1, 4, 128, torch.float32, False, 0.0),
+    (45, 3, 4, 64, torch.float64, False, 0.1),
+])
+def test_forward_against_torch_actor_fp32(fe, fo, N, A, W, H, obs_dtype, evaluate, drop):
+    from finenvs_amd.sac import FusedSACRollout
+
+    ref, env = _make(fe, fo, N, A, W, 6, 50, drop, evaluate, seed=N + H, obs_dtype=obs_dtype)
+    actor = _actor(H, W, seed=H + W)
+    roll = FusedSACRollout(env, actor)
+    g = torch.Generator(device="cuda").manual_seed(3)
+    worst = {}
+    for rep in range(6):
+        eps = torch.randn((N, A), generator=g, device="cuda")
+        obs = roll.observation()
+        act, lp, mu, sd = roll.forward(roll.obs_src, roll.obs_pos, noise=eps)
+        _, _, mu2, sd2 = roll.forward(roll.obs_src, roll.obs_pos)
+        assert_bits(t2n(mu2), t2n(mu), "mu without noise")
+        assert_bits(t2n(sd2), t2n(sd), "std without noise")
+        tmu, tsd, tact, tlp, u = _torch_head(actor, obs, A, eps)
+        for name, a, b in (("mu", mu, tmu), ("std", sd, tsd), ("tanh(u)", act, tact)):
+            torch.testing.assert_close(a, b, rtol=0, atol=1e-5, msg=name)
+            worst[name] = max(worst.get(name, 0.0), float((a - b).abs().max()))
+        assert bool(torch.isfinite(lp).all())
+        inner = u.abs() <= 4
+        torch.testing.assert_close(lp[inner], tlp[inner], rtol=0, atol=1e-3)
+        roll.run(2, noise=torch.randn((2, N, A), generator=g, device="cuda"))
+    assert float(tmu.std()) > 0.05 and float(tsd.std()) > 1e-3, "the head must actually depend on the observation"
+    print(f"worst |kernel - torch| {worst}")
+
+
+@pytest.mark.parametrize("N,A,W,H,obs_dtype,evaluate,drop", [
+    (300, 1, 4, 32, torch.float64, False, 0.0),
+    (260, 1, 16, 128, torch.float32, False, 0.1),
+    (77, 3, 4, 64, torch.float64, True, 0.05),
+    (40, 3, 16, 128, torch.float64, False, 0.0),
+])
+def test_run_equals_oracle_env_bit_for_bit(fe, fo, N, A, W, H, obs_dtype, evaluate, drop):
+    from finenvs_amd.sac import FusedSACRollout
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    days, bars = 5, 40
+    ref, env = _make(fe, fo, N, A, W, days, bars, drop, evaluate, seed=3 * N + W, obs_dtype=obs_dtype)
+    actor = _actor(H, W, seed=W + H)
+    roll = FusedSACRollout(env, actor)
+    obs = ref.reset().copy()
+    g = torch.Generator(device="cuda").manual_seed(N)
+    K, reps = 8, 2 * (bars + 3) // 8 + 1
+    seen = set()
+    for rep in range(reps):
+        noise = torch.randn((K, N, A), generator=g, device="cuda")
+        traj = TrajectoryBuffer(K, N, A, states=True)
+        acts, rews, dones = roll.run(K, noise=noise, trajectory=traj, record_means=True)
+        for k in range(K):
+            if obs_dtype == torch.float64:
+                assert_bits(t2n(traj.states(env, k)), obs, f"rep {rep} step {k} trajectory state")
+            ob = torch.from_numpy(obs).cuda()
+            tmu, tsd, tact, _, _ = _torch_head(actor, ob, A, noise[k])
+            want = tact.clone()
+            if not evaluate:
+                want[-1] = tmu[-1]  # the eval env acts on the mean
+            torch.testing.assert_close(acts[k], want, rtol=0, atol=1e-5)
+            a_k = t2n(acts[k])
+            seen.update(np.unique(np.clip(np.rint(a_k * 5.5), -5, 5)).tolist())
+            obs, r_ref, d_ref, _ = ref.step(a_k)
+            obs = obs.copy()
+            assert_bits(t2n(rews[k]), r_ref, f"rep {rep} step {k} rewards")
+            assert_bits(t2n(dones[k]), d_ref, f"rep {rep} step {k} dones")
+        if obs_dtype == torch.float64:
+            assert_bits(t2n(traj.states(env, K)), obs, f"rep {rep} last trajectory state")
+            assert_bits(t2n(roll.observation()), obs, f"rep {rep} observation()")
+        assert_bits(t2n(env.cash), ref.cash, f"rep {rep} cash")
+        assert_bits(t2n(env.margin), ref.margin, f"rep {rep} margin")
+        assert_bits(t2n(env.env_indices), ref.env_idx, f"rep {rep} env_idx")
+        if evaluate and int(ref.n_terminated[0]) == N:
+            env.reset_evaluation_metrics()
+            ref.terminated[:] = 0; ref.episode_returns[:] = 0; ref.n_terminated[0] = 0
+    assert len(seen) >= 4, f"the policy must trade in both directions (share changes seen: {sorted(seen)})"
+
+
+def _twins(fe, fo, N, A, W, H, evaluate=False, mu_bias=0.0):
+    from finenvs_amd.sac import FusedSACRollout
+
+    out = []
+    for _ in range(2):
+        ref, env = _make(fe, fo, N, A, W, 5, 60, 0.05, evaluate, seed=17)
+        out.append((env, FusedSACRollout(env, _actor(H, W, seed=5, mu_bias=mu_bias))))
+    return out
+
+
+@pytest.mark.parametrize("H", [32, 64, 128])
+def test_forward_on_trajectory_rows_and_chunking_equal_run_bit_for_bit(fe, fo, H):
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    N, A, W = 203, 3, 4
+    (env1, r1), (env2, r2) = _twins(fe, fo, N, A, W, H)
+    g = torch.Generator(device="cuda").manual_seed(H)
+    noise = torch.randn((32, N, A), generator=g, device="cuda")
+    traj = TrajectoryBuffer(32, N, A, states=True)
+    acts, rews, dones = r1.run(32, noise=noise, trajectory=traj, record_means=True, record_stds=True)
+    a_a, r_a, d_a = r2.run(16, noise=noise[:16].clone())
+    a_b, r_b, d_b = r2.run(16, noise=noise[16:].clone())
+    assert_bits(t2n(acts), t2n(torch.cat([a_a, a_b])), "run(16); run(16) actions")
+    assert_bits(t2n(rews), t2n(torch.cat([r_a, r_b])), "rewards")
+    assert_bits(t2n(dones), t2n(torch.cat([d_a, d_b])), "dones")
+    assert_bits(t2n(env1.cash), t2n(env2.cash), "cash")
+    src, pos = traj.obs_src[:32].reshape(-1), traj.obs_pos[:32].reshape(-1, A)
+    f_act, f_lp, f_mu, f_sd = r1.forward(src, pos, noise=noise.reshape(-1, A))
+    f_act, f_mu, f_sd = f_act.reshape(32, N, A), f_mu.reshape(32, N, A), f_sd.reshape(32, N, A)
+    assert_bits(t2n(f_mu), t2n(r1.means), "forward means == run means")
+    assert_bits(t2n(f_sd), t2n(r1.stds), "forward stds == run stds")
+    assert_bits(t2n(f_act[:, :-1]), t2n(acts[:, :-1]), "forward actions == run actions")
+    assert_bits(t2n(acts[:, -1]), t2n(r1.means[:, -1]), "the eval env acts on the mean")
+
+
+def test_eval_env_acts_on_the_unsquashed_mean(fe, fo):
+    N, A, W, H = 150, 1, 4, 64
+    (env, roll), _ = _twins(fe, fo, N, A, W, H, mu_bias=1.5)
+    noise = torch.randn((8, N, A), device="cuda")
+    acts, _, _ = roll.run(8, noise=noise, record_means=True)
+    assert_bits(t2n(acts[:, -1]), t2n(roll.means[:, -1]), "eval env")
+    assert float(roll.means[:, -1].abs().max()) > 1.0, "the test needs a mean outside [-1, 1] at the eval env"
+    assert float(acts[:, :-1].abs().max()) <= 1.0
+    # without noise every env acts on the mean
+    acts0, _, _ = roll.run(4, record_means=True)
+    assert_bits(t2n(acts0), t2n(roll.means), "deterministic form")
+    # an evaluate-mode env has no eval env: every env samples
+    (ev, rev), _ = _twins(fe, fo, N, A, W, H, evaluate=True, mu_bias=1.5)
+    a2, _, _ = rev.run(4, noise=noise[:4].clone())
+    assert float(a2.abs().max()) <= 1.0
+
+
+def test_replay_extend_after_a_fused_chunk_equals_per_step_store(fe, fo):
+    from finenvs_amd.replay import ReplayBuffer
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    N, A, W, H, K = 96, 3, 4, 32, 8
+    (env, roll), _ = _twins(fe, fo, N, A, W, H)
+    rb_x, rb_s = ReplayBuffer(env, max_size=5 * N), ReplayBuffer(env, max_size=5 * N)
+    for chunk in range(2):  # the second chunk wraps the ring
+        traj = TrajectoryBuffer(K, N, A, states=True)
+        roll.run(K, noise=torch.randn((K, N, A), device="cuda"), trajectory=traj)
+        rb_x.extend(traj)
+        for k in range(K):
+            rb_s.store((traj.obs_src[k], traj.obs_pos[k]), traj.actions[k], traj.rewards[k],
+                       (traj.obs_src[k + 1], traj.obs_pos[k + 1]), traj.dones[k])
+    assert (rb_x.head, rb_x.size()) == (rb_s.head, rb_s.size())
+    idx = torch.arange(rb_x.size(), device="cuda")
+    bx, bs = rb_x.get_mini_batch(0, indices=idx), rb_s.get_mini_batch(0, indices=idx)
+    for key in bx:
+        assert_bits(t2n(bx[key]), t2n(bs[key]), key)
+
+
+def test_an_optimizer_step_is_seen_by_the_next_run(fe, fo):
+    N, A, W, H = 64, 1, 4, 64
+    (env1, r1), (env2, r2) = _twins(fe, fo, N, A, W, H)
+    noise = torch.randn((4, N, A), device="cuda")
+    obs = r1.observation()
+    a_old, _, _ = r2.run(4, noise=noise)  # the twin keeps the initial weights
+    actor = r1.actor
+    opt = torch.optim.Adam(actor.parameters(), lr=1e-2)
+    loss = actor.get_distribution(torch.randn((16, W, 5), device="cuda") * 1e-2).loc.pow(2).mean()
+    opt.zero_grad()
+    loss.backward()
+    opt.step()
+    a_new, _, _ = r1.run(4, noise=noise)
+    assert not torch.equal(a_new[0], a_old[0])
+    _, _, tact, _, _ = _torch_head(actor, obs, A, noise[0])
+    torch.testing.assert_close(a_new[0, :-1], tact[:-1], rtol=0, atol=1e-5)
+
+
+def test_refusals(fe, fo):
+    from finenvs_amd.sac import FusedSACRollout, SACActorLSTM
+
+    N, A, W = 20, 1, 4
+    ref, env = _make(fe, fo, N, A, W, 5, 40, 0.0, False, seed=1)
+    roll = FusedSACRollout(env, _actor(32, W, seed=0))
+    for bad in (torch.zeros((4, N + 1, A), device="cuda"),           # shape
+                torch.zeros((4, N, A), dtype=torch.float64, device="cuda"),  # dtype
+                torch.zeros((4, N, A)),                                # device
+                torch.zeros((3, N, A), device="cuda")):                # K
+        with pytest.raises(ValueError):
+            roll.run(4, noise=bad)
+    with pytest.raises(ValueError):
+        roll.forward(roll.obs_src, roll.obs_pos, noise=torch.zeros((N, A + 1), device="cuda"))
+    for actor in (SACActorLSTM(H=256, W=W), SACActorLSTM(H=48, W=W), SACActorLSTM(H=32, W=W, A=2)):
+        with pytest.raises(ValueError):
+            FusedSACRollout(env, actor.cuda())
+    two = SACActorLSTM(H=32, W=W)
+    two.lstm = torch.nn.LSTM(5, 32, num_layers=2, batch_first=True)
+    with pytest.raises(ValueError, match="num_layers"):
+        FusedSACRollout(env, two.cuda())
+    with pytest.raises(ValueError):
+        FusedSACRollout(env, SACActorLSTM(H=32, W=W))  # the actor on the host
+    # the C ABI names the supported sizes
+    from finenvs_amd import _lib
+
+    lib = _lib.load()
+    rc = lib.fe_sac_forward(env._handle, roll._lr32.data_ptr(), 1, 1, 1, 1, 1, 0.0, 1, 0.0, 256, roll.obs_src.data_ptr(),
+                            roll.obs_pos.data_ptr(), N, None, None, None, None, None, None)
+    assert rc == _lib.FE_ERR_ARG and b"32, 64 or 128" in lib.fe_last_error()
+
+
+def test_example_runs_to_finite_losses():
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import sac_time_series
+
+    history = sac_time_series.main(num_envs=256, iterations=6, chunk=4, batch=128, quiet=True)
+    assert history and all(np.isfinite([h["critic_loss"], h["actor_loss"], h["alpha_loss"]]).all() for h in history)
