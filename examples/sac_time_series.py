@@ -8,7 +8,12 @@ Rollout chunks come from ``FusedSACRollout.run(K, noise, trajectory=)`` -- K env
 and go into the device replay ring with one ``ReplayBuffer.extend``; every training step samples a mini-batch whose
 states and next states are rendered in one launch.  The last env is the evaluation env: it acts on the mean.
 
-    python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256]
+With ``--fused-targets`` the no-grad target half of every training step runs on the replayed descriptors instead: the
+actor in ``FusedSACRollout.forward`` and both target critics plus the Bellman combination in
+``FusedTwinCritic.sac_targets`` (the next states are never rendered).  It draws the same indices and normals as the
+default path, so with the same seed both compute the same targets up to fp32 rounding.
+
+    python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
 """
 import argparse
 import copy
@@ -16,29 +21,16 @@ import os
 import sys
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
+from finenvs_amd.critic import CriticLSTM, FusedTwinCritic  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
 from finenvs_amd.replay import ReplayBuffer  # noqa: E402
 from finenvs_amd.sac import FusedSACRollout, SACActorLSTM  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
-
-
-class CriticLSTM(nn.Module):
-    """The reference's CriticLSTM: LSTM over [state row | action] per window row, Linear(H, 1) on the last step."""
-
-    def __init__(self, H, W):
-        super().__init__()
-        self.lstm = nn.LSTM(5 + 1, H, num_layers=1, batch_first=True)
-        self.out = nn.Linear(H, 1)
-
-    def forward(self, states, actions):
-        x = torch.cat([states, actions.unsqueeze(1).repeat(1, states.shape[1], 1)], dim=2)  # match_actions_dim_with_states
-        return self.out(self.lstm(x)[0][:, -1, :])
 
 
 def soft_update(target, source, rho):
@@ -48,7 +40,7 @@ def soft_update(target, source, rho):
 
 
 def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
-         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False):
+         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False):
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
@@ -61,6 +53,7 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
     alpha_opt = torch.optim.Adam([actor.log_alpha], lr=lr)
     critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
     roll = FusedSACRollout(env, actor)  # re-packs the actor's weights at every run: updates are seen right away
+    twin = FusedTwinCritic(env, critic_1t, critic_2t) if fused_targets else None  # re-packs at every call, too
     gen = torch.Generator(device=dev).manual_seed(seed)
     history = []
     for it in range(iterations):
@@ -71,13 +64,20 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
         if buffer.size() < batch:
             continue
         for _ in range(updates_per_chunk):
-            b = buffer.get_mini_batch(batch)
-            s, a, s2 = b["states"], b["actions"], b["next_states"]
-            r, d = b["rewards"] * reward_scale, b["dones"]
-            with torch.no_grad():  # compute_targets (SAC_agent.py:200-225)
-                a2, lp2 = actor.get_actions_and_log_probs(s2)
-                q2 = torch.min(critic_1t(s2, a2), critic_2t(s2, a2))
-                y = r + gamma * (1.0 - d) * (q2 - actor.log_alpha.exp() * lp2.mean(dim=1, keepdim=True))
+            if fused_targets:  # the same draws as below: get_mini_batch's indices, then rsample's normals
+                idx = torch.randint(0, buffer.size(), (batch,), device=dev)
+                b = buffer.get_mini_batch(batch, indices=idx)
+                s, a = b["states"], b["actions"]
+                eps = torch.randn((batch, 1), device=dev)
+                y = twin.sac_targets(buffer, idx, roll, eps, gamma, actor.log_alpha, reward_scale=reward_scale)
+            else:
+                b = buffer.get_mini_batch(batch)
+                s, a, s2 = b["states"], b["actions"], b["next_states"]
+                r, d = b["rewards"] * reward_scale, b["dones"]
+                with torch.no_grad():  # compute_targets (SAC_agent.py:200-225)
+                    a2, lp2 = actor.get_actions_and_log_probs(s2)
+                    q2 = torch.min(critic_1t(s2, a2), critic_2t(s2, a2))
+                    y = r + gamma * (1.0 - d) * (q2 - actor.log_alpha.exp() * lp2.mean(dim=1, keepdim=True))
             critic_loss = F.mse_loss(critic_1(s, a), y) + F.mse_loss(critic_2(s, a), y)
             critic_opt.zero_grad()
             critic_loss.backward()
@@ -110,5 +110,6 @@ if __name__ == "__main__":
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--chunk", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--fused-targets", action="store_true")
     a = ap.parse_args()
-    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch)
+    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets)

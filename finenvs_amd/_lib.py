@@ -132,6 +132,21 @@ SAC_SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp]),
 }
 
+
+# include/finenvs_amd_critic.h: the twin LSTM critics and their Bellman targets (finenvs_amd/critic.py; same library)
+class FeCriticWeights(C.Structure):
+    """struct fe_critic_weights of include/finenvs_amd_critic.h."""
+
+    _fields_ = [("whh", _vp), ("wx", _vp), ("wout", _vp), ("bout", _vp)]
+
+
+_cw = C.POINTER(FeCriticWeights)
+CRITIC_SIGNATURES = {
+    "fe_twin_q_forward": (C.c_int, [_vp, _vp, _cw, _cw, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "fe_twin_q_target": (C.c_int, [_vp, _vp, _cw, _cw, _i32, C.POINTER(FeReplayRing), _i64, _i64, _vp, _i64, _vp, _vp,
+                                   C.c_float, C.c_float, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -156,7 +171,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
                 "finenvs_amd has no CPU fallback"
             ) from exc
     lib = C.CDLL(p)
-    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
+                         **CRITIC_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

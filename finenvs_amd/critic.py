@@ -1,0 +1,257 @@
+"""SAC's and TD3's twin LSTM critics: the torch module a learner trains, and the fused no-grad target half.
+
+``CriticLSTM`` restates the reference's ``CriticLSTM((6, H, 1), W)`` (finenvs/agents/SAC/critic.py, the same class in
+agents/TD3/critic.py; networks/lstm.py:28-57) for one asset: ``nn.LSTM(6, H)`` over ``[state row | action]`` -- the
+action repeated over the window (agent_utils.py:5-14) -- and ``last_layer = Linear(H, 1)`` + Identity on the last hidden
+state.  Its submodule names are the reference's, so a reference ``state_dict`` loads unchanged.
+
+``FusedTwinCritic`` evaluates two such critics on observation descriptors in one launch (C ABI ``fe_twin_q_forward``,
+include/finenvs_amd_critic.h) and forms the Bellman targets of ``SACAgent.compute_targets`` (SAC_agent.py:200-227) and
+``TD3Agent.compute_targets`` (TD3_agent.py:231-251) straight from the replay ring (``fe_twin_q_target``): the sampled
+next states are never rendered.  The actor half runs on the same descriptors in ``FusedSACRollout.forward`` /
+``FusedLSTMRollout.forward``.  Scope: one asset (the reference's multi-asset critic is ``nn.LSTM(5A + A, H)`` over the
+whole env, not a per-pair network) and H in {32, 64, 128}.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .rollout import lstm_pack, lstm_row_order
+
+CRITIC_HIDDEN_SIZES = (32, 64, 128)
+
+
+def match_actions_dim_with_states(states: torch.Tensor, actions: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """agent_utils.py:5-14: actions (B, A) repeated over the window of (B, W, F) states, and the dim to concatenate on."""
+    if actions.dim() < states.dim():
+        return actions.unsqueeze(1).repeat(1, states.shape[1], 1), 2
+    return actions, 1
+
+
+class CriticLSTM(nn.Module):
+    """The reference's ``CriticLSTM((6, H, 1), sequence_length=W)`` as a plain module (no optimizer inside): submodules
+    ``lstm = nn.LSTM(6, H, batch_first=True)`` and ``last_layer = Sequential(Linear(H, 1), Identity())``."""
+
+    def __init__(self, H: int = 128, W: int = 4, device=None):
+        super().__init__()
+        self.input_size, self.hidden_size, self.output_size, self.sequence_length = 6, int(H), 1, int(W)
+        self.lstm = nn.LSTM(6, self.hidden_size, num_layers=1, batch_first=True, device=device)
+        self.last_layer = nn.Sequential(nn.Linear(self.hidden_size, 1, device=device), nn.Identity())
+
+    def forward(self, states: torch.Tensor, actions: torch.Tensor) -> torch.Tensor:
+        """states (B, W, 5), actions (B, 1) -> Q (B, 1)."""
+        if states.dim() != 3 or states.shape[1] != self.sequence_length or states.shape[2] != 5:
+            raise ValueError(f"states must be (B, {self.sequence_length}, 5), got {tuple(states.shape)}")
+        actions, dim = match_actions_dim_with_states(states, actions)
+        out, _ = self.lstm(torch.cat([states, actions], dim=dim))
+        return self.last_layer(out[:, -1, :])
+
+
+def check_critic(critic: nn.Module) -> int:
+    """The hidden size of a critic the fused twin critic can run; ValueError otherwise."""
+    lstm = getattr(critic, "lstm", None)
+    if not isinstance(lstm, nn.LSTM):
+        raise ValueError("the fused critic needs a module with an nn.LSTM `lstm`")
+    if lstm.num_layers != 1 or lstm.bidirectional or lstm.input_size != 6 or not lstm.batch_first or lstm.proj_size:
+        raise ValueError("the fused critic needs nn.LSTM(6, H, num_layers=1, batch_first=True) (5 observation features "
+                         "and one action: A = 1)")
+    H = int(lstm.hidden_size)
+    if H not in CRITIC_HIDDEN_SIZES:
+        raise ValueError(f"the fused critic supports H in {CRITIC_HIDDEN_SIZES} (got {H})")
+    last = getattr(critic, "last_layer", None)
+    if not isinstance(last, nn.Sequential) or len(last) != 2 or not isinstance(last[0], nn.Linear) \
+            or not isinstance(last[1], nn.Identity) or last[0].in_features != H or last[0].out_features != 1 \
+            or last[0].bias is None:
+        raise ValueError(f"last_layer must be Sequential(Linear({H}, 1), Identity())")
+    return H
+
+
+def pack_critic_weights(critic: nn.Module) -> Dict[str, torch.Tensor]:
+    """The critic's current parameters as fe_twin_q_forward reads them (f32, on the parameters' device, no host sync):
+    whh / wx as ``lstm_pack`` of the five observation inputs (slot 5 = b_ih + b_hh) plus slot 6 = the action's input
+    weight ``w_ih[:, 5]``; ``wout`` (H) and ``bout`` (1)."""
+    H = check_critic(critic)
+    lstm = critic.lstm
+    w_ih = lstm.weight_ih_l0.detach().float()
+    whh, wx = lstm_pack(w_ih[:, :5], lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, H)
+    wx[:, 6] = w_ih[lstm_row_order(H).to(w_ih.device), 5]
+    last = critic.last_layer[0]
+    return {
+        "whh": whh, "wx": wx,
+        "wout": last.weight.detach().float().reshape(H).contiguous(),
+        "bout": last.bias.detach().float().reshape(1).contiguous(),
+    }
+
+
+class FusedTwinCritic:
+    """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
+
+    The critics' parameters are re-packed on the device at every call (a few small launches, no host round trip), so an
+    optimizer step or a soft update is seen by the next call.  Both critics must live on the env's device."""
+
+    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module):
+        if int(env.num_assets) != 1:
+            raise ValueError(f"the fused twin critic runs one asset (the env has {env.num_assets}): the reference's critic "
+                             "for A > 1 is one nn.LSTM(5A + A, H) over the whole env's window, not a per-(env, asset) pair "
+                             "network")
+        H1, H2 = check_critic(critic_1), check_critic(critic_2)
+        if H1 != H2:
+            raise ValueError(f"the two critics must have the same hidden size (got {H1} and {H2})")
+        self.env, self.critic_1, self.critic_2, self.H = env, critic_1, critic_2, H1
+        self._check_devices()
+        self._lr32 = getattr(env, "_log_return_f32", None)
+        if self._lr32 is None:
+            self._lr32 = env.log_return_environments.float().contiguous()
+        self.last: Dict[str, torch.Tensor] = {}
+
+    def _check_devices(self) -> None:
+        dev = torch.device(self.env._dev)
+        for name, c in (("critic_1", self.critic_1), ("critic_2", self.critic_2)):
+            if any(p.device != dev for p in c.parameters()):
+                raise ValueError(f"{name}'s parameters must live on the env's device {dev}")
+
+    def _weights(self):
+        self._check_devices()
+        w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
+        self._packed = w  # kept alive until the launch has been queued
+        return [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
+                for x in w]
+
+    def _vector(self, t, B: int, name: str, dtype=torch.float32) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.dtype is not dtype or t.numel() != B or t.device != torch.device(self.env._dev):
+            raise ValueError(f"{name} must be a {dtype} tensor of {B} elements ((B,) or (B, 1)) on {self.env._dev}, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
+        return t.reshape(B).contiguous()
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
+        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
+        env = self.env
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        act = self._vector(actions, B, "actions")
+        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        if B:
+            c1, c2 = self._weights()
+            _lib.check(env._lib.fe_twin_q_forward(
+                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, src.data_ptr(), pos.data_ptr(),
+                act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
+        return q1, q2
+
+    __call__ = forward
+
+    # ---------------------------------------------------------------- targets from the replay ring
+    def _indices(self, buffer, indices, batch_size) -> torch.Tensor:
+        if buffer.A != 1 or buffer.W != int(self.env.num_intervals) or buffer.device != torch.device(self.env._dev):
+            raise ValueError("the replay buffer must hold one-asset descriptors of this env's tables, on its device")
+        buffer._ring.check_sample()
+        if indices is None:
+            if batch_size is None:
+                raise ValueError("give indices or batch_size")
+            # the draw ReplayBuffer.get_mini_batch makes (OPB:69): pass the same tensor to get_mini_batch for the grad half
+            return torch.randint(0, buffer.size(), (int(batch_size),), device=buffer.device)
+        if not isinstance(indices, torch.Tensor) or indices.dtype.is_floating_point or indices.dtype.is_complex \
+                or indices.dtype is torch.bool or indices.device != buffer.device:
+            raise ValueError(f"indices must be an integer tensor of logical indices on {buffer.device}")
+        return indices.reshape(-1).to(torch.int64).contiguous()
+
+    def _next_descriptors(self, buffer, idx):
+        # the actor half reads the sampled next states' descriptors (an out-of-range index wraps to some slot here; its
+        # target is NaN all the same and fe_twin_q_target counts it)
+        slots = buffer.physical(idx)
+        return buffer.next_src[slots], buffer.next_pos[slots]
+
+    def _targets(self, buffer, idx, next_actions, smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma,
+                 reward_scale) -> torch.Tensor:
+        env, B = self.env, int(idx.numel())
+        dev = env._dev
+        y = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        q1 = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        q2 = torch.empty((B, 1), dtype=torch.float32, device=dev)
+        if B:
+            c1, c2 = self._weights()
+            ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+            _lib.check(env._lib.fe_twin_q_target(
+                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
+                buffer.head, buffer.size(), idx.data_ptr(), B, next_actions.data_ptr(), ptr(smooth_noise),
+                float(smooth_std), float(smooth_clip), ptr(log_probs), ptr(alpha), float(gamma), float(reward_scale),
+                y.data_ptr(), q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
+        self.last = {"indices": idx, "next_actions": next_actions.reshape(B, 1), "q1": q1, "q2": q2}
+        return y
+
+    def sac_targets(self, buffer, indices: Optional[torch.Tensor], actor_roll, noise: Optional[torch.Tensor] = None,
+                    gamma: float = 0.99, log_alpha: Optional[torch.Tensor] = None, reward_scale: float = 1.0,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+        """``SACAgent.compute_targets`` (SAC_agent.py:200-227) for the transitions ``indices`` (logical, (B,)) of
+        ``buffer``: the actor half in ``actor_roll.forward`` (a ``FusedSACRollout``) on the sampled next descriptors with
+        ``noise`` (B, 1) standard normals -- by default ``torch.randn``, the draw ``rsample`` makes -- then both target
+        critics and ``y = r + gamma * (1 - d) * (min(q1, q2) - alpha * log_prob)`` with ``alpha = log_alpha.exp()``,
+        ``r`` the stored reward times ``reward_scale``.  (B, 1) float32.  ``indices=None`` draws ``batch_size`` of them as
+        ``get_mini_batch`` does; ``self.last`` keeps the indices, next actions, log-probabilities and values."""
+        from .sac import FusedSACRollout
+
+        if not isinstance(actor_roll, FusedSACRollout):
+            raise ValueError("actor_roll must be a FusedSACRollout (the SAC actor's head)")
+        if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.device != torch.device(self.env._dev):
+            raise ValueError(f"log_alpha must be a one-element tensor on {self.env._dev}")
+        idx = self._indices(buffer, indices, batch_size)
+        B = int(idx.numel())
+        if noise is None:
+            noise = torch.randn((B, 1), device=self.env._dev)
+        src, pos = self._next_descriptors(buffer, idx)
+        actions, log_probs, _, _ = actor_roll.forward(src, pos, noise=noise.reshape(B, 1))
+        alpha = log_alpha.detach().exp().float().reshape(1).contiguous()
+        y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale)
+        self.last.update(log_probs=log_probs, alpha=alpha)
+        return y
+
+    def td3_targets(self, buffer, indices: Optional[torch.Tensor], target_actor, noise: Optional[torch.Tensor] = None,
+                    gamma: float = 0.99, policy_std: float = 0.2, policy_clip: float = 0.5, reward_scale: float = 1.0,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+        """``TD3Agent.compute_targets`` (TD3_agent.py:231-251): the target actor (a ``FusedLSTMRollout`` with
+        ``output_activation="tanh"``) on the sampled next descriptors, the smoothed action ``clamp(a + clamp(noise *
+        policy_std, -policy_clip, policy_clip), -1, 1)`` with ``noise`` (B, 1) standard normals (default ``torch.randn``),
+        both target critics and ``y = r + gamma * (1 - d) * min(q1, q2)``.  (B, 1) float32."""
+        from .rollout import FusedLSTMRollout
+
+        if not isinstance(target_actor, FusedLSTMRollout) or target_actor.out_act != 0:
+            raise ValueError('target_actor must be a FusedLSTMRollout with output_activation="tanh"')
+        idx = self._indices(buffer, indices, batch_size)
+        B = int(idx.numel())
+        src, pos = self._next_descriptors(buffer, idx)
+        actions = target_actor.forward(src, pos)
+        if noise is None:
+            noise = torch.randn((B, 1), device=self.env._dev)
+        noise = self._vector(noise, B, "noise")
+        return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale)
+
+
+# ---------------------------------------------------------------- the torch restatements (host or device)
+def torch_sac_targets(actor, critic_1, critic_2, rewards, next_states, dones, eps, gamma: float, reward_scale: float = 1.0):
+    """``SACAgent.compute_targets`` (SAC_agent.py:200-227) in torch, its operations in its order, with the actor's
+    standard normals ``eps`` given: ``actor`` a ``SACActorLSTM``, next_states (B, W, 5), rewards / dones (B, 1)."""
+    with torch.no_grad():
+        next_actions, next_log_probs = actor.get_actions_and_log_probs(next_states, eps)
+        mean_log_probs = next_log_probs.mean(dim=1, keepdim=True)
+        q = torch.min(critic_1(next_states, next_actions), critic_2(next_states, next_actions))
+        next_entropy = -actor.log_alpha.exp() * mean_log_probs
+        return rewards * reward_scale + gamma * (1 - dones) * (q + next_entropy)
+
+
+def torch_td3_targets(target_actor, critic_1, critic_2, rewards, next_states, dones, eps, gamma: float, std: float,
+                      clip: float, reward_scale: float = 1.0):
+    """``TD3Agent.compute_targets`` (TD3_agent.py:231-251) in torch with the smoothing normals ``eps`` given:
+    ``target_actor`` maps (B, W, 5) to tanh actions (B, 1)."""
+    with torch.no_grad():
+        target_actions = target_actor(next_states.float())
+        clipped_noise = torch.clamp(eps * std, -clip, +clip)
+        target_actions = torch.clamp(target_actions + clipped_noise, -1, +1)
+        q = torch.minimum(critic_1(next_states, target_actions), critic_2(next_states, target_actions))
+        return rewards * reward_scale + gamma * (1 - dones) * q

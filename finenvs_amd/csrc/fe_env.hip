@@ -25,7 +25,7 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, ten files:
+// One translation unit, eleven files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
@@ -35,9 +35,10 @@
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
+//   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
-//                         five headers in include/
+//                         six headers in include/
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
 // reference's mixed f32/f64 tensor arithmetic; this file
@@ -60,6 +61,7 @@
 #include "finenvs_amd_evo.h"
 #include "finenvs_amd_replay.h"
 #include "finenvs_amd_sac.h"
+#include "finenvs_amd_critic.h"
 
 #include "fe_device_common.h"
 #include "fe_step_kernel.h"
@@ -68,6 +70,7 @@
 #include "fe_aux_kernels.h"
 #include "fe_evo_kernels.h"
 #include "fe_replay_kernels.h"
+#include "fe_critic_kernels.h"
 
 namespace {
 
@@ -1352,6 +1355,102 @@ int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const
     s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
     s.stds_out = stds_out; s.logp_out = log_probs_out;
     return launch_sac(env, s, count, "fe_sac_forward", stream);
+}
+
+// ---- include/finenvs_amd_critic.h: the twin LSTM critics and their Bellman targets ----
+static bool critic_weights_ok(const fe_critic_weights *c) { return c && c->whh && c->wx && c->wout && c->bout; }
+
+// The checks both entry points share; `env` is dereferenced only after the ones that need no env.
+static int critic_check(const fe_env *env, const fe_critic_weights *c1, const fe_critic_weights *c2, int32_t H, const char *who) {
+    if (H != 32 && H != 64 && H != 128)
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the twin critic has no streamed or split kernel", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only (the reference's critic for A > 1 "
+                    "is one nn.LSTM(5A + A, H) over the whole env, not a per-(env, asset) pair network)", who, (int)env->p.A);
+    return FE_OK;
+}
+
+// Shared by fe_twin_q_forward and fe_twin_q_target: the split grid -- blockIdx.y = critic -- of fe_twin_q_kernel, each
+// half at most half the resident workgroups, looping over all tiles.
+static int launch_twin_q(fe_env *env, CriticArgs &cq, int64_t count, const char *who, void *stream) {
+    const int32_t H = cq.l.H;
+    Params p = env->p;
+    p.eval_env = -1;
+    const int SP = lstm_geometry(env, p, count, H, false, who);
+    if (SP == 0) return FE_ERR_ARG;
+    const size_t lds = lstm_lds_bytes(p.EB, p.A, H, SP);
+    const void *kern = H == 32 ? (const void *)fe_twin_q_kernel<1>
+                               : (H == 64 ? (const void *)fe_twin_q_kernel<2> : (const void *)fe_twin_q_kernel<4>);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "twin critic kernel: hipFuncSetAttribute / occupancy query");
+    int64_t half = (int64_t)env->cus * per_cu / 2;
+    if (half < 1) half = 1;
+    const int64_t grid = p.num_tiles < half ? p.num_tiles : half;
+    void *args[] = {&p, &cq};
+    return launched(who, hipLaunchKernel(kern, dim3((unsigned)grid, 2), dim3(kLstmBlock), args, lds, (hipStream_t)stream));
+}
+
+static void critic_args(CriticArgs &cq, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                        int32_t H, float *q1_out, float *q2_out) {
+    memset(&cq, 0, sizeof(cq));
+    cq.l.lr32 = logret_f32; cq.l.H = H; cq.l.out_act = 2; cq.l.K = 1; cq.l.forward_only = 1;
+    const fe_critic_weights *c[2] = {c1, c2};
+    float *q[2] = {q1_out, q2_out};
+    for (int i = 0; i < 2; ++i) cq.net[i] = CriticNet{c[i]->whh, c[i]->wx, c[i]->wout, c[i]->bout, q[i]};
+}
+
+int fe_twin_q_forward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                      int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                      float *q1_out, float *q2_out, void *stream) {
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !obs_src || !obs_pos || !actions ||
+        !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "fe_twin_q_forward: bad argument");
+    if (int rc = critic_check(env, c1, c2, H, "fe_twin_q_forward")) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    CriticArgs cq;
+    critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
+    cq.l.obs_src = const_cast<int64_t *>(obs_src); cq.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
+    cq.actions = actions;
+    return launch_twin_q(env, cq, count, "fe_twin_q_forward", stream);
+}
+
+int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                     int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
+                     int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
+                     float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
+                     float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
+        !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "fe_twin_q_target: bad argument");
+    if (log_probs && !alpha) return fail(FE_ERR_ARG, "fe_twin_q_target: log_probs (SAC) need alpha");
+    if (smooth_noise && log_probs)
+        return fail(FE_ERR_ARG, "fe_twin_q_target: smooth_noise (TD3) and log_probs (SAC) are exclusive");
+    if (int rc = critic_check(env, c1, c2, H, "fe_twin_q_target")) return rc;
+    const int64_t C = ring->capacity;
+    if (size < 1 || size > C || head < 0 || head >= C)
+        return fail(FE_ERR_ARG, "fe_twin_q_target: size %lld / head %lld do not describe a non-empty ring of %lld slots",
+                    (long long)size, (long long)head, (long long)C);
+    if (ring->num_assets != 1) return fail(FE_ERR_ARG, "fe_twin_q_target: the ring holds %d assets, the env 1", (int)ring->num_assets);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int64_t start = ((head - size) % C + C) % C;
+    CriticArgs cq;
+    critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
+    cq.indices = indices; cq.ring_src = ring->next_src; cq.ring_pos = ring->next_pos;
+    cq.ring_C = C; cq.start = start; cq.size = size;
+    cq.actions = next_actions; cq.smooth_noise = smooth_noise; cq.smooth_std = smooth_std; cq.smooth_clip = smooth_clip;
+    if (int rc = launch_twin_q(env, cq, count, "fe_twin_q_target: critics", stream)) return rc;
+    TwinTargetArgs t;
+    t.q1 = q1_out; t.q2 = q2_out; t.indices = indices; t.ring_rew = ring->rewards; t.ring_done = ring->dones;
+    t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
+    t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
+    t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
+    hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
+    return launched("fe_twin_q_target: epilogue");
 }
 
 }  // extern "C"

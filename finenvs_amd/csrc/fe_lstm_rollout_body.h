@@ -1,10 +1,12 @@
 // fe_lstm_rollout_body.h -- part of fe_env.hip (one translation unit; see the overview there): the body of the
-// register-resident LSTM rollout, included INSIDE fe_rollout_lstm_kernel (FE_LSTM_SAC_HEAD 0: tanh / clamp / value head)
-// and fe_rollout_sac_kernel (FE_LSTM_SAC_HEAD 1: the SAC actor's head), see fe_lstm_kernel.h.  Shared as source text
+// register-resident LSTM rollout, included INSIDE fe_rollout_lstm_kernel (FE_LSTM_SAC_HEAD 0: tanh / clamp / value head),
+// fe_rollout_sac_kernel (FE_LSTM_SAC_HEAD 1: the SAC actor's head), see fe_lstm_kernel.h, and fe_twin_q_kernel
+// (FE_LSTM_CRITIC_HEAD 1: a twin critic's value on given descriptors and actions, see fe_critic_kernels.h; it also
+// defines FE_LSTM_SAC_HEAD 0).  Shared as source text
 // rather than as an inlined device function: a function boundary around the body -- its arguments taken by reference or
 // by value -- changes how the kernel reads its argument block, and with it the register allocation of the LSTM kernels
 // (their VGPR / scratch figures in tools/resource_usage.py moved either way).  Expects p (Params), r (LstmArgs),
-// SINGLE, NT and, with the SAC head, hd (SacArgs).
+// SINGLE, NT and, with the SAC head, hd (SacArgs), with the critic head, cq (CriticArgs).
     using G = LstmGeom<NT>;
     constexpr int H = G::H, HP = G::HP, MPW = G::MPW, NSPLIT = G::NSPLIT, MAXNT = G::MAXNT, NG = H / 8;
     constexpr int JB = MPW == 1 ? 2 : 1;  // column tiles processed together
@@ -68,6 +70,11 @@
         const bool active = e < ebt;
         const int64_t n = n0 + e;
         const int64_t sl = n * A + a;
+#if FE_LSTM_CRITIC_HEAD
+        // (A = 1: pair e is env e) the critic has no accounting: the sleeve field shr holds the pair's action
+        if (active) critic_load_pair(cq, n, l.src + e, l.pos + e, l.shr + e);
+        (void)sl, (void)l_idx, (void)NA;
+#else
         SleeveReg st = rollout_load_state(p, active && !r.forward_only, n, sl);
         if (active) {
             const double pos0 = r.obs_pos[sl];
@@ -78,6 +85,7 @@
                 if (a == 0) r.traj_src[n] = r.obs_src[n];
             }
         }
+#endif
         __syncthreads();  // also covers the head's weights on the first tile
         const int pairs = ebt * A;
         const int ntiles = (pairs + 31) / 32;
@@ -93,7 +101,11 @@
                 const int ee = SINGLE ? qc : (int)fdiv((uint32_t)qc, p.div_A);
                 const int aa = SINGLE ? 0 : qc - ee * A;
                 xsrc[j] = r.lr32 + l.src[ee] + 4 * aa;
+#if FE_LSTM_CRITIC_HEAD
+                xh[j] = make_float4((float)l.pos[qc], 1.0f, l.shr[qc], 0.0f);  // slot 6: the action, the same in every row
+#else
                 xh[j] = make_float4((float)l.pos[qc], 1.0f, 0.0f, 0.0f);
+#endif
                 xc[j] = half == 0 ? *reinterpret_cast<const float4 *>(xsrc[j]) : xh[j];
 #pragma unroll
                 for (int i = 0; i < MPW; ++i)
@@ -257,6 +269,16 @@
                     if (r.actions_out) r.actions_out[o] = act;
                 }
             }
+#elif FE_LSTM_CRITIC_HEAD
+            // ---- the critic's value, Linear(H, 1) + Identity: the LSTM head's reduction with out_act 2 ----
+            if (active) {
+                const float *hl = s_h + (size_t)((W - 1) & 1) * G::SP * HP + (size_t)(e * A + a) * HP;
+                float o = *cq.net[blockIdx.y].bout;
+#pragma unroll 8
+                for (int u = 0; u < H; ++u) o = fmaf(s_wout[u], hl[u], o);
+                critic_store(cq, n, o);
+            }
+            (void)act;
 #else
             // ---- output layer: the pair's accounting lane reduces its last hidden state ----
             if (active) {
@@ -274,6 +296,7 @@
                 if (r.actions_out) r.actions_out[(int64_t)k * NA + sl] = act;
             }
 #endif
+#if !FE_LSTM_CRITIC_HEAD
             if (!r.forward_only) {  // (uniform)
                 account_keep<SINGLE>(p, l, l_idx, A, e, a, active, n, st, act, r.rew_out + (int64_t)k * p.N,
                                      r.done_out + (int64_t)k * p.N);
@@ -282,8 +305,10 @@
                     if (a == 0) r.traj_src[(int64_t)(k + 1) * p.N + n] = l.src[e];
                 }
             }
+#endif
             lds_barrier();  // the new observation's descriptors are complete; everyone is done with h_W (and z)
         }
+#if !FE_LSTM_CRITIC_HEAD
         if (!r.forward_only) {
             rollout_store_state(p, active, a, n, sl, st);  // state and descriptors go back to HBM once per launch
             if (active) {
@@ -291,5 +316,6 @@
                 if (a == 0) r.obs_src[n] = l.src[e];
             }
         }
+#endif
         __syncthreads();
     }
