@@ -13,7 +13,13 @@ actor in ``FusedSACRollout.forward`` and both target critics plus the Bellman co
 ``FusedTwinCritic.sac_targets`` (the next states are never rendered).  It draws the same indices and normals as the
 default path, so with the same seed both compute the same targets up to fp32 rounding.
 
+With ``--fused-critics`` the gradient half of the critics runs on the replayed descriptors too: the critic update is
+``FusedTwinCritic.critic_loss`` (both critics' forward and backward through time in HIP, nothing rendered) and the
+actor update takes ``min(q1, q2)`` from ``FusedTwinCritic.q`` on the sampled state descriptors, so ``dQ/da`` reaches the
+torch actor (which still runs on the rendered states) through the fused backward.
+
     python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
+                                       [--fused-critics]
 """
 import argparse
 import copy
@@ -40,7 +46,8 @@ def soft_update(target, source, rho):
 
 
 def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
-         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False):
+         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False,
+         fused_critics=False):
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
@@ -54,6 +61,7 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
     critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
     roll = FusedSACRollout(env, actor)  # re-packs the actor's weights at every run: updates are seen right away
     twin = FusedTwinCritic(env, critic_1t, critic_2t) if fused_targets else None  # re-packs at every call, too
+    twin_online = FusedTwinCritic(env, critic_1, critic_2) if fused_critics else None
     gen = torch.Generator(device=dev).manual_seed(seed)
     history = []
     for it in range(iterations):
@@ -71,20 +79,28 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
                 eps = torch.randn((batch, 1), device=dev)
                 y = twin.sac_targets(buffer, idx, roll, eps, gamma, actor.log_alpha, reward_scale=reward_scale)
             else:
-                b = buffer.get_mini_batch(batch)
+                idx = torch.randint(0, buffer.size(), (batch,), device=dev) if fused_critics else None
+                b = buffer.get_mini_batch(batch, indices=idx)
                 s, a, s2 = b["states"], b["actions"], b["next_states"]
                 r, d = b["rewards"] * reward_scale, b["dones"]
                 with torch.no_grad():  # compute_targets (SAC_agent.py:200-225)
                     a2, lp2 = actor.get_actions_and_log_probs(s2)
                     q2 = torch.min(critic_1t(s2, a2), critic_2t(s2, a2))
                     y = r + gamma * (1.0 - d) * (q2 - actor.log_alpha.exp() * lp2.mean(dim=1, keepdim=True))
-            critic_loss = F.mse_loss(critic_1(s, a), y) + F.mse_loss(critic_2(s, a), y)
+            if fused_critics:  # the ring's state descriptors and stored actions of the same transitions
+                critic_loss = twin_online.critic_loss(buffer, idx, y)
+            else:
+                critic_loss = F.mse_loss(critic_1(s, a), y) + F.mse_loss(critic_2(s, a), y)
             critic_opt.zero_grad()
             critic_loss.backward()
             critic_opt.step()
             a_new, lp = actor.get_actions_and_log_probs(s)  # SAC/actor.py:63-85
             mean_lp = lp.mean(dim=1, keepdim=True)
-            q = torch.min(critic_1(s, a_new), critic_2(s, a_new))
+            if fused_critics:
+                slots = buffer.physical(idx)
+                q = torch.min(*twin_online.q(buffer.state_src[slots], buffer.state_pos[slots], a_new))
+            else:
+                q = torch.min(critic_1(s, a_new), critic_2(s, a_new))
             actor_loss = -(q - actor.log_alpha.exp().detach() * mean_lp).mean()
             actor_opt.zero_grad()
             actor_loss.backward()
@@ -111,5 +127,7 @@ if __name__ == "__main__":
     ap.add_argument("--chunk", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--fused-targets", action="store_true")
+    ap.add_argument("--fused-critics", action="store_true")
     a = ap.parse_args()
-    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets)
+    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
+         fused_critics=a.fused_critics)

@@ -147,6 +147,20 @@ CRITIC_SIGNATURES = {
                                    C.c_float, C.c_float, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
 }
 
+
+# include/finenvs_amd_critic_grad.h: the twin critics' backward pass (finenvs_amd/critic.py; same library)
+class FeCriticGrads(C.Structure):
+    """struct fe_critic_grads of include/finenvs_amd_critic_grad.h."""
+
+    _fields_ = [("w_ih", _vp), ("w_hh", _vp), ("b_ih", _vp), ("b_hh", _vp), ("w_out", _vp), ("b_out", _vp)]
+
+
+_cg = C.POINTER(FeCriticGrads)
+CRITIC_GRAD_SIGNATURES = {
+    "fe_twin_q_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_twin_q_backward": (C.c_int, [_vp, _vp, _cw, _cw, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _cg, _cg, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -172,7 +186,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
             ) from exc
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
-                         **CRITIC_SIGNATURES}.items():
+                         **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -9,7 +9,9 @@ state.  Its submodule names are the reference's, so a reference ``state_dict`` l
 include/finenvs_amd_critic.h) and forms the Bellman targets of ``SACAgent.compute_targets`` (SAC_agent.py:200-227) and
 ``TD3Agent.compute_targets`` (TD3_agent.py:231-251) straight from the replay ring (``fe_twin_q_target``): the sampled
 next states are never rendered.  The actor half runs on the same descriptors in ``FusedSACRollout.forward`` /
-``FusedLSTMRollout.forward``.  Scope: one asset (the reference's multi-asset critic is ``nn.LSTM(5A + A, H)`` over the
+``FusedLSTMRollout.forward``.  The gradient half runs on descriptors too: ``FusedTwinCritic.q`` is the values as a
+differentiable function of the actions and both critics' parameters (C ABI ``fe_twin_q_backward``,
+include/finenvs_amd_critic_grad.h), and ``critic_loss`` the critics' MSE on replayed transitions.  Scope: one asset (the reference's multi-asset critic is ``nn.LSTM(5A + A, H)`` over the
 whole env, not a per-pair network) and H in {32, 64, 128}.
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 from .rollout import lstm_pack, lstm_row_order
@@ -88,6 +91,90 @@ def pack_critic_weights(critic: nn.Module) -> Dict[str, torch.Tensor]:
     }
 
 
+GRAD_KEYS = ("w_ih", "w_hh", "b_ih", "b_hh", "w_out", "b_out")  # fe_critic_grads' fields, in critic_parameters' order
+
+
+def critic_parameters(critic: nn.Module) -> Tuple[torch.Tensor, ...]:
+    """The six parameter tensors of a critic in ``GRAD_KEYS`` order: ``lstm.weight_ih_l0 (4H, 6)``, ``weight_hh_l0
+    (4H, H)``, ``bias_ih_l0``, ``bias_hh_l0`` (4H), ``last_layer[0].weight (1, H)`` and ``.bias (1)``."""
+    lstm, last = critic.lstm, critic.last_layer[0]
+    return lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, last.weight, last.bias
+
+
+def empty_packed_grads(H: int, device) -> Dict[str, torch.Tensor]:
+    """Buffers for one critic's gradients as fe_twin_q_backward writes them (include/finenvs_amd_critic_grad.h)."""
+    shapes = {"w_ih": (4 * H, 6), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,), "w_out": (H,), "b_out": (1,)}
+    return {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in GRAD_KEYS}
+
+
+def packed_grads_to_torch(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch.Tensor]:
+    """fe_twin_q_backward's gradients (rows of the 4H-row tensors in ``lstm_row_order``) in the layout and row order of
+    the critic's parameters (``critic_parameters``)."""
+    order = lstm_row_order(H).to(g["w_hh"].device)
+    inv = torch.empty_like(order)
+    inv[order] = torch.arange(4 * H, device=order.device)
+    return {"w_ih": g["w_ih"][inv], "w_hh": g["w_hh"][inv], "b_ih": g["b_ih"][inv], "b_hh": g["b_hh"][inv],
+            "w_out": g["w_out"].reshape(1, H), "b_out": g["b_out"].reshape(1)}
+
+
+def torch_grads_to_packed(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch.Tensor]:
+    """The inverse of ``packed_grads_to_torch``."""
+    order = lstm_row_order(H).to(g["w_hh"].device)
+    return {"w_ih": g["w_ih"][order], "w_hh": g["w_hh"][order], "b_ih": g["b_ih"][order], "b_hh": g["b_hh"][order],
+            "w_out": g["w_out"].reshape(H), "b_out": g["b_out"].reshape(1)}
+
+
+class _TwinQ(torch.autograd.Function):
+    """(q1, q2) of ``FusedTwinCritic`` as a differentiable function of the actions and the twelve parameters: the
+    forward is ``fe_twin_q_forward``, the backward ``fe_twin_q_backward`` (the same activations, recomputed)."""
+
+    @staticmethod
+    def forward(ctx, fused, src, pos, actions, *params):
+        q1, q2 = fused.forward(src, pos, actions.detach())
+        ctx.set_materialize_grads(False)  # an output nobody used gets None, not zeros: its critic does not run
+        ctx.fused, ctx.packed, ctx.action_shape = fused, fused._packed, actions.shape
+        ctx.save_for_backward(src, pos, actions.detach().reshape(-1).contiguous())
+        return q1, q2
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        fused = ctx.fused
+        src, pos, act = ctx.saved_tensors
+        env, H, B = fused.env, fused.H, int(src.numel())
+        need = ctx.needs_input_grad
+        need_a = need[3]
+        need_w = (any(need[4:10]), any(need[10:16]))
+        dq = [g if g is not None and (need_w[c] or need_a) else None for c, g in enumerate((g1, g2))]
+        out = [None] * 16
+        if dq[0] is None and dq[1] is None:
+            return tuple(out)
+        dev = env._dev
+        dq = [None if g is None else g.reshape(B).float().contiguous() for g in dq]
+        grads = [empty_packed_grads(H, dev) if dq[c] is not None and need_w[c] else None for c in range(2)]
+        da = torch.empty((B,), dtype=torch.float32, device=dev) if need_a else None
+        ws = torch.empty((int(env._lib.fe_twin_q_grad_workspace_floats(H, int(env.num_intervals), B)),),
+                         dtype=torch.float32, device=dev)
+        cw = [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
+              for x in ctx.packed]
+        cg = [None if g is None else _lib.FeCriticGrads(*(g[k].data_ptr() for k in GRAD_KEYS)) for g in grads]
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
+        _lib.check(env._lib.fe_twin_q_backward(
+            env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), H, src.data_ptr(), pos.data_ptr(),
+            act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
+            env._stream()), env._lib)
+        if need_a:
+            out[3] = da.reshape(ctx.action_shape)
+        for c in range(2):
+            if grads[c] is None:
+                continue
+            t = packed_grads_to_torch(grads[c], H)
+            for k, key in enumerate(GRAD_KEYS):
+                if need[4 + 6 * c + k]:
+                    out[4 + 6 * c + k] = t[key]
+        return tuple(out)
+
+
 class FusedTwinCritic:
     """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
 
@@ -146,6 +233,41 @@ class FusedTwinCritic:
         return q1, q2
 
     __call__ = forward
+
+    # ---------------------------------------------------------------- the gradient half
+    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """``forward`` as a differentiable function (C ABI ``fe_twin_q_backward``, include/finenvs_amd_critic_grad.h):
+        ``(q1, q2)`` (B, 1) float32, the same values bit for bit.  ``backward()`` accumulates into the ``.grad`` of both
+        critics' parameters and of ``actions`` (float32, (B, 1) or (B,)) as the torch modules would: the critic loss of
+        SAC/critic.py:30-45 / TD3/critic.py:31-46, ``dQ/da`` for TD3/actor.py ``compute_loss`` and the SAC actor loss.
+        A critic whose output gets no gradient does not run; one whose parameters are frozen has no weight
+        reduction."""
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        self._vector(actions, B, "actions")
+        params = critic_parameters(self.critic_1) + critic_parameters(self.critic_2)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError("the fused critic's gradient needs float32 parameters")
+        q1, q2 = _TwinQ.apply(self, src, pos, actions, *params)
+        return q1, q2
+
+    def critic_loss(self, buffer, indices: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+        """``MSE(q1, y) + MSE(q2, y)`` of both critics (SAC/critic.py:30-45 compute_loss, once per critic) on the
+        transitions ``indices`` (logical, (B,)) of ``buffer``: the ring's state descriptors and stored actions of those
+        transitions, nothing rendered.  ``targets`` (B, 1) float32, e.g. from ``sac_targets`` / ``td3_targets``.  An
+        index outside ``[0, size)`` makes its values NaN (as ``fe_twin_q_target``)."""
+        if indices is None:
+            raise ValueError("critic_loss needs the indices of the sampled transitions")
+        idx = self._indices(buffer, indices, None)
+        B = int(idx.numel())
+        y = self._vector(targets, B, "targets").reshape(B, 1)
+        slots = buffer.physical(idx)
+        q1, q2 = self.q(buffer.state_src[slots], buffer.state_pos[slots].reshape(B), buffer.actions[slots].reshape(B, 1))
+        valid = ((idx >= 0) & (idx < buffer.size())).reshape(B, 1)
+        nan = torch.full((), float("nan"), device=q1.device)
+        q1, q2 = torch.where(valid, q1, nan), torch.where(valid, q2, nan)
+        return F.mse_loss(q1, y) + F.mse_loss(q2, y)
 
     # ---------------------------------------------------------------- targets from the replay ring
     def _indices(self, buffer, indices, batch_size) -> torch.Tensor:

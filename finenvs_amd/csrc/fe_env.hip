@@ -25,7 +25,7 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, eleven files:
+// One translation unit, twelve files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
@@ -36,6 +36,7 @@
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
+//   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
 //                         six headers in include/
@@ -62,6 +63,7 @@
 #include "finenvs_amd_replay.h"
 #include "finenvs_amd_sac.h"
 #include "finenvs_amd_critic.h"
+#include "finenvs_amd_critic_grad.h"
 
 #include "fe_device_common.h"
 #include "fe_step_kernel.h"
@@ -71,6 +73,7 @@
 #include "fe_evo_kernels.h"
 #include "fe_replay_kernels.h"
 #include "fe_critic_kernels.h"
+#include "fe_critic_grad_kernels.h"
 
 namespace {
 
@@ -1451,6 +1454,90 @@ int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weigh
     t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
     hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
     return launched("fe_twin_q_target: epilogue");
+}
+
+// ---- include/finenvs_amd_critic_grad.h: the twin critics' backward pass ----
+// Workspace: [wt of each critic][partials of each critic][stash of each critic][da of each critic].
+int64_t fe_twin_q_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t groups = tiles < critic_grad_max_groups(H) ? tiles : critic_grad_max_groups(H);
+    return 2 * (critic_grad_wt_floats(H) + groups * (critic_grad_part_floats(H) + critic_grad_stash_floats(H, W))) +
+           2 * count;
+}
+
+static bool critic_grads_ok(const fe_critic_grads *g) {
+    return g && g->w_ih && g->w_hh && g->b_ih && g->b_hh && g->w_out && g->b_out;
+}
+
+int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                       int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                       const float *dq1, const float *dq2, float *workspace, const fe_critic_grads *grads1,
+                       const fe_critic_grads *grads2, float *d_actions, void *stream) {
+    static const char *who = "fe_twin_q_backward";
+    if (!env || !logret_f32 || !obs_src || !obs_pos || !actions || !workspace || count < 0 ||
+        (dq1 && (!critic_weights_ok(c1) || (grads1 && !critic_grads_ok(grads1)) || (!grads1 && !d_actions))) ||
+        (dq2 && (!critic_weights_ok(c2) || (grads2 && !critic_grads_ok(grads2)) || (!grads2 && !d_actions))))
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (H != 32 && H != 64 && H != 128)
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only", who, (int)env->p.A);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t max_groups = tiles < critic_grad_max_groups(H) ? tiles : critic_grad_max_groups(H);
+    CriticGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos; g.actions = actions;
+    g.count = count; g.num_tiles = tiles; g.W = W; g.d_actions = d_actions;
+    const fe_critic_weights *cw[2] = {c1, c2};
+    const fe_critic_grads *cg[2] = {grads1, grads2};
+    const float *dq[2] = {dq1, dq2};
+    float *wt = workspace, *part = wt + 2 * critic_grad_wt_floats(H);
+    float *stash = part + 2 * max_groups * critic_grad_part_floats(H);
+    float *da = stash + 2 * max_groups * critic_grad_stash_floats(H, W);
+    for (int i = 0; i < 2; ++i) {
+        if (!dq[i]) continue;
+        CriticGradNet &n = g.net[g.ncrit];
+        n.whh = cw[i]->whh; n.wx = cw[i]->wx; n.wout = cw[i]->wout; n.dq = dq[i];
+        n.wt = wt + g.ncrit * critic_grad_wt_floats(H);
+        n.part = part + g.ncrit * max_groups * critic_grad_part_floats(H);
+        n.stash = stash + g.ncrit * max_groups * critic_grad_stash_floats(H, W);
+        n.da = da + g.ncrit * count;
+        if (cg[i]) {
+            n.g_wih = cg[i]->w_ih; n.g_whh = cg[i]->w_hh; n.g_bih = cg[i]->b_ih; n.g_bhh = cg[i]->b_hh;
+            n.g_wout = cg[i]->w_out; n.g_bout = cg[i]->b_out;
+        }
+        ++g.ncrit;
+    }
+    if (g.ncrit == 0) {
+        if (!d_actions) return FE_OK;
+        return launched(who, hipMemsetAsync(d_actions, 0, (size_t)count * sizeof(float), (hipStream_t)stream));
+    }
+    hipLaunchKernelGGL(fe_critic_grad_pack_kernel, dim3(grid_for(critic_grad_wt_floats(H)), g.ncrit), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H, const_cast<float *>(g.net[0].wt), const_cast<float *>(g.net[1].wt));
+    if (int rc = launched("fe_twin_q_backward: weight transpose")) return rc;
+    const void *kern = H == 32 ? (const void *)fe_critic_grad_kernel<1>
+                               : (H == 64 ? (const void *)fe_critic_grad_kernel<2> : (const void *)fe_critic_grad_kernel<4>);
+    const size_t lds = critic_grad_lds_bytes(H);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kCriticGradBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "critic gradient kernel: hipFuncSetAttribute / occupancy query");
+    int64_t resident = (int64_t)env->cus * per_cu / g.ncrit;
+    if (resident < 1) resident = 1;
+    g.groups = max_groups < resident ? max_groups : resident;
+    void *args[] = {&g};
+    if (int rc = launched("fe_twin_q_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups, g.ncrit),
+                                                                          dim3(kCriticGradBlock), args, lds, (hipStream_t)stream)))
+        return rc;
+    const int64_t elems = 4LL * H * (H + 32) + H + 1;
+    const int64_t work = elems > count ? elems : count;
+    hipLaunchKernelGGL(fe_critic_grad_reduce_kernel, dim3(grid_for(work), g.ncrit + 1), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    return launched("fe_twin_q_backward: reduction");
 }
 
 }  // extern "C"
