@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the fused TimeSeriesEnv.step() hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5|1] [--repeats R] [--no-cpu] [--no-extra] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5|1] [--repeats R] [--full [--no-cpu] [--no-extra]] [--dump-outputs DIR]
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -17,14 +17,16 @@ rollout loop keeps the previous observation alive while the next is written).
 
 The timed region is EXACTLY K steps between two (barrier + synchronize) fences; it is repeated
 R times and the MEDIAN block is reported (min / max beside it), because one K-step block at
-64k envs is under a millisecond.  With N > 1 there are two legs per workload: steps with the
-asynchronous trajectory all-gather (the headline `value`; one whole gather per timed block) and steps without it.
+64k envs is under a millisecond.  With N > 1 the timed steps carry the asynchronous trajectory all-gather (one whole
+gather per timed block); --full adds a leg of steps without it.
 
-After the headline workload (BASELINE.json's "64k envs" configuration) the same process runs
-the larger BASELINE configs for a few steps each and reports them under "extra_configs" -- on
-one GPU configs 3 and 4 (the 1M-env north-star run), on N > 1 GPUs the per-GPU shard of
-config 5 (4M envs over 8 GPUs); at N = 1 also four fused-rollout legs ("fused_rollouts": K steps per launch
-with an in-kernel linear / MLP / LSTM (H = 128, 1024) policy; never part of `value`).  Prints ONE JSON line on rank 0.
+A plain run measures the headline workload (BASELINE.json's "64k envs" configuration) and nothing
+else.  With --full the same process goes on: the store ceiling on the headline's ring, the CPU
+baseline, live rocprofv3 counter passes, and the larger BASELINE configs for a few steps each under
+"extra_configs" -- on one GPU configs 3 and 4 (the 1M-env north-star run), on N > 1 GPUs the per-GPU shard of
+config 5 (4M envs over 8 GPUs); the strong-scaling reading; at N = 1 also four fused-rollout legs ("fused_rollouts": K steps per launch
+with an in-kernel linear / MLP / LSTM (H = 128, 1024) policy; never part of `value`); at N > 1 the no-gather and
+gather-only legs and the DeviceGuard check.  Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
 
@@ -781,28 +783,29 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
         if reuse_blocks is None:
             before_value = launched[0]
         legs["with_all_gather"], kern = reuse_blocks if reuse_blocks is not None else timed_blocks(R, capture=True)
-        fence()
-        gather[0] = False
-        traj.clear()
-        settle()
-        legs["no_all_gather"], _ = timed_blocks(R)
         head = legs["with_all_gather"]
-        # Gather-only leg: the all-gather of one filled chunk ALONE (issue + drain between fences, no env steps beside
-        # it), so that "with / without all-gather" above can be decomposed: an exposed gather shows up as
-        # with - without ~ gather_only, a hidden one as with ~ without.  SURVEY section 5 expects the direct
-        # (all-links) algorithm on the fully connected xGMI node; `bus_GBps` = inbound bytes per GPU / time.
-        fence()
-        traj.clear()
-        run_steps(T)  # a full chunk of real data
-        gather_only = []
-        for _ in range(max(R, 5)):
+        if args.full:
             fence()
-            t0 = time.perf_counter()
-            traj.mark_filled(T)  # the chunk counts as full again (same bytes; the data is not the point)
-            traj.all_gather_async()
-            traj.drain()
-            torch.cuda.synchronize()
-            gather_only.append(D.max_over_ranks(time.perf_counter() - t0))
+            gather[0] = False
+            traj.clear()
+            settle()
+            legs["no_all_gather"], _ = timed_blocks(R)
+            # Gather-only leg: the all-gather of one filled chunk ALONE (issue + drain between fences, no env steps beside
+            # it), so that "with / without all-gather" above can be decomposed: an exposed gather shows up as
+            # with - without ~ gather_only, a hidden one as with ~ without.  SURVEY section 5 expects the direct
+            # (all-links) algorithm on the fully connected xGMI node; `bus_GBps` = inbound bytes per GPU / time.
+            fence()
+            traj.clear()
+            run_steps(T)  # a full chunk of real data
+            gather_only = []
+            for _ in range(max(R, 5)):
+                fence()
+                t0 = time.perf_counter()
+                traj.mark_filled(T)  # the chunk counts as full again (same bytes; the data is not the point)
+                traj.all_gather_async()
+                traj.drain()
+                torch.cuda.synchronize()
+                gather_only.append(D.max_over_ranks(time.perf_counter() - t0))
         fence()
         traj.clear()
     else:
@@ -822,14 +825,14 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
     kern_ms = statistics.median(kern)
     form = train[0].form
 
-    # The practical store ceiling beside the roofline: torch's fill kernel (one aligned 4 KiB unit per workgroup, one store per
+    # The practical store ceiling beside the roofline (--full): torch's fill kernel (one aligned 4 KiB unit per workgroup, one store per
     # lane: the fastest way of writing HBM found on this part) over the SAME observation ring, in the same
     # train protocol as `kernel_ms` (back-to-back launches, alternating ring members, one HIP-event pair per train).  Pure stores:
     # it reads nothing and computes nothing, so it bounds what any kernel that has to produce these bytes can reach here.
     fill_ms = None
     try:
         ring = list(env._obs_ring)
-        if ring:
+        if args.full and ring:
             kf = max(4, min(k2, 60))
             fills = []
             for rep in range(4):
@@ -911,6 +914,10 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
             "packed_bytes_per_rank_per_chunk": traj._nbytes,
             "gathered_bytes_per_rank_per_chunk": traj._nbytes * world,
             "value_with_all_gather": res["repeats"]["with_all_gather"]["value_median"],
+            "rccl": D.rccl_report(),
+        }
+    if D.multi and args.full:
+        res["multi_gpu"].update({
             "value_no_all_gather": res["repeats"]["no_all_gather"]["value_median"],
             # decomposition: one chunk's all-gather alone, and what it costs per step if fully exposed
             "gather_only_ms": statistics.median(gather_only) * 1e3,
@@ -918,8 +925,7 @@ def run_workload(config: int, args, D: Dist, steps: int, warmup: int, repeats: i
             "gather_only_ms_per_step_if_exposed": statistics.median(gather_only) * 1e3 / T,
             "gather_only_inbound_GBps_per_gpu": traj._nbytes * (D.dist.get_world_size() - 1) / statistics.median(gather_only) / 1e9,
             "exposed_ms_per_step": res["repeats"]["with_all_gather"]["ms_per_step_median"] - res["repeats"]["no_all_gather"]["ms_per_step_median"],
-            "rccl": D.rccl_report(),
-        }
+        })
         # DESIGN.md section 7's prediction evaluated for THIS world size and workload (written in round 4, before RCCL had
         # ever run with more than one rank here): what the gather needs from xGMI and whether a block can hide it
         ws = D.dist.get_world_size()
@@ -1243,15 +1249,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--repeats", type=int, default=0, help="timed K-step blocks (0 = auto: ~0.15 s of timed work, 5..40)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs and the extra legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything beside it: store ceiling, cpu_baseline, live counter passes, "
+                         "extra_configs, strong scaling, the extra legs (N > 1: the no-gather and gather-only legs, the DeviceGuard check)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra_configs and the extra legs")
     ap.add_argument("--redraw", default="torch", choices=["torch", "device"],
                     help="the evaluation env's day redraw: 'torch' = the reference's RNG stream and per-step host read (class default, "
-                         "pinned by the reference's fixtures); 'device' = in-kernel Philox (timed as the `device_redraw` leg by default)")
+                         "pinned by the reference's fixtures); 'device' = in-kernel Philox (timed as the `device_redraw` leg by --full)")
     ap.add_argument("--obs-f32", action="store_true", help="f32 observations (NOT the reference dtype; extra mode)")
     ap.add_argument("--graph", action="store_true", help="replay the 8-action ring as one hipGraph per 8 steps")
     ap.add_argument("--no-audition", action="store_true", help="take the observation ring as allocated (no placement audition)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 child passes")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without measuring roofline.traffic in rocprofv3 child passes")
     ap.add_argument("--detail", default=None, metavar="PATH", help="also write the full record (everything stderr's [bench-detail] lines carry) as one JSON document")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the headline's last timed step returned (observation, rewards, dones) as DIR/<name>.npy (OutputDump)")
@@ -1285,9 +1294,9 @@ def main():
     # device's: a fixed seed makes the inputs of every workload the same from run to run (and on every rank)
     torch.manual_seed(BENCH_SEED)
 
-    # ---- 1. the headline (+ cpu_baseline on the plain N = 1 run): nothing else has touched the GPU yet
-    head = run_workload(args.config, args, D, args.steps, args.warmup, args.repeats, with_cpu=(not args.no_cpu and not D.multi),
-                        dump_dir=args.dump_outputs)
+    # ---- 1. the headline (+ cpu_baseline on a --full N = 1 run): nothing else has touched the GPU yet
+    head = run_workload(args.config, args, D, args.steps, args.warmup, args.repeats,
+                        with_cpu=(args.full and not args.no_cpu and not D.multi), dump_dir=args.dump_outputs)
     if "error" in head:
         sys.exit(f"bench.py: headline workload failed: {head['error']}")
     detail = {"n_gpus": D.world, "steps": args.steps, "dtype": "f32" if args.obs_f32 else "f64", "eval_redraw": args.redraw,
@@ -1296,7 +1305,8 @@ def main():
     emit_detail("headline", head)
     note(f"headline: {head['value']:.4g} env-steps/s, kernel {head['roofline']['kernel_ms'] * 1e3:.2f} us, frac {head['roofline']['frac']:.3f}")
 
-    # ---- 2. from here on a watchdog owns the line: whatever hangs below costs its own leg, not `value` / roofline / cpu_baseline
+    # ---- 2. from here on a watchdog owns the line: whatever hangs below costs its own leg, not `value` / roofline / cpu_baseline.
+    # A plain run goes straight to the teardown; --full measures everything else first.
     guard.arm(WATCHDOG_S)
 
     def leg(name):
@@ -1305,7 +1315,7 @@ def main():
 
     def measure_traffic(res, config):
         """roofline.traffic measured live (the workload's env is gone by now: the children have the card to themselves)."""
-        if D.multi or args.no_pmc or args.graph or "error" in res:
+        if not args.full or D.multi or args.no_pmc or args.graph or "error" in res:
             return
         leg(f"pmc_traffic_config{config}")
         # the workload's tensors died with run_workload's frame, AFTER its own empty_cache(): without this the caching allocator of
@@ -1320,8 +1330,8 @@ def main():
             note(f"live PMC pass of config {config} failed: {src}")
 
     measure_traffic(head, args.config)
-    want_extra = not args.no_extra and not args.graph and os.environ.get("FE_BENCH_NO_EXTRA") != "1"
-    if os.environ.get("FE_BENCH_HANG_LEG") == "1":  # rehearsal of the watchdog (tests only): a leg that never returns
+    want_extra = args.full and not args.no_extra and not args.graph and os.environ.get("FE_BENCH_NO_EXTRA") != "1"
+    if args.full and os.environ.get("FE_BENCH_HANG_LEG") == "1":  # rehearsal of the watchdog (tests only): a leg that never returns
         leg("rehearsal_hang")
         time.sleep(1e6)
     if want_extra:
@@ -1342,7 +1352,7 @@ def main():
 
     # the strong-scaling reading of the metric (64k envs IN TOTAL over the world) beside the weak one; at N = 1 also the
     # per-GPU shard of a 2 / 4 / 8-GPU world emulated on this GPU (no collectives): the measured basis of DESIGN.md section 7
-    if not args.no_extra and not args.graph and not args.obs_f32 and args.config == 2:
+    if args.full and not args.no_extra and not args.graph and not args.obs_f32 and args.config == 2:
         sys.path.insert(0, os.path.join(REPO, "tools"))
         import bench_legs as L
 

@@ -46,7 +46,7 @@ def _run(args, env=None, timeout=900, detail=None, launcher=()):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
-    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extra", "--no-pmc"], {"FE_CPU_THREADS": "4"}, 600, tmp_path / "d.json")
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extra", "--no-pmc"], {"FE_CPU_THREADS": "4"}, 600, tmp_path / "d.json")
     d = _one_json_line(out)
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["higher_is_better"] is True
     assert d["scaling"] == "weak" and d["vs_baseline"] is None and d["dtype"] == "f64" and d["data"] == "synthetic"
@@ -80,6 +80,41 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     assert lay["repeats"] >= 3 and lay["loop_launches_per_block"] == 20 and lay["train_launches"] >= 40
     assert h["as_allocated"]["blocks"] >= 3 and h["obs_ring_audition"]["candidates"] <= 12
     assert "[bench-detail] {\"headline\"" in out.stderr
+
+
+def test_plain_run_measures_the_headline_and_nothing_else(tmp_path):
+    """The driver's plain command (`--gpus 1 --steps 20 --warmup 5`, no `--full`): the headline's own protocol -- settle steps,
+    as-allocated blocks and the ring audition, a kernel train after every timed block -- and nothing after it: no cpu_baseline,
+    no live counter passes, no store ceiling, no extra_configs, legs or strong-scaling reading."""
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=600, detail=tmp_path / "d.json")
+    d = _one_json_line(out)
+    assert d["metric"] == "env-steps/sec" and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["config"]["workload"] == "64k envs, 1 asset, window=64"
+    assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert d["config"]["untimed_steps_before_value"] >= d["config"]["settle_steps"] + d["warmup"] and d["as_allocated"]["value"] > 0
+    r = d["roofline"]
+    assert r["kernel_ms"] <= d["ms_per_step"] * 1.01 and 0.3 < r["frac"] < 1.0 and r["kernel"] == "fe_env_kernel<double, 2, true, false, 2>"
+    assert d["cpu_baseline"] is None and d["extra_configs"] == [] and d["legs"] == [] and "strong_scaling" not in d and "unfinished" not in d
+    assert not r["traffic_source"].startswith("measured in this run") and "fill_GBps" not in r
+    full = json.load(open(tmp_path / "d.json"))
+    assert full["headline"]["value"] == d["value"] and full["headline"]["roofline"]["fill_ms"] is None and "legs_detail" not in full
+    assert "pmc_traffic" not in out.stderr
+
+
+def test_plain_run_over_rccl_with_one_rank_times_the_all_gather_steps_only(tmp_path):
+    """bench.py's N > 1 path without `--full` (FE_BENCH_FORCE_DIST=1: one RCCL rank): `value` is the steps with the trajectory
+    all-gather; the no-gather and gather-only legs, the config-5 shard, the strong-scaling reading and the DeviceGuard check are
+    --full's."""
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"],
+               {"FE_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29549"}, 600, tmp_path / "d.json")
+    d = _one_json_line(out)
+    m = d["multi_gpu"]
+    assert m["ranks_seen"] == 1 and m["collective_backend"] == "nccl" and m["kernel_form_by_rank"] == [2]
+    assert abs(d["value"] - m["with_all_gather"]) / d["value"] < 1e-4
+    assert m["no_all_gather"] is None and m["gather_only_ms"] is None and m["device_guard"] is None and "strong" not in m
+    assert d["cpu_baseline"] is None and d["extra_configs"] == []
+    full = json.load(open(tmp_path / "d.json"))
+    assert set(full["headline"]["repeats"]) == {"with_all_gather"} and full["strong_scaling"] is None
 
 
 def test_dump_outputs_is_step_k_of_the_timed_path_and_repeats_across_runs(tmp_path):
@@ -124,12 +159,12 @@ def test_dump_outputs_is_step_k_of_the_timed_path_and_repeats_across_runs(tmp_pa
 
 
 def test_default_driver_command_every_leg_kernel_below_step_and_both_scaling_readings(tmp_path):
-    """The driver's N = 1 command in full (`--steps 20 --warmup 5`, live counter passes included): the line is small and strict;
+    """The driver's N = 1 command with `--full` (`--steps 20 --warmup 5 --full`, live counter passes included): the line is small and strict;
     for the headline AND every extra_configs leg the kernel interval is at most the wall step (1 % slack) and `roofline.traffic`
     was MEASURED IN THIS RUN (the config-4 / 5 children used to die); the build's own redraw contract is a leg
     timed with the same protocol; the strong-scaling reading (64k envs in total) sits beside the weak one, with the per-GPU shard
     of a 2 / 4 / 8-GPU world measured on this GPU."""
-    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu"], {"FE_CPU_THREADS": "4"}, 1100, tmp_path / "d.json")
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu"], {"FE_CPU_THREADS": "4"}, 1100, tmp_path / "d.json")
     d = _one_json_line(out)
     assert d["config"]["eval_redraw"] == "torch" and d["scaling"] == "weak" and "unfinished" not in d and "dropped_for_size" not in d
     assert [e["config"] for e in d["extra_configs"]] == [3, 4, 5]
@@ -171,7 +206,7 @@ def test_a_hung_leg_at_one_gpu_still_leaves_value_roofline_and_cpu_baseline():
     """at N = 1 the headline is measured first but printed last.  A leg that never returns (rehearsed with a
     sleep and a 5 s watchdog) must cost its own entry only: the line carries value / roofline / cpu_baseline, names the leg in
     `unfinished`, and the process ends with the watchdog's exit code (a hang is not a success)."""
-    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-pmc"], {"FE_CPU_THREADS": "4", "FE_BENCH_WATCHDOG_S": "5", "FE_BENCH_HANG_LEG": "1"}, 600)
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-pmc"], {"FE_CPU_THREADS": "4", "FE_BENCH_WATCHDOG_S": "5", "FE_BENCH_HANG_LEG": "1"}, 600)
     d = _one_json_line(out, rc=3)
     assert d["value"] > 0 and 0.3 < d["roofline"]["frac"] < 1.0 and d["cpu_baseline"]["value"] > 0
     assert d["unfinished"] == ["rehearsal_hang"] and d["extra_configs"] == [] and d["legs"] == []
@@ -204,7 +239,7 @@ def test_bench_n_gt_1_code_path_over_rccl_with_one_rank(tmp_path):
     rank shard -- with the one rank a one-GPU box allows (FE_BENCH_FORCE_DIST=1: a rehearsal knob the driver never sets).
     The first execution with more than one RCCL rank happens on the driver's 8-GPU node; everything but the transport is
     exercised here."""
-    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-pmc"],
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-pmc"],
                {"FE_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29537"}, 900, tmp_path / "d.json")
     d = _one_json_line(out)
     full = json.load(open(tmp_path / "d.json"))
@@ -234,7 +269,7 @@ def test_watchdog_prints_the_line_if_the_new_multi_gpu_legs_hang():
     If they hang there (a collective that never completes), every rank gives up after WATCHDOG_S, rank 0 still prints the
     line with the headline, and every rank leaves with exit code 3 -- a hang is reported as a failure, with its record
      -- rehearsed here with a leg that sleeps forever and a 5 s watchdog (RCCL world 1)."""
-    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-pmc"],
+    out = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-pmc"],
                {"FE_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29545", "FE_BENCH_NO_EXTRA": "1",
                 "FE_BENCH_WATCHDOG_S": "5", "FE_BENCH_HANG_STRONG": "1"}, 600)
     d = _one_json_line(out, rc=3)
@@ -250,7 +285,7 @@ def test_bench_two_ranks_through_torch_distributed_run(tmp_path):
     the last rank), the collective legs with two real ranks, max-over-ranks timing, that only rank 0 prints, and that the N > 1
     line obeys the size cap and carries the multi_gpu keys.  The config-5 leg is skipped here: two ranks' shards (2 x 154 GB)
     do not fit one card."""
-    out = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-pmc"],
+    out = _run(["--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-pmc"],
                {"FE_BENCH_SINGLE_DEVICE": "1", "FE_BENCH_BACKEND": "gloo", "FE_BENCH_NO_EXTRA": "1"}, 900, tmp_path / "d.json",
                launcher=("-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541"))
     d = _one_json_line(out)

@@ -151,7 +151,7 @@ def test_bench_helpers_and_cli_parse_without_a_gpu():
     # the audition and the settle phase are bounded
     assert bench.AUDITION_EXTRA <= 10 and bench.AUDITION_BUDGET <= 64 << 30 and 5.0 <= bench.SETTLE_MS <= 50.0
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout
+    assert out.returncode == 0 and "--gpus" in out.stdout and "--steps" in out.stdout and "--warmup" in out.stdout and "--full" in out.stdout
 
 
 def test_bench_never_nests_a_profiler(monkeypatch):
