@@ -29,7 +29,10 @@ constexpr int kMultiAssetWaves = 6;
 //     ring larger than itself.  nt on top of sc1 keeps the stream out of it: 64k envs x W64 f64 (ring 336 MB) 29.73 ->
 //     28.93 and 28.84 -> 28.21 us on two boxes; with f32 observations (ring 168 MB, fits) the same bits cost +8.9 %, and
 //     at 256k x 30 assets sc1 | nt instead of nt is +0.5 % (profiles/r04_microbench/ab_store_aux.txt).  The host decides per
-//     env (fe_env.hip: Params::obs_stream = one observation buffer >= 128 MiB, i.e. two of them overflow the cache).
+//     env (fe_env.hip: Params::obs_stream = one observation buffer >= 128 MiB, i.e. two of them overflow the cache) and then
+//     per LAUNCH (fe_store_policy.h): the env keeps ONE resident buffer whose launches store plain sc1 -- the streamed
+//     members' nt stores leave its lines in the cache: 27.5 us for the resident member, 28.1 for the streamed one of a
+//     ring of two (profiles/launch_head/ab.txt).
 constexpr int kStoreAuxSingle = 16;
 constexpr int kStoreAuxSingleStream = 16 | 2;
 constexpr int kStoreAuxMulti = 2;
@@ -128,7 +131,7 @@ struct Params {
     int32_t W, A, EB;
     int32_t evaluate, redraw_mode;
     uint32_t env_elems;  // W * 5 * A, observation elements per env
-    int32_t obs_stream;  // single-asset envs: 1 = the observation ring is larger than the Infinity Cache (stores sc1 | nt)
+    int32_t obs_stream;  // single-asset envs: 1 = this launch streams its observation past the Infinity Cache (stores sc1 | nt; fe_store_policy.h)
     FastDiv div_WA;  // by tuples per env (W * A)
     FastDiv div_A;
     float scale32, ms32, c32, imr32, S32;

@@ -25,8 +25,9 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, twelve files:
+// One translation unit, thirteen files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
+//   fe_store_policy.h     host only: which launches of a large single-asset env stream past the Infinity Cache
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
@@ -66,6 +67,7 @@
 #include "finenvs_amd_critic_grad.h"
 
 #include "fe_device_common.h"
+#include "fe_store_policy.h"
 #include "fe_step_kernel.h"
 #include "fe_rollout_kernels.h"
 #include "fe_lstm_kernel.h"
@@ -131,9 +133,10 @@ struct fe_env {
     size_t lds;
     size_t lds_promoted;  // dynamic LDS of the kernel fe_env_step_promoted dispatches to (== lds unless it takes the tile loop at A = 1)
     bool promoted_used;   // sticky: fe_env_step_promoted has been called (fe_env_launch_info then describes that kernel)
-    // the observation buffer of the previous step launch: the store policy is decided per launch from how the buffers are
-    // actually used (launch_env).  Relaxed: a stale value costs one launch the other policy, never correctness.
-    mutable std::atomic<const void *> last_obs{nullptr};
+    // the observation buffer that may live in the Infinity Cache: the store policy is decided per launch from how the
+    // buffers are actually used (launch_env, fe_store_policy.h).  Relaxed atomics: a stale value costs one launch the other
+    // policy, never correctness.
+    mutable FeObsResidency obs_residency;
     bool bound;
     int cus;              // compute units of that device
     int tile_override, grid_override, rollout_tile_override;  // fe_env_set_launch (tuning), 0 = automatic
@@ -335,13 +338,12 @@ static int launch_env(const fe_env *env, const float *actions, void *obs, double
     }
     if (!RESET_ONLY) {
         // Store policy of a large single-asset observation (Params::obs_stream, fe_device_common.h): sc1 | nt keeps the
-        // stream out of the 256 MiB Infinity Cache, which pays when the caller ALTERNATES over buffers that together
-        // overflow it (a ring of two, fresh tensors per call) -- but a caller that rewrites ONE buffer of 128 - 256 MiB
-        // (obs_buffers=1, a C host with one d_obs) is absorbed by the cache and runs 3 % faster with plain sc1
-        // (profiles/r04_microbench/ring_alternation.txt: 27.5 vs 28.4 us).  So: stream unless this launch writes the very
-        // buffer the previous one wrote.
-        const void *prev = env->last_obs.exchange(obs, std::memory_order_relaxed);
-        if (p.obs_stream && prev == obs && (size_t)p.N * p.env_elems * (f32 ? 4 : 8) <= (256ull << 20)) p.obs_stream = 0;
+        // stream out of the 256 MiB Infinity Cache, which pays when the caller goes round buffers that together overflow
+        // it (a ring of two, fresh tensors per call) -- but ONE buffer of 128 - 256 MiB that is rewritten again and again
+        // is absorbed by the cache and runs 3 % faster with plain sc1 (profiles/r04_microbench/ring_alternation.txt: 27.5
+        // vs 28.4 us), also while the other ring members stream past it (profiles/launch_head/ab.txt).  So the env keeps
+        // one resident buffer: launches that write it store plain, all others stream (fe_obs_store_policy).
+        if (p.obs_stream) p.obs_stream = fe_obs_store_policy(env->obs_residency, obs, (uint64_t)p.N * p.env_elems * (f32 ? 4 : 8));
     }
     return launched(RESET_ONLY ? "fe_env_reset_obs" : "fe_env_step", hipLaunchKernel(kern, dim3(env->grid), dim3(kBlock), args, lds, st));
 }

@@ -6,6 +6,7 @@
 path from finenvs_amd/csrc/variants/); "=tile,grid" overrides the launch geometry (0 = automatic).
 Every arm first replays 24 steps and must equal the product bit for bit (observation, rewards, dones, state);
 then R rounds of K back-to-back launches per arm, arms interleaved, one HIP-event pair per block.
+AB_K=<launches per block> overrides K (longer trains: a host hiccup weighs less on a block).
 """
 import os
 import statistics
@@ -56,7 +57,7 @@ def replay(env, steps=24):
 
 BIG = obs_bytes * nbuf > 100e9  # only one env of this size fits at a time: arms run one after the other
 ref = None if BIG else replay(make("product"))  # (BIG: the first arm's own replay is the reference -- list "product" first)
-K = 100 if obs_bytes < 1e9 else 10
+K = int(os.environ.get("AB_K", 100 if obs_bytes < 1e9 else 10))
 R = 15 if obs_bytes < 1e9 else 5
 stream = torch.cuda.current_stream().cuda_stream
 times = {a: [] for a in arms}

@@ -5,6 +5,8 @@ kernel name: the phase marker in the trace):  A only | B only | A,B alternating 
 
     rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 tools/ring_alternation.py [config]
     python tools/ring_alternation.py --digest OUT      (prints per phase: average duration by position in the pattern)
+
+RING_ALT_LIB=<name> runs an experiment build (finenvs_amd.csrc.build.build_variant) instead of the product library.
 """
 import csv
 import glob
@@ -50,7 +52,10 @@ def main():
     cfg = int(sys.argv[1]) if len(sys.argv) > 1 else 2
     name, N, A, W = CONFIGS[cfg]
     prices, day_id, _ = make_series(A)
-    env = finenvs_amd.TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=W, num_envs=N, redraw="device", seed=1234, obs_buffers=3)
+    variant = os.environ.get("RING_ALT_LIB")
+    native = _lib.load(os.path.join(os.path.dirname(_lib.LIB_PATH), "variants", f"libfinenvs_amd.{variant}.so")) if variant else None
+    env = finenvs_amd.TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=W, num_envs=N, redraw="device", seed=1234, obs_buffers=3,
+                                    _native=native)
     g = torch.Generator(device="cuda:0").manual_seed(7)
     actions = [(torch.rand((N, A), generator=g, device="cuda:0") * 2 - 1).float() for _ in range(8)]
     stream = torch.cuda.current_stream().cuda_stream
