@@ -18,8 +18,14 @@ With ``--fused-critics`` the gradient half of the critics runs on the replayed d
 actor update takes ``min(q1, q2)`` from ``FusedTwinCritic.q`` on the sampled state descriptors, so ``dQ/da`` reaches the
 torch actor (which still runs on the rendered states) through the fused backward.
 
+With ``--fused-actor`` the actor's own update runs on the replayed state descriptors as well: ``FusedSACRollout.sample``
+gives the actions and log-probabilities with a HIP backward through the head and the recurrence, with the normals drawn
+where ``rsample`` drew them.  ``q`` comes from ``FusedTwinCritic.q`` with ``--fused-critics`` (``dQ/da`` then goes from one
+fused backward into the other) and from the torch critics on the rendered states otherwise.  With all three flags a
+training step renders no observation at all: ``get_mini_batch`` is not called.
+
     python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
-                                       [--fused-critics]
+                                       [--fused-critics] [--fused-actor]
 """
 import argparse
 import copy
@@ -47,7 +53,7 @@ def soft_update(target, source, rho):
 
 def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
          days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False,
-         fused_critics=False):
+         fused_critics=False, fused_actor=False):
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
@@ -63,6 +69,7 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
     twin = FusedTwinCritic(env, critic_1t, critic_2t) if fused_targets else None  # re-packs at every call, too
     twin_online = FusedTwinCritic(env, critic_1, critic_2) if fused_critics else None
     gen = torch.Generator(device=dev).manual_seed(seed)
+    render = not (fused_critics and fused_actor)  # somebody still reads the rendered states
     history = []
     for it in range(iterations):
         traj = TrajectoryBuffer(chunk, N, A, device=dev, states=True)
@@ -74,12 +81,13 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
         for _ in range(updates_per_chunk):
             if fused_targets:  # the same draws as below: get_mini_batch's indices, then rsample's normals
                 idx = torch.randint(0, buffer.size(), (batch,), device=dev)
-                b = buffer.get_mini_batch(batch, indices=idx)
-                s, a = b["states"], b["actions"]
+                if render:
+                    b = buffer.get_mini_batch(batch, indices=idx)
+                    s, a = b["states"], b["actions"]
                 eps = torch.randn((batch, 1), device=dev)
                 y = twin.sac_targets(buffer, idx, roll, eps, gamma, actor.log_alpha, reward_scale=reward_scale)
             else:
-                idx = torch.randint(0, buffer.size(), (batch,), device=dev) if fused_critics else None
+                idx = torch.randint(0, buffer.size(), (batch,), device=dev) if fused_critics or fused_actor else None
                 b = buffer.get_mini_batch(batch, indices=idx)
                 s, a, s2 = b["states"], b["actions"], b["next_states"]
                 r, d = b["rewards"] * reward_scale, b["dones"]
@@ -94,10 +102,14 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
             critic_opt.zero_grad()
             critic_loss.backward()
             critic_opt.step()
-            a_new, lp = actor.get_actions_and_log_probs(s)  # SAC/actor.py:63-85
+            if fused_critics or fused_actor:
+                slots = buffer.physical(idx)
+            if fused_actor:  # SAC/actor.py:63-85 on the descriptors, the normals drawn where rsample draws them
+                a_new, lp = roll.sample(buffer.state_src[slots], buffer.state_pos[slots], torch.randn((batch, 1), device=dev))
+            else:
+                a_new, lp = actor.get_actions_and_log_probs(s)  # SAC/actor.py:63-85
             mean_lp = lp.mean(dim=1, keepdim=True)
             if fused_critics:
-                slots = buffer.physical(idx)
                 q = torch.min(*twin_online.q(buffer.state_src[slots], buffer.state_pos[slots], a_new))
             else:
                 q = torch.min(critic_1(s, a_new), critic_2(s, a_new))
@@ -128,6 +140,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--fused-targets", action="store_true")
     ap.add_argument("--fused-critics", action="store_true")
+    ap.add_argument("--fused-actor", action="store_true")
     a = ap.parse_args()
     main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
-         fused_critics=a.fused_critics)
+         fused_critics=a.fused_critics, fused_actor=a.fused_actor)

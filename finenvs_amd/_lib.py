@@ -161,6 +161,21 @@ CRITIC_GRAD_SIGNATURES = {
     "fe_twin_q_backward": (C.c_int, [_vp, _vp, _cw, _cw, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _cg, _cg, _vp, _vp]),
 }
 
+
+# include/finenvs_amd_sac_grad.h: the SAC actor's backward pass (finenvs_amd/sac.py; same library)
+class FeSacGrads(C.Structure):
+    """struct fe_sac_grads of include/finenvs_amd_sac_grad.h."""
+
+    _fields_ = [("w_ih", _vp), ("w_hh", _vp), ("b_ih", _vp), ("b_hh", _vp), ("w_l", _vp), ("b_l", _vp), ("w_mu", _vp),
+                ("b_mu", _vp), ("w_std", _vp), ("b_std", _vp)]
+
+
+SAC_GRAD_SIGNATURES = {
+    "fe_sac_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_sac_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, C.c_float, _i32, _vp, _vp, _i64, _vp,
+                                  _vp, _vp, _vp, _vp, _vp, C.POINTER(FeSacGrads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -186,7 +201,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
             ) from exc
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
-                         **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES}.items():
+                         **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -25,7 +25,7 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, thirteen files:
+// One translation unit, fourteen files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_store_policy.h     host only: which launches of a large single-asset env stream past the Infinity Cache
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
@@ -38,9 +38,10 @@
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
+//   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
-//                         six headers in include/
+//                         headers in include/
 //
 // Arithmetic contract: every (float)/(double) cast is a rounding point of the
 // reference's mixed f32/f64 tensor arithmetic; this file
@@ -65,6 +66,7 @@
 #include "finenvs_amd_sac.h"
 #include "finenvs_amd_critic.h"
 #include "finenvs_amd_critic_grad.h"
+#include "finenvs_amd_sac_grad.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -76,6 +78,7 @@
 #include "fe_replay_kernels.h"
 #include "fe_critic_kernels.h"
 #include "fe_critic_grad_kernels.h"
+#include "fe_sac_grad_kernels.h"
 
 namespace {
 
@@ -1540,6 +1543,72 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
     hipLaunchKernelGGL(fe_critic_grad_reduce_kernel, dim3(grid_for(work), g.ncrit + 1), dim3(kBlock), 0, (hipStream_t)stream,
                        g, H);
     return launched("fe_twin_q_backward: reduction");
+}
+
+// ---- include/finenvs_amd_sac_grad.h: the SAC actor's backward pass ----
+// Workspace: [W_hh^T | W_l^T][partials of every workgroup][stash of every workgroup].
+int64_t fe_sac_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t groups = tiles < sac_grad_max_groups(H) ? tiles : sac_grad_max_groups(H);
+    return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + sac_grad_stash_floats(H, W));
+}
+
+int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                    const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H,
+                    const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                    const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                    float *workspace, const fe_sac_grads *grads, void *stream) {
+    static const char *who = "fe_sac_backward";
+    (void)bmu;  // the gradient does not depend on it
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0 || !noise ||
+        !actions || !stds || (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih || !grads->w_hh ||
+        !grads->b_ih || !grads->b_hh || !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu || !grads->w_std ||
+        !grads->b_std)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (H != 32 && H != 64 && H != 128)
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused actor gradient runs A = 1 only (its consumer, the "
+                    "fused twin critic, does)", who, (int)env->p.A);
+    if (count == 0) return FE_OK;
+    const size_t lds = sac_grad_lds_bytes(H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t max_groups = tiles < sac_grad_max_groups(H) ? tiles : sac_grad_max_groups(H);
+    SacGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
+    g.whh = whh; g.wx = wx; g.wl = wl; g.bl = bl; g.wmu = wmu; g.wstd = wstd; g.bstd = bstd;
+    g.noise = noise; g.actions = actions; g.stds = stds; g.d_actions = d_actions; g.d_log_probs = d_log_probs;
+    g.wt = workspace;
+    g.part = g.wt + sac_grad_wt_floats(H);
+    g.stash = g.part + max_groups * sac_grad_part_floats(H);
+    g.count = count; g.num_tiles = tiles; g.W = W;
+    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wl = grads->w_l;
+    g.g_bl = grads->b_l; g.g_wmu = grads->w_mu; g.g_bmu = grads->b_mu; g.g_wstd = grads->w_std; g.g_bstd = grads->b_std;
+    hipLaunchKernelGGL(fe_sac_grad_pack_kernel, dim3(grid_for(sac_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    if (int rc = launched("fe_sac_backward: weight transpose")) return rc;
+    const void *kern = H == 32 ? (const void *)fe_sac_grad_kernel<1>
+                               : (H == 64 ? (const void *)fe_sac_grad_kernel<2> : (const void *)fe_sac_grad_kernel<4>);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kSacGradBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "SAC gradient kernel: hipFuncSetAttribute / occupancy query");
+    int64_t resident = (int64_t)env->cus * per_cu;
+    if (resident < 1) resident = 1;
+    g.groups = max_groups < resident ? max_groups : resident;
+    void *args[] = {&g};
+    if (int rc = launched("fe_sac_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups), dim3(kSacGradBlock),
+                                                                       args, lds, (hipStream_t)stream)))
+        return rc;
+    hipLaunchKernelGGL(fe_sac_grad_reduce_kernel, dim3(grid_for(sac_grad_part_floats(H))), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H);
+    return launched("fe_sac_backward: reduction");
 }
 
 }  // extern "C"

@@ -10,12 +10,16 @@ multi-asset observation ``(B, W, 5A)`` into those.
 ``FusedSACRollout`` runs ``SACAgent.step`` -> ``env.step`` (SAC_agent.py:110-121) for K steps in one launch of
 ``fe_env_rollout_sac`` (include/finenvs_amd_sac.h): the LSTM recurrence of ``FusedLSTMRollout`` plus the SAC head,
 with ``mu_layer`` / ``std_layer`` of one output per pair (``A = 1``).  Its ``forward`` is the no-grad actor half of
-``compute_targets`` (SAC_agent.py:200-225) on observation descriptors, e.g. replayed next states.
+``compute_targets`` (SAC_agent.py:200-225) on observation descriptors, e.g. replayed next states.  The gradient half
+runs on descriptors too: ``sample`` is ``forward``'s (actions, log_probs) as a differentiable function of the actor's
+ten parameters (C ABI ``fe_sac_backward``, include/finenvs_amd_sac_grad.h), and ``actor_losses`` the actor's and the
+temperature's losses of ``Actor.compute_losses`` (SAC/actor.py:63-81) on replayed transitions.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -129,6 +133,66 @@ def unpack_last_layer(wl: torch.Tensor) -> torch.Tensor:
     return wl.reshape(H // 32, H // 8, 2, 32, 4).permute(0, 3, 1, 2, 4).reshape(H, H)
 
 
+SAC_GRAD_KEYS = ("w_ih", "w_hh", "b_ih", "b_hh", "w_l", "b_l", "w_mu", "b_mu", "w_std", "b_std")  # fe_sac_grads' fields
+
+
+def actor_parameters(actor: nn.Module) -> Tuple[torch.Tensor, ...]:
+    """The ten parameter tensors of a SAC actor in ``SAC_GRAD_KEYS`` order: ``lstm.weight_ih_l0 (4H, 5)``,
+    ``weight_hh_l0 (4H, H)``, ``bias_ih_l0``, ``bias_hh_l0`` (4H), ``last_layer[0].weight (H, H)`` / ``.bias (H)``,
+    ``mu_layer.weight (1, H)`` / ``.bias (1)``, ``std_layer.weight (1, H)`` / ``.bias (1)``."""
+    lstm, last = actor.lstm, actor.last_layer[0]
+    return (lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, last.weight, last.bias,
+            actor.mu_layer.weight, actor.mu_layer.bias, actor.std_layer.weight, actor.std_layer.bias)
+
+
+class _SacSample(torch.autograd.Function):
+    """(actions, log_probs) of ``FusedSACRollout.forward`` as a differentiable function of the actor's ten parameters:
+    the forward is ``fe_sac_forward``, the backward ``fe_sac_backward`` (the same activations, recomputed)."""
+
+    @staticmethod
+    def forward(ctx, roll, src, pos, noise, *params):
+        actions, log_probs, means, stds = roll.forward(src, pos, noise)
+        roll.last = {"means": means, "stds": stds}
+        ctx.set_materialize_grads(False)  # an output nobody used gets None, not zeros: its pointer is null
+        # the packed weights and the two bias floats forward() fetched: backward makes no second copy to the host
+        # (an empty batch packs nothing and launches nothing, in either direction)
+        ctx.roll, ctx.packed, ctx.biases = roll, getattr(roll, "_packed", None), getattr(roll, "_biases", None)
+        ctx.save_for_backward(src, pos, noise, actions, stds)
+        return actions, log_probs
+
+    @staticmethod
+    def backward(ctx, g_a, g_lp):
+        roll = ctx.roll
+        out = [None] * 14
+        if (g_a is None and g_lp is None) or not any(ctx.needs_input_grad[4:]):
+            return tuple(out)
+        src, pos, noise, actions, stds = ctx.saved_tensors
+        env, H, B = roll.env, roll.H, int(src.numel())
+        dev = env._dev
+        shapes = {"w_ih": (4 * H, 5), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,), "w_l": (H, H), "b_l": (H,),
+                  "w_mu": (1, H), "b_mu": (1,), "w_std": (1, H), "b_std": (1,)}
+        grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in SAC_GRAD_KEYS]
+        if B:
+            g_a, g_lp = (None if g is None else g.reshape(B).float().contiguous() for g in (g_a, g_lp))
+            ws = torch.empty((int(env._lib.fe_sac_grad_workspace_floats(H, int(env.num_intervals), B)),),
+                             dtype=torch.float32, device=dev)
+            w, (bmu, bstd) = ctx.packed, ctx.biases
+            sg = _lib.FeSacGrads(*(g.data_ptr() for g in grads))
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            _lib.check(env._lib.fe_sac_backward(
+                env._handle, roll._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(),
+                w["bl"].data_ptr(), w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, H, src.data_ptr(),
+                pos.data_ptr(), B, noise.data_ptr(), actions.data_ptr(), stds.data_ptr(), ptr(g_a), ptr(g_lp),
+                ws.data_ptr(), C.byref(sg), env._stream()), env._lib)
+        else:
+            for g in grads:
+                g.zero_()
+        for k in range(10):
+            if ctx.needs_input_grad[4 + k]:
+                out[4 + k] = grads[k]
+        return tuple(out)
+
+
 class FusedSACRollout(_FusedEvaluation):
     """K env steps per launch with the SAC actor's head in the kernel (C ABI ``fe_env_rollout_sac``).
 
@@ -150,6 +214,7 @@ class FusedSACRollout(_FusedEvaluation):
         if self._lr32 is None:
             self._lr32 = env.log_return_environments.float().contiguous()
         self.means = self.stds = None
+        self.last: Dict[str, torch.Tensor] = {}  # means / stds of the latest sample()
         self.sync_from_env()
 
     def _weights(self):
@@ -158,7 +223,7 @@ class FusedSACRollout(_FusedEvaluation):
             raise ValueError(f"the actor's parameters must live on the env's device {self.env._dev}")
         # the two output biases are kernel arguments: one small copy to the host, ordered after any pending update
         bmu, bstd = torch.cat([w["bmu"], w["bstd"]]).cpu().tolist()
-        self._packed = w  # kept alive until the launch has been queued
+        self._packed, self._biases = w, (bmu, bstd)  # kept alive until the launch has been queued
         return (self._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(), w["bl"].data_ptr(),
                 w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, self.H)
 
@@ -238,3 +303,69 @@ class FusedSACRollout(_FusedEvaluation):
                 env._handle, *self._weights(), src.data_ptr(), pos.data_ptr(), B, ptr(noise), ptr(actions),
                 ptr(log_probs), means.data_ptr(), stds.data_ptr(), env._stream()))
         return actions, log_probs, means, stds
+
+    # ---------------------------------------------------------------- the gradient half
+    def sample(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, noise: torch.Tensor):
+        """``forward``'s ``(actions, log_probs)``, each (B, 1) float32 and the same values bit for bit, as a
+        differentiable function of the actor's ten parameters (C ABI ``fe_sac_backward``,
+        include/finenvs_amd_sac_grad.h): ``get_actions_and_log_probs`` (SAC/actor.py:51-61) with ``noise`` (B, 1) the
+        standard normals of ``rsample``.  ``backward()`` accumulates into the parameters' ``.grad`` as the torch module
+        would; an output that received no gradient costs nothing, and with every parameter frozen nothing launches.
+        The means and stds of the call stay in ``self.last`` (not differentiable)."""
+        env = self.env
+        if int(env.num_assets) != 1:
+            raise ValueError(f"the fused actor gradient runs one asset (the env has {env.num_assets}): its consumer, the "
+                             "fused twin critic, does")
+        if not isinstance(obs_src, torch.Tensor) or not isinstance(obs_pos, torch.Tensor):
+            raise ValueError("obs_src / obs_pos must be tensors of observation descriptors")
+        B = int(obs_src.numel())
+        if noise is None:
+            raise ValueError(f"sample needs noise: a ({B}, 1) float32 tensor of standard normals on {env._dev}")
+        noise = self._check_noise(noise, (B, 1))
+        params = actor_parameters(self.actor)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError("the fused actor's gradient needs float32 parameters")
+        if any(p.device != torch.device(env._dev) for p in params):
+            raise ValueError(f"the actor's parameters must live on the env's device {env._dev}")
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, 1).to(device=env._dev, dtype=torch.float64).contiguous()
+        return _SacSample.apply(self, src, pos, noise, *params)
+
+    def actor_losses(self, buffer, indices: torch.Tensor, twin, noise: Optional[torch.Tensor] = None):
+        """``(actor_loss, alpha_loss)`` of ``Actor.compute_losses`` (SAC/actor.py:63-81) on the transitions ``indices``
+        (logical, (B,)) of ``buffer``: the ring's state descriptors, nothing rendered.  ``sample`` with ``noise`` (B, 1)
+        -- by default ``torch.randn``, the draw ``rsample`` makes -- then ``q = min(twin.q(src, pos, actions))`` of
+        ``twin``, a ``FusedTwinCritic`` of this env, and
+
+            entropy_term = -log_alpha.exp() * mean_log_probs
+            actor_loss = -(q + entropy_term).mean()
+            alpha_loss = (-log_alpha.exp() * (mean_log_probs + target_entropy).detach()).mean()
+
+        with ``log_alpha`` / ``target_entropy`` the actor's.  ``alpha`` enters the actor loss as the reference combines
+        it, with its graph: ``actor_loss.backward()`` also leaves ``mean(log_probs) * alpha`` in ``log_alpha.grad``, which
+        the reference discards (its temperature optimizer zeroes the gradient before ``alpha_loss.backward()``).
+        examples/sac_time_series.py writes the detached form ``-(q - alpha.detach() * mean_log_probs).mean()``: the same
+        value and the same actor gradients, without that stray temperature gradient.  ``backward()`` of the actor loss
+        also accumulates into the critics' ``.grad`` unless they are frozen (as in torch); an index outside
+        ``[0, size)`` makes the actor loss NaN."""
+        from .critic import FusedTwinCritic
+
+        if not isinstance(twin, FusedTwinCritic) or twin.env is not self.env:
+            raise ValueError("twin must be a FusedTwinCritic of this rollout's env")
+        if indices is None:
+            raise ValueError("actor_losses needs the indices of the sampled transitions")
+        idx = twin._indices(buffer, indices, None)
+        B = int(idx.numel())
+        if noise is None:
+            noise = torch.randn((B, 1), device=self.env._dev)
+        slots = buffer.physical(idx)
+        src, pos = buffer.state_src[slots], buffer.state_pos[slots].reshape(B)
+        actions, log_probs = self.sample(src, pos, noise)
+        q = torch.min(*twin.q(src, pos, actions))
+        valid = ((idx >= 0) & (idx < buffer.size())).reshape(B, 1)
+        q = torch.where(valid, q, torch.full((), float("nan"), device=q.device))
+        mean_log_probs = log_probs.mean(dim=1, keepdim=True)
+        log_alpha = self.actor.log_alpha
+        actor_loss = -(q + -log_alpha.exp() * mean_log_probs).mean()
+        alpha_loss = (-log_alpha.exp() * (mean_log_probs + self.actor.target_entropy).detach()).mean()
+        return actor_loss, alpha_loss
