@@ -6,7 +6,7 @@ fields written into a trajectory chunk whose ``states`` are 16-byte descriptors)
 user code (agents are out of this repo's scope): clipped-surrogate PPO with an LSTM actor and an LSTM critic, shaped
 like finenvs/agents/PPO/{PPO_agent,continuous_actor,critic}.py.
 
-    python examples/ppo_lstm_fused.py [--envs 4096] [--steps 16] [--iters 5] [--hidden 64] [--window 4]
+    python examples/ppo_lstm_fused.py [--envs 4096] [--steps 16] [--iters 5] [--hidden 64] [--window 4] [--fused-update]
 
 What runs where:
     rollout   : FusedLSTMRollout.run(K, noise, std, trajectory)       one launch per K steps, nothing written but
@@ -14,6 +14,9 @@ What runs where:
     values    : FusedLSTMRollout(..., "none").forward(descriptors)    all (K + 1) x N states in one launch, no observations
     returns   : TrajectoryBuffer.returns_and_advantages               one reverse-scan kernel (buffer.py:80-100)
     update    : torch autograd on minibatches rendered from descriptors (PPO_agent.py:175-196)
+                --fused-update: ppo_actor_loss / ppo_critic_loss of finenvs_amd/lstm_head.py on the minibatches'
+                descriptors (fe_lstm_forward / fe_lstm_backward, H <= 128): nothing is rendered, and the updated
+                parameters reach the rollout kernel without a trip through the host
 """
 import argparse
 import math
@@ -27,6 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
+from finenvs_amd.lstm_head import FusedLSTMHead, ppo_actor_loss, ppo_critic_loss  # noqa: E402
+from finenvs_amd.lstm_head import LSTMHead as TrainableLSTMHead  # noqa: E402
 from finenvs_amd.rollout import FusedLSTMRollout  # noqa: E402
 from finenvs_amd.stats import EpisodeStats  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
@@ -46,20 +51,29 @@ class LSTMHead(torch.nn.Module):
         return torch.tanh(out) if self.squash else out
 
 
-def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatches=4, seed=0, quiet=False):
+def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatches=4, seed=0, quiet=False,
+         fused_update=False):
     torch.manual_seed(seed)
     dev = "cuda:0"
     prices, day_id, _ = synthetic.synthetic_series(12, 1, 390, 1234)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=envs, redraw="device", seed=seed,
                         obs_dtype=torch.float32)  # the learner consumes states.float() (PPO_agent.py:101)
-    actor, critic = LSTMHead(hidden, True).to(dev), LSTMHead(hidden, False).to(dev)
+    if fused_update:
+        actor = TrainableLSTMHead(hidden, window, "tanh", device=dev)
+        critic = TrainableLSTMHead(hidden, window, "none", device=dev)
+    else:
+        actor, critic = LSTMHead(hidden, True).to(dev), LSTMHead(hidden, False).to(dev)
     log_std = torch.nn.Parameter(torch.full((1,), math.log(0.5), device=dev))
     opt_a = torch.optim.Adam(list(actor.parameters()) + [log_std], 3e-4)
     opt_c = torch.optim.Adam(critic.parameters(), 3e-4)
     traj = TrajectoryBuffer(steps, envs, 1, states=True)
     stats = EpisodeStats(env)
-    roll = FusedLSTMRollout.from_modules(env, actor.lstm, actor.last)
-    value_head = FusedLSTMRollout.from_modules(env, critic.lstm, critic.last, output_activation="none")
+    if fused_update:  # the heads train on descriptors; each owns the rollout object that runs its parameters
+        actor_head, critic_head = FusedLSTMHead(env, actor), FusedLSTMHead(env, critic)
+        roll, value_head = actor_head.rollout, critic_head.rollout
+    else:
+        roll = FusedLSTMRollout.from_modules(env, actor.lstm, actor.last)
+        value_head = FusedLSTMRollout.from_modules(env, critic.lstm, critic.last, output_activation="none")
     gen = torch.Generator(device=dev).manual_seed(seed)
     clip, ent_coef, gamma = 0.2, 0.01, 0.99
     history = []
@@ -81,6 +95,17 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
         for _ in range(epochs):
             perm = torch.randperm(total, device=dev)
             for mb in perm.chunk(minibatches):
+                if fused_update:  # the same two updates on the minibatch's descriptors (16 bytes per state)
+                    src, pos = traj.minibatch_descriptors(mb)
+                    loss_a = ppo_actor_loss(actor_head, log_std, src, pos, f_act[mb], f_logp[mb], f_adv[mb], clip, ent_coef)
+                    opt_a.zero_grad()
+                    loss_a.backward()
+                    opt_a.step()
+                    loss_c = ppo_critic_loss(critic_head, src, pos, f_ret[mb])
+                    opt_c.zero_grad()
+                    loss_c.backward()
+                    opt_c.step()
+                    continue
                 states = traj.minibatch_states(env, mb)  # (B, W, 5) f32, rendered now
                 dist = torch.distributions.Normal(actor(states).squeeze(-1), log_std.exp())
                 ratio = (dist.log_prob(f_act[mb]) - f_logp[mb]).exp()
@@ -94,9 +119,13 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
                 opt_c.zero_grad()
                 loss_c.backward()
                 opt_c.step()
-        for head, net in ((roll, actor), (value_head, critic)):  # the updated networks go back into the kernels
-            head.set_weights(net.lstm.weight_ih_l0, net.lstm.weight_hh_l0, net.lstm.bias_ih_l0, net.lstm.bias_hh_l0,
-                             net.last.weight, float(net.last.bias.detach()))
+        if fused_update:  # the last optimizer steps, packed on the device
+            actor_head.refresh()
+            critic_head.refresh()
+        else:
+            for head, net in ((roll, actor), (value_head, critic)):  # the updated networks go back into the kernels
+                head.set_weights(net.lstm.weight_ih_l0, net.lstm.weight_hh_l0, net.lstm.bias_ih_l0, net.lstm.bias_hh_l0,
+                                 net.last.weight, float(net.last.bias.detach()))
         traj.clear()
         log = stats.read(reset=True)
         history.append((float(loss_c.detach()), float(rewards.mean()), log))
@@ -118,5 +147,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=64, choices=[32, 64, 128, 256, 512, 1024])
     ap.add_argument("--window", type=int, default=4)
+    ap.add_argument("--fused-update", action="store_true",
+                    help="train both heads on descriptors with the fused backward (hidden <= 128)")
     a = ap.parse_args()
-    main(a.envs, a.steps, a.iters, a.hidden, a.window)
+    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update)

@@ -176,6 +176,20 @@ SAC_GRAD_SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, C.POINTER(FeSacGrads), _vp]),
 }
 
+
+# include/finenvs_amd_lstm_grad.h: the one-output LSTM head's backward pass (finenvs_amd/lstm_head.py; same library)
+class FeLstmGrads(C.Structure):
+    """struct fe_lstm_grads of include/finenvs_amd_lstm_grad.h."""
+
+    _fields_ = [("w_ih", _vp), ("w_hh", _vp), ("b_ih", _vp), ("b_hh", _vp), ("w_out", _vp), ("b_out", _vp)]
+
+
+LSTM_GRAD_SIGNATURES = {
+    "fe_lstm_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_lstm_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                   C.POINTER(FeLstmGrads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -201,7 +215,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
             ) from exc
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
-                         **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES}.items():
+                         **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
+                         **LSTM_GRAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

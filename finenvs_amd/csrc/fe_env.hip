@@ -39,6 +39,7 @@
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
 //   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
+//   fe_lstm_grad_kernels.h    the one-output LSTM head's backward pass (PPO actor / critic, TD3 actor) and its reduction
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
 //                         headers in include/
@@ -67,6 +68,7 @@
 #include "finenvs_amd_critic.h"
 #include "finenvs_amd_critic_grad.h"
 #include "finenvs_amd_sac_grad.h"
+#include "finenvs_amd_lstm_grad.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -79,6 +81,7 @@
 #include "fe_critic_kernels.h"
 #include "fe_critic_grad_kernels.h"
 #include "fe_sac_grad_kernels.h"
+#include "fe_lstm_grad_kernels.h"
 
 namespace {
 
@@ -1609,6 +1612,74 @@ int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, cons
     hipLaunchKernelGGL(fe_sac_grad_reduce_kernel, dim3(grid_for(sac_grad_part_floats(H))), dim3(kBlock), 0,
                        (hipStream_t)stream, g, H);
     return launched("fe_sac_backward: reduction");
+}
+
+
+// ---- include/finenvs_amd_lstm_grad.h: the one-output LSTM head's backward pass ----
+// Workspace: [W_hh^T][partials of every workgroup][stash of every workgroup].
+int64_t fe_lstm_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t groups = tiles < lstm_grad_max_groups(H) ? tiles : lstm_grad_max_groups(H);
+    return lstm_grad_wt_floats(H) + groups * (lstm_grad_part_floats(H) + lstm_grad_stash_floats(H, W));
+}
+
+int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                     int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                     const float *outputs, const float *d_outputs, float *workspace, const fe_lstm_grads *grads,
+                     void *stream) {
+    static const char *who = "fe_lstm_backward";
+    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || count < 0 || !d_outputs || !workspace ||
+        !grads || !grads->w_ih || !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_out || !grads->b_out)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (out_activation != 0 && out_activation != 2)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on "
+                    "(got %d)", who, (int)out_activation);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_lstm_forward returned", who);
+    if (H != 32 && H != 64 && H != 128)
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the streamed-weight forward of H >= 256 has no "
+                    "register-resident recurrence to mirror", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused twin "
+                    "critic does)", who, (int)env->p.A);
+    if (count == 0) return FE_OK;
+    const size_t lds = lstm_grad_lds_bytes(H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const int64_t tiles = (count + 31) / 32;
+    const int64_t max_groups = tiles < lstm_grad_max_groups(H) ? tiles : lstm_grad_max_groups(H);
+    LstmGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
+    g.whh = whh; g.wx = wx; g.wout = wout; g.outputs = outputs; g.d_outputs = d_outputs;
+    g.wt = workspace;
+    g.part = g.wt + lstm_grad_wt_floats(H);
+    g.stash = g.part + max_groups * lstm_grad_part_floats(H);
+    g.count = count; g.num_tiles = tiles; g.W = W; g.out_act = out_activation;
+    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_out;
+    g.g_bout = grads->b_out;
+    hipLaunchKernelGGL(fe_lstm_grad_pack_kernel, dim3(grid_for(lstm_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    if (int rc = launched("fe_lstm_backward: weight transpose")) return rc;
+    const void *kern = H == 32 ? (const void *)fe_lstm_grad_kernel<1>
+                               : (H == 64 ? (const void *)fe_lstm_grad_kernel<2> : (const void *)fe_lstm_grad_kernel<4>);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kLstmGradBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query");
+    int64_t resident = (int64_t)env->cus * per_cu;
+    if (resident < 1) resident = 1;
+    g.groups = max_groups < resident ? max_groups : resident;
+    void *args[] = {&g};
+    if (int rc = launched("fe_lstm_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups), dim3(kLstmGradBlock),
+                                                                        args, lds, (hipStream_t)stream)))
+        return rc;
+    hipLaunchKernelGGL(fe_lstm_grad_reduce_kernel, dim3(grid_for(lstm_grad_part_floats(H))), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H);
+    return launched("fe_lstm_backward: reduction");
 }
 
 }  // extern "C"

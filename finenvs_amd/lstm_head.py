@@ -1,0 +1,248 @@
+"""The one-output LSTM head of the reference's PPO and TD3 learners: the torch module, and its fused training path.
+
+``LSTMHead`` restates ``LSTMNetwork((5, H, 1), sequence_length=W, output_activation)`` of
+finenvs/agents/networks/lstm.py:28-57 -- ``nn.LSTM(5, H)`` over the observation window, ``last_layer = Linear(H, 1)``
+on the last hidden state, then ``Tanh`` or ``Identity``.  Three of the reference's networks are this module:
+PPO's ``ContinuousActorLSTM`` (PPO/continuous_actor.py:104-124, tanh), PPO's ``CriticLSTM`` (PPO/critic.py:53-68,
+identity) and TD3's ``ActorLSTM`` (TD3/actor.py:83-94, tanh).  Its submodule names are the reference's, so a reference
+``state_dict`` (without the learner's own ``log_standard_deviation``) loads unchanged.
+
+``FusedLSTMHead`` evaluates such a module on observation descriptors (C ABI ``fe_lstm_forward``) as a differentiable
+function of its six parameters (C ABI ``fe_lstm_backward``, include/finenvs_amd_lstm_grad.h): no observation is
+rendered in either direction.  It owns the ``FusedLSTMRollout`` that acts with the same parameters in the kernel.
+``ppo_actor_loss`` / ``ppo_critic_loss`` / ``td3_actor_loss`` are the reference's three losses on that output.  Scope:
+one asset, H in {32, 64, 128}.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Tuple
+
+import torch
+import torch.nn as nn
+from torch.distributions import Normal
+
+from . import _lib
+from .rollout import FusedLSTMRollout, lstm_pack
+
+LSTM_HEAD_HIDDEN_SIZES = (32, 64, 128)
+LSTM_HEAD_ACTIVATIONS = {"tanh": nn.Tanh, "none": nn.Identity}
+LSTM_GRAD_KEYS = ("w_ih", "w_hh", "b_ih", "b_hh", "w_out", "b_out")  # fe_lstm_grads' fields, in head_parameters' order
+
+
+class LSTMHead(nn.Module):
+    """The reference's ``LSTMNetwork((5, H, 1), sequence_length=W, output_activation)`` as a plain module (no optimizer
+    inside): ``lstm = nn.LSTM(5, H, batch_first=True)`` and ``last_layer = Sequential(Linear(H, 1), Tanh() |
+    Identity())``.  ``output_activation``: ``"tanh"`` (the two actors) or ``"none"`` (PPO's critic)."""
+
+    def __init__(self, H: int = 128, W: int = 4, output_activation: str = "tanh", device=None):
+        super().__init__()
+        if output_activation not in LSTM_HEAD_ACTIVATIONS:
+            raise ValueError(f"output_activation must be one of {sorted(LSTM_HEAD_ACTIVATIONS)} (got {output_activation!r}): "
+                             '"clamp" bounds an action, it is not an output a learner trains through')
+        self.input_size, self.hidden_size, self.output_size, self.sequence_length = 5, int(H), 1, int(W)
+        self.output_activation = output_activation
+        self.lstm = nn.LSTM(5, self.hidden_size, num_layers=1, batch_first=True, device=device)
+        self.last_layer = nn.Sequential(nn.Linear(self.hidden_size, 1, device=device),
+                                        LSTM_HEAD_ACTIVATIONS[output_activation]())
+
+    def forward(self, states: torch.Tensor) -> torch.Tensor:
+        """(B, W, 5) -> (B, 1)."""
+        if states.dim() != 3 or states.shape[1] != self.sequence_length or states.shape[2] != self.input_size:
+            raise ValueError(f"states must be (B, {self.sequence_length}, {self.input_size}), got {tuple(states.shape)}")
+        out, _ = self.lstm(states)
+        return self.last_layer(out[:, -1, :])
+
+
+def check_head(module: nn.Module) -> Tuple[int, str]:
+    """(hidden size, output activation) of a module the fused head can run; ValueError otherwise."""
+    lstm = getattr(module, "lstm", None)
+    if not isinstance(lstm, nn.LSTM):
+        raise ValueError("the fused LSTM head needs a module with an nn.LSTM `lstm`")
+    if lstm.num_layers != 1 or lstm.bidirectional or lstm.input_size != 5 or not lstm.batch_first or lstm.proj_size:
+        raise ValueError("the fused LSTM head needs nn.LSTM(5, H, num_layers=1, batch_first=True)")
+    H = int(lstm.hidden_size)
+    if H not in LSTM_HEAD_HIDDEN_SIZES:
+        raise ValueError(f"the fused LSTM head trains H in {LSTM_HEAD_HIDDEN_SIZES} (got {H}): the streamed-weight forward "
+                         "of H >= 256 has no register-resident recurrence for a backward to mirror")
+    last = getattr(module, "last_layer", None)
+    if not isinstance(last, nn.Sequential) or len(last) != 2 or not isinstance(last[0], nn.Linear) \
+            or last[0].in_features != H or last[0].out_features != 1 or last[0].bias is None:
+        raise ValueError(f"last_layer must be Sequential(Linear({H}, 1), Tanh() or Identity()): one output per (env, asset) "
+                         "pair")
+    if isinstance(last[1], nn.Tanh):
+        return H, "tanh"
+    if isinstance(last[1], nn.Identity):
+        return H, "none"
+    raise ValueError(f"the output activation must be Tanh or Identity (got {type(last[1]).__name__}): a clamp has no "
+                     "gradient to train on")
+
+
+def head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
+    """The six parameter tensors of a head in ``LSTM_GRAD_KEYS`` order: ``lstm.weight_ih_l0 (4H, 5)``, ``weight_hh_l0
+    (4H, H)``, ``bias_ih_l0``, ``bias_hh_l0`` (4H), ``last_layer[0].weight (1, H)`` and ``.bias (1)``."""
+    lstm, last = module.lstm, module.last_layer[0]
+    return lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, last.weight, last.bias
+
+
+class _HeadValue(torch.autograd.Function):
+    """``FusedLSTMRollout.forward`` as a differentiable function of the head's six parameters: the forward is
+    ``fe_lstm_forward``, the backward ``fe_lstm_backward`` (the same activations, recomputed)."""
+
+    @staticmethod
+    def forward(ctx, head, src, pos, *params):
+        roll = head.rollout
+        out = roll.forward(src, pos)
+        ctx.set_materialize_grads(False)
+        # the packed weights forward() ran with: backward packs nothing again and makes no copy to the host
+        ctx.head, ctx.packed = head, (roll.whh, roll.wx, roll.wout)
+        ctx.save_for_backward(src, pos, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        out = [None] * 9
+        if g_out is None or not any(ctx.needs_input_grad[3:]):
+            return tuple(out)
+        head = ctx.head
+        src, pos, values = ctx.saved_tensors
+        env, H, B = head.env, head.H, int(src.numel())
+        dev = env._dev
+        shapes = {"w_ih": (4 * H, 5), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,), "w_out": (1, H), "b_out": (1,)}
+        grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in LSTM_GRAD_KEYS]
+        if B:
+            g_out = g_out.reshape(B).float().contiguous()
+            ws = torch.empty((int(env._lib.fe_lstm_grad_workspace_floats(H, int(env.num_intervals), B)),),
+                             dtype=torch.float32, device=dev)
+            whh, wx, wout = ctx.packed
+            lg = _lib.FeLstmGrads(*(g.data_ptr() for g in grads))
+            _lib.check(env._lib.fe_lstm_backward(
+                env._handle, head.rollout._lr32.data_ptr(), whh.data_ptr(), wx.data_ptr(), wout.data_ptr(), H,
+                head.rollout.out_act, src.data_ptr(), pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(),
+                ws.data_ptr(), C.byref(lg), env._stream()), env._lib)
+        else:
+            for g in grads:
+                g.zero_()
+        for k in range(6):
+            if ctx.needs_input_grad[3 + k]:
+                out[3 + k] = grads[k]
+        return tuple(out)
+
+
+class FusedLSTMHead:
+    """An ``LSTMHead`` (or the reference's network of that shape) trained on observation descriptors.
+
+    ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_lstm_forward`` --
+    (B, 1) float32, differentiable with respect to the module's six parameters through ``fe_lstm_backward``;
+    ``backward()`` accumulates into their ``.grad`` as the torch module would.  ``.rollout`` is a ``FusedLSTMRollout``
+    of the same parameters: ``run`` steps the env with them, ``evaluate_returns`` evaluates them, and it serves as
+    ``FusedTwinCritic.td3_targets(target_actor=head.rollout)``.  The module's parameters are re-packed on the device at
+    every call (``refresh``), so an optimizer step is seen by the next call and by the next ``rollout.run`` after a
+    ``refresh()``.  The module must live on the env's device."""
+
+    def __init__(self, env, module: nn.Module):
+        self.H, self.output_activation = check_head(module)
+        if int(env.num_assets) != 1:
+            raise ValueError(f"the fused LSTM head trains one asset (the env has {env.num_assets}), as the fused twin "
+                             "critic does")
+        self.env, self.module = env, module
+        self._check_parameters()
+        self.rollout = FusedLSTMRollout.from_modules(env, module.lstm, module.last_layer[0], self.output_activation)
+
+    def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
+        params = head_parameters(self.module)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError("the fused LSTM head's gradient needs float32 parameters")
+        if any(p.device != torch.device(self.env._dev) for p in params):
+            raise ValueError(f"the head's parameters must live on the env's device {self.env._dev}")
+        return params
+
+    def refresh(self) -> None:
+        """The module's current parameters into ``self.rollout``, packed on the device (``lstm_pack``).  One 4-byte copy
+        of the output bias goes to the host, ordered after any pending update: ``fe_lstm_forward`` takes it by value."""
+        w_ih, w_hh, b_ih, b_hh, w_out, b_out = self._check_parameters()
+        roll = self.rollout
+        roll.whh, roll.wx = lstm_pack(w_ih, w_hh, b_ih, b_hh, self.H)
+        roll.wout = w_out.detach().reshape(self.H).clone()
+        roll.bout = float(b_out.detach())
+
+    def __call__(self, obs_src: torch.Tensor, obs_pos: torch.Tensor) -> torch.Tensor:
+        """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B,)`` or ``(B, 1)`` float64):
+        (B, 1) float32, ``self.rollout.forward``'s values bit for bit."""
+        env = self.env
+        if not isinstance(obs_src, torch.Tensor) or not isinstance(obs_pos, torch.Tensor):
+            raise ValueError("obs_src / obs_pos must be tensors of observation descriptors")
+        B = int(obs_src.numel())
+        if obs_pos.numel() != B:
+            raise ValueError(f"obs_pos must hold one position per descriptor ({B}), got {tuple(obs_pos.shape)}")
+        params = self._check_parameters()
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, 1).to(device=env._dev, dtype=torch.float64).contiguous()
+        if B:  # an empty batch packs nothing and launches nothing, in either direction
+            self.refresh()
+        return _HeadValue.apply(self, src, pos, *params)
+
+
+# ---------------------------------------------------------------- the reference's losses, plain torch on the output
+def torch_ppo_actor_loss(means: torch.Tensor, log_std: torch.Tensor, actions: torch.Tensor, old_log_probs: torch.Tensor,
+                         advantages: torch.Tensor, clip_epsilon: float = 0.2, entropy_coefficient: float = 0.01) -> torch.Tensor:
+    """``ContinuousActor.compute_actor_loss`` (PPO/continuous_actor.py:59-78), its operations in its order, on the
+    actor's output ``means`` (B, 1); ``log_std`` is the learner's ``log_standard_deviation`` (1, 1)."""
+    distribution = Normal(means, torch.exp(log_std))
+    new_log_probs = distribution.log_prob(actions)
+    prob_ratios = torch.exp(new_log_probs - old_log_probs)
+    first_term = prob_ratios * advantages
+    second_term = torch.clamp(prob_ratios, 1 - clip_epsilon, 1 + clip_epsilon) * advantages
+    mean_clipped_objective = torch.minimum(first_term, second_term).mean().mean()
+    entropy = distribution.entropy().mean()
+    return -(mean_clipped_objective + entropy_coefficient * entropy)
+
+
+def torch_ppo_critic_loss(values: torch.Tensor, returns: torch.Tensor) -> torch.Tensor:
+    """``Critic.compute_critic_loss`` (PPO/critic.py:26-32) on the critic's output ``values`` (B, 1)."""
+    return ((returns - values) ** 2).mean()
+
+
+def _column(t: torch.Tensor, B: int, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.numel() != B:
+        raise ValueError(f"{name} must be a tensor of {B} elements ((B,) or (B, 1)), got {tuple(getattr(t, 'shape', ()))}")
+    return t.reshape(B, 1)
+
+
+def ppo_actor_loss(head: FusedLSTMHead, log_std: torch.Tensor, src: torch.Tensor, pos: torch.Tensor, actions: torch.Tensor,
+                   old_log_probs: torch.Tensor, advantages: torch.Tensor, clip_epsilon: float = 0.2,
+                   entropy_coefficient: float = 0.01) -> torch.Tensor:
+    """``compute_actor_loss`` (PPO/continuous_actor.py:59-78) on B state descriptors, nothing rendered: the clipped
+    surrogate of ``Normal(head(src, pos), exp(log_std))`` plus the entropy bonus, negated.  ``actions``,
+    ``old_log_probs``, ``advantages``: B elements each.  ``log_std`` gets its gradient from autograd."""
+    B = int(src.numel())
+    return torch_ppo_actor_loss(head(src, pos), log_std, _column(actions, B, "actions"),
+                                _column(old_log_probs, B, "old_log_probs"), _column(advantages, B, "advantages"),
+                                clip_epsilon, entropy_coefficient)
+
+
+def ppo_critic_loss(head: FusedLSTMHead, src: torch.Tensor, pos: torch.Tensor, returns: torch.Tensor) -> torch.Tensor:
+    """``compute_critic_loss`` (PPO/critic.py:26-32) on B state descriptors: the mean squared error of
+    ``head(src, pos)`` against ``returns`` (B elements)."""
+    return torch_ppo_critic_loss(head(src, pos), _column(returns, int(src.numel()), "returns"))
+
+
+def td3_actor_loss(head: FusedLSTMHead, buffer, indices: torch.Tensor, twin) -> torch.Tensor:
+    """``Actor.compute_loss`` (TD3/actor.py:50-56) on the transitions ``indices`` (logical, (B,)) of ``buffer``:
+    ``-twin.q(src, pos, head(src, pos))[0].mean()`` on the ring's state descriptors, nothing rendered (the reference
+    passes its first critic).  ``backward()`` also accumulates into that critic's ``.grad`` unless it is frozen (as in
+    torch); an index outside ``[0, size)`` makes the loss NaN."""
+    from .critic import FusedTwinCritic
+
+    if not isinstance(twin, FusedTwinCritic) or twin.env is not head.env:
+        raise ValueError("twin must be a FusedTwinCritic of this head's env")
+    if indices is None:
+        raise ValueError("td3_actor_loss needs the indices of the sampled transitions")
+    idx = twin._indices(buffer, indices, None)
+    B = int(idx.numel())
+    slots = buffer.physical(idx)
+    src, pos = buffer.state_src[slots], buffer.state_pos[slots].reshape(B)
+    q = twin.q(src, pos, head(src, pos))[0]
+    valid = ((idx >= 0) & (idx < buffer.size())).reshape(B, 1)
+    q = torch.where(valid, q, torch.full((), float("nan"), device=q.device))
+    return -q.mean()

@@ -221,6 +221,18 @@ class TrajectoryBuffer:
         n, t = idx // self.t, idx % self.t
         return env.render(self.obs_src[t, n], self.obs_pos[t, n])
 
+    def minibatch_descriptors(self, sample_indices: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(obs_src (B,), obs_pos (B, A))``: the descriptor rows ``minibatch_states`` renders for the same
+        ``sample_indices`` -- what a head that runs on descriptors (``FusedLSTMHead``) takes instead of the
+        observations."""
+        if not self.has_states:
+            raise RuntimeError("this TrajectoryBuffer was built without states=True")
+        if self.t == 0:
+            raise IndexError("the chunk being filled is empty")
+        idx = sample_indices.reshape(-1).to(device=self.device, dtype=torch.int64)
+        n, t = idx // self.t, idx % self.t
+        return self.obs_src[t, n], self.obs_pos[t, n]
+
     def next_slot(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Zero-copy form of ``store``: views of slot t -- actions (N, A), rewards (N,), dones (N,) --
         for the policy and ``env.step(actions, rewards_out=..., dones_out=...)`` to write into
