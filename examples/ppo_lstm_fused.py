@@ -15,8 +15,8 @@ What runs where:
     returns   : TrajectoryBuffer.returns_and_advantages               one reverse-scan kernel (buffer.py:80-100)
     update    : torch autograd on minibatches rendered from descriptors (PPO_agent.py:175-196)
                 --fused-update: ppo_actor_loss / ppo_critic_loss of finenvs_amd/lstm_head.py on the minibatches'
-                descriptors (fe_lstm_forward / fe_lstm_backward, H <= 128): nothing is rendered, and the updated
-                parameters reach the rollout kernel without a trip through the host
+                descriptors (fe_lstm_forward / fe_lstm_backward; fe_lstm_backward_streamed at H >= 256): nothing is
+                rendered, and the updated parameters reach the rollout kernel without a trip through the host
 """
 import argparse
 import math
@@ -69,7 +69,8 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
     traj = TrajectoryBuffer(steps, envs, 1, states=True)
     stats = EpisodeStats(env)
     if fused_update:  # the heads train on descriptors; each owns the rollout object that runs its parameters
-        actor_head, critic_head = FusedLSTMHead(env, actor), FusedLSTMHead(env, critic)
+        streamed = {"streamed": True} if hidden > 128 else {}  # H >= 256: the chunked backward, an opt-in of the head
+        actor_head, critic_head = FusedLSTMHead(env, actor, **streamed), FusedLSTMHead(env, critic, **streamed)
         roll, value_head = actor_head.rollout, critic_head.rollout
     else:
         roll = FusedLSTMRollout.from_modules(env, actor.lstm, actor.last)
@@ -148,6 +149,7 @@ if __name__ == "__main__":
     ap.add_argument("--hidden", type=int, default=64, choices=[32, 64, 128, 256, 512, 1024])
     ap.add_argument("--window", type=int, default=4)
     ap.add_argument("--fused-update", action="store_true",
-                    help="train both heads on descriptors with the fused backward (hidden <= 128)")
+                    help="train both heads on descriptors with the fused backward (every --hidden; the chunked "
+                         "streamed-weight backward at 256 and above)")
     a = ap.parse_args()
     main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update)

@@ -190,6 +190,14 @@ LSTM_GRAD_SIGNATURES = {
                                    C.POINTER(FeLstmGrads), _vp]),
 }
 
+# include/finenvs_amd_lstm_grad_streamed.h: the same head's backward pass at H = 256 / 512 / 1024 (FeLstmGrads again)
+LSTM_STREAMED_GRAD_SIGNATURES = {
+    "fe_lstm_streamed_grad_chunk_pairs": (_i64, [_i32, _i32]),
+    "fe_lstm_streamed_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_lstm_backward_streamed": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                            C.POINTER(FeLstmGrads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -216,7 +224,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
-                         **LSTM_GRAD_SIGNATURES}.items():
+                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

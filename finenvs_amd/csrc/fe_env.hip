@@ -69,6 +69,7 @@
 #include "finenvs_amd_critic_grad.h"
 #include "finenvs_amd_sac_grad.h"
 #include "finenvs_amd_lstm_grad.h"
+#include "finenvs_amd_lstm_grad_streamed.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -82,6 +83,7 @@
 #include "fe_critic_grad_kernels.h"
 #include "fe_sac_grad_kernels.h"
 #include "fe_lstm_grad_kernels.h"
+#include "fe_lstm_grad_streamed_kernels.h"
 
 namespace {
 
@@ -1680,6 +1682,111 @@ int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, con
     hipLaunchKernelGGL(fe_lstm_grad_reduce_kernel, dim3(grid_for(lstm_grad_part_floats(H))), dim3(kBlock), 0,
                        (hipStream_t)stream, g, H);
     return launched("fe_lstm_backward: reduction");
+}
+
+
+// ---- include/finenvs_amd_lstm_grad_streamed.h: the one-output LSTM head's backward pass at H = 256 / 512 / 1024 ----
+int64_t fe_lstm_streamed_grad_chunk_pairs(int32_t H, int32_t W) {
+    if (!lstm_sgrad_hidden_ok(H) || W < 1) return -1;
+    return lstm_sgrad_chunk_pairs(H, W);
+}
+
+// Workspace: [W_hh^T][split sums][head block sums][gates][c][h_{t-1} | x_t | 1][h_W][dh][dc], the last six for the pairs
+// of one pass.
+int64_t fe_lstm_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!lstm_sgrad_hidden_ok(H) || W < 1 || count < 0) return -1;
+    const int64_t pp = lstm_sgrad_padded_pairs(H, W, count);
+    return lstm_sgrad_wt_floats(H) + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H) +
+           lstm_sgrad_head_blocks(pp) * (H + 32) + pp * (lstm_sgrad_pair_floats(H, W) + 3LL * H);
+}
+
+int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                              int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
+                              int64_t count, const float *outputs, const float *d_outputs, float *workspace,
+                              const fe_lstm_grads *grads, void *stream) {
+    static const char *who = "fe_lstm_backward_streamed";
+    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || count < 0 || !d_outputs || !workspace ||
+        !grads || !grads->w_ih || !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_out || !grads->b_out)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (out_activation != 0 && out_activation != 2)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on "
+                    "(got %d)", who, (int)out_activation);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_lstm_forward returned", who);
+    if (!lstm_sgrad_hidden_ok(H))
+        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); fe_lstm_backward runs H = 32, 64 and 128", who,
+                    (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused twin "
+                    "critic does)", who, (int)env->p.A);
+    if (count == 0) return FE_OK;
+    const size_t lds = lstm_sgrad_forward_lds_bytes(H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
+    hipStream_t st = (hipStream_t)stream;
+    LstmSGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.whh = whh; g.wx = wx; g.wout = wout; g.W = W; g.out_act = out_activation;
+    g.wt = workspace;  // the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest pass (pp pairs)
+    g.part = g.wt + lstm_sgrad_wt_floats(H);
+    g.hpart = g.part + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H);
+    g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_out;
+    g.g_bout = grads->b_out;
+    hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
+    if (int rc = launched("fe_lstm_backward_streamed: weight transpose")) return rc;
+    const void *kern = H == 256 ? (const void *)fe_lstm_sgrad_forward_kernel<4>
+                                : (H == 512 ? (const void *)fe_lstm_sgrad_forward_kernel<8>
+                                            : (const void *)fe_lstm_sgrad_forward_kernel<16>);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "streamed LSTM head gradient kernel: hipFuncSetAttribute / occupancy query");
+    int64_t resident = (int64_t)env->cus * per_cu;
+    if (resident < 1) resident = 1;
+    // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
+    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+        g.cnt = count - c0 < chunk ? count - c0 : chunk;
+        g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
+        g.splits = lstm_sgrad_splits(H, W, g.pp);
+        g.cst = g.gates + (int64_t)W * g.pp * 4 * H;
+        g.vst = g.cst + (int64_t)W * g.pp * H;
+        g.hw = g.vst + (int64_t)W * g.pp * (H + 32);
+        g.dh = g.hw + g.pp * H;
+        g.dc = g.dh + g.pp * H;
+        g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0;
+        g.outputs = outputs ? outputs + c0 : nullptr; g.d_outputs = d_outputs + c0;
+        g.first = c0 == 0;
+        const int64_t tiles = g.pp / 32;
+        void *args[] = {&g};
+        if (int rc = launched("fe_lstm_backward_streamed: recurrence",
+                              hipLaunchKernel(kern, dim3((unsigned)(tiles < resident ? tiles : resident)),
+                                              dim3(kLstmBlock), args, lds, st)))
+            return rc;
+        hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
+        if (int rc = launched("fe_lstm_backward_streamed: head")) return rc;
+        for (int t = W - 1; t >= 0; --t) {
+            g.t = t;
+            hipLaunchKernelGGL(fe_lstm_sgrad_dz_kernel, dim3(grid_for(g.pp * (H / 4))), dim3(kBlock), 0, st, g, H);
+            if (t > 0)
+                hipLaunchKernelGGL(fe_lstm_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles),
+                                   dim3(kBlock), 0, st, g, H);
+            // a launch that fails fails the first time: stop before queueing 2 W launches behind it
+            if (t == W - 1) {
+                if (int rc = launched("fe_lstm_backward_streamed: backward through time")) return rc;
+            }
+        }
+        hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
+                           dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
+                           st, g, H);
+        if (int rc = launched("fe_lstm_backward_streamed: weight gradients")) return rc;
+        hipLaunchKernelGGL(fe_lstm_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
+        if (int rc = launched("fe_lstm_backward_streamed: final write")) return rc;
+    }
+    return FE_OK;
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@ identity) and TD3's ``ActorLSTM`` (TD3/actor.py:83-94, tanh).  Its submodule nam
 function of its six parameters (C ABI ``fe_lstm_backward``, include/finenvs_amd_lstm_grad.h): no observation is
 rendered in either direction.  It owns the ``FusedLSTMRollout`` that acts with the same parameters in the kernel.
 ``ppo_actor_loss`` / ``ppo_critic_loss`` / ``td3_actor_loss`` are the reference's three losses on that output.  Scope:
-one asset, H in {32, 64, 128}.
+one asset, H in {32, 64, 128}; with ``streamed=True`` also H in {256, 512, 1024} (C ABI ``fe_lstm_backward_streamed``,
+include/finenvs_amd_lstm_grad_streamed.h).
 """
 from __future__ import annotations
 
@@ -23,9 +24,10 @@ import torch.nn as nn
 from torch.distributions import Normal
 
 from . import _lib
-from .rollout import FusedLSTMRollout, lstm_pack
+from .rollout import FusedLSTMRollout, lstm_fragment_major, lstm_pack
 
 LSTM_HEAD_HIDDEN_SIZES = (32, 64, 128)
+LSTM_HEAD_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
 LSTM_HEAD_ACTIVATIONS = {"tanh": nn.Tanh, "none": nn.Identity}
 LSTM_GRAD_KEYS = ("w_ih", "w_hh", "b_ih", "b_hh", "w_out", "b_out")  # fe_lstm_grads' fields, in head_parameters' order
 
@@ -54,17 +56,23 @@ class LSTMHead(nn.Module):
         return self.last_layer(out[:, -1, :])
 
 
-def check_head(module: nn.Module) -> Tuple[int, str]:
-    """(hidden size, output activation) of a module the fused head can run; ValueError otherwise."""
+def check_head(module: nn.Module, streamed: bool = False) -> Tuple[int, str]:
+    """(hidden size, output activation) of a module the fused head can run; ValueError otherwise.  ``streamed``: H may
+    also be 256, 512 or 1024 (the chunked backward of ``fe_lstm_backward_streamed``)."""
     lstm = getattr(module, "lstm", None)
     if not isinstance(lstm, nn.LSTM):
         raise ValueError("the fused LSTM head needs a module with an nn.LSTM `lstm`")
     if lstm.num_layers != 1 or lstm.bidirectional or lstm.input_size != 5 or not lstm.batch_first or lstm.proj_size:
         raise ValueError("the fused LSTM head needs nn.LSTM(5, H, num_layers=1, batch_first=True)")
     H = int(lstm.hidden_size)
-    if H not in LSTM_HEAD_HIDDEN_SIZES:
+    if streamed and H not in LSTM_HEAD_HIDDEN_SIZES + LSTM_HEAD_STREAMED_HIDDEN_SIZES:
+        raise ValueError(f"the fused LSTM head trains H in {LSTM_HEAD_HIDDEN_SIZES + LSTM_HEAD_STREAMED_HIDDEN_SIZES} "
+                         f"(got {H})")
+    if not streamed and H not in LSTM_HEAD_HIDDEN_SIZES:
         raise ValueError(f"the fused LSTM head trains H in {LSTM_HEAD_HIDDEN_SIZES} (got {H}): the streamed-weight forward "
-                         "of H >= 256 has no register-resident recurrence for a backward to mirror")
+                         "of H >= 256 has no register-resident recurrence for a backward to mirror"
+                         + ("; pass streamed=True for the chunked backward of H in "
+                            f"{LSTM_HEAD_STREAMED_HIDDEN_SIZES}" if H in LSTM_HEAD_STREAMED_HIDDEN_SIZES else ""))
     last = getattr(module, "last_layer", None)
     if not isinstance(last, nn.Sequential) or len(last) != 2 or not isinstance(last[0], nn.Linear) \
             or last[0].in_features != H or last[0].out_features != 1 or last[0].bias is None:
@@ -112,11 +120,13 @@ class _HeadValue(torch.autograd.Function):
         grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in LSTM_GRAD_KEYS]
         if B:
             g_out = g_out.reshape(B).float().contiguous()
-            ws = torch.empty((int(env._lib.fe_lstm_grad_workspace_floats(H, int(env.num_intervals), B)),),
-                             dtype=torch.float32, device=dev)
+            streamed = H > 128
+            floats = env._lib.fe_lstm_streamed_grad_workspace_floats if streamed else env._lib.fe_lstm_grad_workspace_floats
+            ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
             whh, wx, wout = ctx.packed
             lg = _lib.FeLstmGrads(*(g.data_ptr() for g in grads))
-            _lib.check(env._lib.fe_lstm_backward(
+            backward = env._lib.fe_lstm_backward_streamed if streamed else env._lib.fe_lstm_backward
+            _lib.check(backward(
                 env._handle, head.rollout._lr32.data_ptr(), whh.data_ptr(), wx.data_ptr(), wout.data_ptr(), H,
                 head.rollout.out_act, src.data_ptr(), pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(),
                 ws.data_ptr(), C.byref(lg), env._stream()), env._lib)
@@ -138,10 +148,15 @@ class FusedLSTMHead:
     of the same parameters: ``run`` steps the env with them, ``evaluate_returns`` evaluates them, and it serves as
     ``FusedTwinCritic.td3_targets(target_actor=head.rollout)``.  The module's parameters are re-packed on the device at
     every call (``refresh``), so an optimizer step is seen by the next call and by the next ``rollout.run`` after a
-    ``refresh()``.  The module must live on the env's device."""
+    ``refresh()``.  The module must live on the env's device.
 
-    def __init__(self, env, module: nn.Module):
-        self.H, self.output_activation = check_head(module)
+    ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent weights stream from L2.  It is an
+    opt-in because that backward is several launches per LSTM time step and its workspace grows with the batch up to
+    ``fe_lstm_streamed_grad_chunk_pairs`` pairs (2 GiB of activations), unlike the bounded one of H <= 128; H <= 128
+    runs the register-resident way either way."""
+
+    def __init__(self, env, module: nn.Module, streamed: bool = False):
+        self.H, self.output_activation = check_head(module, streamed)
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused LSTM head trains one asset (the env has {env.num_assets}), as the fused twin "
                              "critic does")
@@ -163,6 +178,8 @@ class FusedLSTMHead:
         w_ih, w_hh, b_ih, b_hh, w_out, b_out = self._check_parameters()
         roll = self.rollout
         roll.whh, roll.wx = lstm_pack(w_ih, w_hh, b_ih, b_hh, self.H)
+        if self.H > 128:  # the streaming kernels read whh fragment-major, as FusedLSTMRollout.set_weights packs it
+            roll.whh = lstm_fragment_major(roll.whh, self.H)
         roll.wout = w_out.detach().reshape(self.H).clone()
         roll.bout = float(b_out.detach())
 

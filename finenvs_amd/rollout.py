@@ -463,6 +463,12 @@ def lstm_pack(weight_ih, weight_hh, bias_ih, bias_hh, H: int):
     return w_hh[order].contiguous(), wx
 
 
+def lstm_fragment_major(whh: torch.Tensor, H: int) -> torch.Tensor:
+    """The packed ``whh`` of ``lstm_pack`` as the streaming kernels of H >= 256 read it, on ``whh``'s device:
+    [row tile][k group][lane = (row & 31) + 32 * k half][4], one contiguous KiB per (row tile, k group)."""
+    return whh.reshape(4 * H // 32, 32, H // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(4 * H, H)
+
+
 class FusedLSTMRollout(_FusedEvaluation):
     """K env steps per launch with the LSTM actor of the reference's time-series scripts evaluated in the kernel
     (C ABI ``fe_env_rollout_lstm``):
@@ -525,8 +531,8 @@ class FusedLSTMRollout(_FusedEvaluation):
             if not bool(torch.isfinite(t.detach()).all()):  # the kernel's activations do not propagate NaN
                 raise ValueError(f"{name} has non-finite entries")
         whh, wx = lstm_pack(w_ih, w_hh, bias_ih.detach().to(**f32), bias_hh.detach().to(**f32), H)  # packed row order
-        if H > 128:  # fragment-major for the streaming kernel: [row tile][k group][lane = (row & 31) + 32 * k half][4]
-            whh = whh.reshape(4 * H // 32, 32, H // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(4 * H, H)
+        if H > 128:  # fragment-major for the streaming kernel
+            whh = lstm_fragment_major(whh, H)
         self.whh = whh.to(dev)
         self.wx = wx.to(dev)
         self.wout = weight_out.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()

@@ -21,8 +21,8 @@
  *
  * Errors (FE_ERR_ARG, message naming the function): null pointers, a null field of fe_lstm_grads, count < 0,
  * out_activation 1 (clamp: an action bound, not a trainable output), null outputs with out_activation 0, H outside
- * {32, 64, 128} (the streamed-weight forward of H >= 256 has no register-resident recurrence to mirror), an env with
- * A != 1.  No host synchronisation and no allocation in any call; count = 0 does nothing.
+ * {32, 64, 128} (the streamed-weight forward of H >= 256 has no register-resident recurrence to mirror: those sizes
+ * are fe_lstm_backward_streamed of finenvs_amd_lstm_grad_streamed.h), an env with A != 1.  No host synchronisation and no allocation in any call; count = 0 does nothing.
  */
 #ifndef FINENVS_AMD_LSTM_GRAD_H
 #define FINENVS_AMD_LSTM_GRAD_H

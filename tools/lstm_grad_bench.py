@@ -15,8 +15,10 @@ No optimizer step in any arm (it is the same in all).  Device-synchronised timin
 within one process and every figure is the median of --rounds rounds.
 
     timeout -k 10 900 python tools/lstm_grad_bench.py [--batch 256 4096 65536] [--hidden 32 64 128] [--window 4]
+    timeout -k 10 900 python tools/lstm_grad_bench.py --hidden 256 512 1024 --example-hidden 1024
 
-Prints one line per (H, B, arm) and a final JSON line (profiles/lstm_grad_bench.txt).
+Prints one line per (H, B, arm) and a final JSON line (profiles/lstm_grad_bench.txt; the large sizes:
+profiles/lstm_grad_streamed_bench.txt).
 """
 import argparse
 import copy
@@ -52,10 +54,12 @@ def timed(fn, reps=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, nargs="+", default=[256, 4096, 65536])
-    ap.add_argument("--hidden", type=int, nargs="+", default=[32, 64, 128])
+    ap.add_argument("--hidden", type=int, nargs="+", default=[32, 64, 128], choices=[32, 64, 128, 256, 512, 1024])
     ap.add_argument("--window", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--no-example", action="store_true")
+    ap.add_argument("--example-hidden", type=int, default=64, choices=[32, 64, 128, 256, 512, 1024])
+    ap.add_argument("--example-iters", type=int, default=5)
     a = ap.parse_args()
     W, N, K = a.window, 4096, 16
     prices, day_id, _ = make_series(1)
@@ -65,7 +69,8 @@ def main():
     for H in a.hidden:
         torch.manual_seed(H)
         actor, critic = LSTMHead(H, W, "tanh", device="cuda"), LSTMHead(H, W, "none", device="cuda")
-        actor_head, critic_head = FusedLSTMHead(env, actor), FusedLSTMHead(env, critic)
+        actor_head = FusedLSTMHead(env, actor, streamed=H > 128)
+        critic_head = FusedLSTMHead(env, critic, streamed=H > 128)
         t_actor, t_critic = copy.deepcopy(actor), copy.deepcopy(critic)
         log_std = torch.full((1, 1), math.log(0.5), device="cuda", requires_grad=True)
         t_log_std = log_std.detach().clone().requires_grad_(True)
@@ -136,17 +141,19 @@ def main():
         spec.loader.exec_module(example)
         modes = {"plain": {}, "fused_update": {"fused_update": True}}
         it = {k: [] for k in modes}
+        EH, iters = a.example_hidden, a.example_iters
         for m in modes.values():  # warm-up (library, kernels, allocator)
-            example.main(iters=2, quiet=True, **m)
+            example.main(iters=2, hidden=EH, quiet=True, **m)
         for _ in range(3):
             for key, m in modes.items():
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                example.main(iters=5, quiet=True, **m)
+                example.main(iters=iters, hidden=EH, quiet=True, **m)
                 torch.cuda.synchronize()
-                it[key].append((time.perf_counter() - t0) / 5)
+                it[key].append((time.perf_counter() - t0) / iters)
+        out["example_hidden"] = EH
         out["example_iteration_ms"] = {k: 1e3 * statistics.median(v) for k, v in it.items()}
-        print("example (defaults: 4096 envs, 16 steps, H 64, 2 epochs x 4 minibatches) ms per iteration:",
+        print(f"example (defaults: 4096 envs, 16 steps, 2 epochs x 4 minibatches; H {EH}) ms per iteration:",
               out["example_iteration_ms"], flush=True)
     print(json.dumps(out))
 
