@@ -8,6 +8,11 @@
   8 - 27 %).  The output layer is scaled so that ``0.5 < max|p| < 4``: unscaled, max|p| is 0.006 - 0.03 at these sizes
   and the tanh head's ``1 - y^2`` factor would never be exercised.  The last case crosses a chunk boundary with a
   ragged tail;
+* the same at the windows and K splits those cases do not reach.  Worst err / tol over kinds and tensors, measured on an
+  MI355X: W = 1 (256, 1, 33) 0.046 (d w_hh identically and exactly zero); odd W (512, 7, 257) 0.192; the reference's
+  default window (256, 390, 33) 0.178 and (1024, 390, 33) 0.082, the latter with the 256-pair minimum chunk; empty
+  trailing K splits (1024, 4, 1100) 0.829 (``ppo_critic`` b_out, a cancelling sum of the upstream gradient; every other
+  kind below 0.12) and (512, 4, 4200) 0.230;
 * values: after an in-place perturbation of all six parameters ``head(src, pos)`` is a fresh
   ``FusedLSTMRollout.from_modules(...).forward(src, pos)`` bit for bit (``refresh()`` packs fragment-major);
 * two backward calls give the same bits; ``.grad`` accumulates as torch's does; a frozen head gets nothing and launches
@@ -55,6 +60,12 @@ def _module(H, W, seed, activation, states):
     return m
 
 
+# The last two cases leave trailing K splits of the weight contraction without a chain; they must write zeros for the
+# final kernel to add.  From the rule of include/finenvs_amd_lstm_grad_streamed.h and the kernel's constants: the pass
+# holds B rounded up to 32 pairs, one MFMA chain covers 1024 (step, pair) columns, there are at most 4 / 16 / 32 splits at
+# H = 1024 / 512 / 256, and every split takes ceil(chains / splits) consecutive chains.
+#   (1024, 4, 1100): 1120 pairs x 4 steps = 4480 columns = 5 chains, 4 splits of 2: chains 0-1, 2-3, 4, none;
+#   (512, 4, 4200): 4224 x 4 = 16 896 columns = 17 chains, 16 splits of 2: nine splits hold chains, seven hold none.
 CASES = [
     (256, 4, 1, torch.float64),
     (256, 4, 31, torch.float32),
@@ -65,6 +76,12 @@ CASES = [
     (1024, 5, 257, torch.float64),
     (1024, 4, 4097, torch.float64),
     (256, 4, "chunk + 33", torch.float32),
+    (256, 1, 33, torch.float64),     # W = 1: no recurrent step at all
+    (512, 7, 257, torch.float32),    # odd W
+    (256, 390, 33, torch.float64),   # the reference's default window
+    (1024, 390, 33, torch.float32),  # the chunk is the 256-pair minimum (a full one's stash, 2.5 GB, exceeds 2 GiB)
+    (1024, 4, 1100, torch.float64),  # an empty trailing K split, see above
+    (512, 4, 4200, torch.float32),   # seven empty trailing K splits
 ]
 
 
