@@ -7,6 +7,7 @@ user code (agents are out of this repo's scope): clipped-surrogate PPO with an L
 like finenvs/agents/PPO/{PPO_agent,continuous_actor,critic}.py.
 
     python examples/ppo_lstm_fused.py [--envs 4096] [--steps 16] [--iters 5] [--hidden 64] [--window 4] [--fused-update]
+                                      [--fused-optim]
 
 What runs where:
     rollout   : FusedLSTMRollout.run(K, noise, std, trajectory)       one launch per K steps, nothing written but
@@ -17,6 +18,9 @@ What runs where:
                 --fused-update: ppo_actor_loss / ppo_critic_loss of finenvs_amd/lstm_head.py on the minibatches'
                 descriptors (fe_lstm_forward / fe_lstm_backward; fe_lstm_backward_streamed at H >= 256): nothing is
                 rendered, and the updated parameters reach the rollout kernel without a trip through the host
+                --fused-optim (implies --fused-update): FusedAdam of finenvs_amd/optim.py -- Adam and the packing of a
+                head in one launch per step (fe_net_update); the heads and their rollouts read its packed buffers and
+                its output bias on the device, so nothing is re-packed per call and refresh() has nothing to do
 """
 import argparse
 import math
@@ -32,6 +36,7 @@ from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
 from finenvs_amd.lstm_head import FusedLSTMHead, ppo_actor_loss, ppo_critic_loss  # noqa: E402
 from finenvs_amd.lstm_head import LSTMHead as TrainableLSTMHead  # noqa: E402
+from finenvs_amd.optim import FusedAdam  # noqa: E402
 from finenvs_amd.rollout import FusedLSTMRollout  # noqa: E402
 from finenvs_amd.stats import EpisodeStats  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
@@ -52,7 +57,8 @@ class LSTMHead(torch.nn.Module):
 
 
 def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatches=4, seed=0, quiet=False,
-         fused_update=False):
+         fused_update=False, fused_optim=False):
+    fused_update = fused_update or fused_optim
     torch.manual_seed(seed)
     dev = "cuda:0"
     prices, day_id, _ = synthetic.synthetic_series(12, 1, 390, 1234)
@@ -64,13 +70,21 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
     else:
         actor, critic = LSTMHead(hidden, True).to(dev), LSTMHead(hidden, False).to(dev)
     log_std = torch.nn.Parameter(torch.full((1,), math.log(0.5), device=dev))
-    opt_a = torch.optim.Adam(list(actor.parameters()) + [log_std], 3e-4)
-    opt_c = torch.optim.Adam(critic.parameters(), 3e-4)
+    if fused_optim:
+        opt_a, opt_c = FusedAdam(lr=3e-4), FusedAdam(lr=3e-4)
+        opt_a.add(actor)
+        opt_a.add_tensor(log_std)
+        opt_c.add(critic)
+    else:
+        opt_a = torch.optim.Adam(list(actor.parameters()) + [log_std], 3e-4)
+        opt_c = torch.optim.Adam(critic.parameters(), 3e-4)
     traj = TrajectoryBuffer(steps, envs, 1, states=True)
     stats = EpisodeStats(env)
     if fused_update:  # the heads train on descriptors; each owns the rollout object that runs its parameters
         streamed = {"streamed": True} if hidden > 128 else {}  # H >= 256: the chunked backward, an opt-in of the head
-        actor_head, critic_head = FusedLSTMHead(env, actor, **streamed), FusedLSTMHead(env, critic, **streamed)
+        resident_a, resident_c = ({"weights": opt_a}, {"weights": opt_c}) if fused_optim else ({}, {})
+        actor_head = FusedLSTMHead(env, actor, **streamed, **resident_a)
+        critic_head = FusedLSTMHead(env, critic, **streamed, **resident_c)
         roll, value_head = actor_head.rollout, critic_head.rollout
     else:
         roll = FusedLSTMRollout.from_modules(env, actor.lstm, actor.last)
@@ -99,11 +113,13 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
                 if fused_update:  # the same two updates on the minibatch's descriptors (16 bytes per state)
                     src, pos = traj.minibatch_descriptors(mb)
                     loss_a = ppo_actor_loss(actor_head, log_std, src, pos, f_act[mb], f_logp[mb], f_adv[mb], clip, ent_coef)
-                    opt_a.zero_grad()
+                    if not fused_optim:  # FusedAdam.step() leaves the gradients zeroed
+                        opt_a.zero_grad()
                     loss_a.backward()
                     opt_a.step()
                     loss_c = ppo_critic_loss(critic_head, src, pos, f_ret[mb])
-                    opt_c.zero_grad()
+                    if not fused_optim:
+                        opt_c.zero_grad()
                     loss_c.backward()
                     opt_c.step()
                     continue
@@ -148,8 +164,10 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=64, choices=[32, 64, 128, 256, 512, 1024])
     ap.add_argument("--window", type=int, default=4)
+    ap.add_argument("--fused-optim", action="store_true",
+                    help="with --fused-update: one launch per optimizer step, packed weights resident on the device")
     ap.add_argument("--fused-update", action="store_true",
                     help="train both heads on descriptors with the fused backward (every --hidden; the chunked "
                          "streamed-weight backward at 256 and above)")
     a = ap.parse_args()
-    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update)
+    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update, fused_optim=a.fused_optim)

@@ -24,8 +24,14 @@ where ``rsample`` drew them.  ``q`` comes from ``FusedTwinCritic.q`` with ``--fu
 fused backward into the other) and from the torch critics on the rendered states otherwise.  With all three flags a
 training step renders no observation at all: ``get_mini_batch`` is not called.
 
+With ``--fused-optim`` the parameter side is one launch per optimizer step: ``FusedAdam`` (finenvs_amd/optim.py) runs
+Adam on both critics, soft-updates both targets and writes all four packed forms in ``fe_net_update``, and another
+does the actor and the temperature.  The fused front ends read those packed buffers (``weights=``) instead of
+re-packing the modules at every call, and the actor's two output biases stay on the device.  The arithmetic is
+torch's, one f32 rounding per operation: with the same seed the losses agree with the default path up to f32 rounding.
+
     python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
-                                       [--fused-critics] [--fused-actor]
+                                       [--fused-critics] [--fused-actor] [--fused-optim]
 """
 import argparse
 import copy
@@ -40,6 +46,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.critic import CriticLSTM, FusedTwinCritic  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
+from finenvs_amd.optim import FusedAdam  # noqa: E402
 from finenvs_amd.replay import ReplayBuffer  # noqa: E402
 from finenvs_amd.sac import FusedSACRollout, SACActorLSTM  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
@@ -51,9 +58,11 @@ def soft_update(target, source, rho):
             t.mul_(1.0 - rho).add_(s, alpha=rho)
 
 
-def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
-         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False,
-         fused_critics=False, fused_actor=False):
+def iterate(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
+            days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, fused_targets=False,
+            fused_critics=False, fused_actor=False, fused_optim=False):
+    """The training loop as a generator: one log entry per iteration that trained (tools/optim_bench.py steps two of
+    these alternately)."""
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
@@ -62,15 +71,24 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
     actor = SACActorLSTM(H=hidden, W=window).to(dev)
     critic_1, critic_2 = CriticLSTM(hidden, window).to(dev), CriticLSTM(hidden, window).to(dev)
     critic_1t, critic_2t = copy.deepcopy(critic_1), copy.deepcopy(critic_2)
-    actor_opt = torch.optim.Adam(actor.parameters(), lr=lr)
-    alpha_opt = torch.optim.Adam([actor.log_alpha], lr=lr)
-    critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
-    roll = FusedSACRollout(env, actor)  # re-packs the actor's weights at every run: updates are seen right away
-    twin = FusedTwinCritic(env, critic_1t, critic_2t) if fused_targets else None  # re-packs at every call, too
-    twin_online = FusedTwinCritic(env, critic_1, critic_2) if fused_critics else None
+    if fused_optim:  # one launch per step: Adam, the soft updates and the packed forms the front ends read
+        actor_opt, critic_opt = FusedAdam(lr=lr), FusedAdam(lr=lr)
+        actor_opt.add(actor)
+        actor_opt.add_tensor(actor.log_alpha)
+        critic_opt.add(critic_1, target=critic_1t, rho=rho)
+        critic_opt.add(critic_2, target=critic_2t, rho=rho)
+        resident_a, resident_c = {"weights": actor_opt}, {"weights": critic_opt}
+    else:
+        actor_opt = torch.optim.Adam(actor.parameters(), lr=lr)
+        alpha_opt = torch.optim.Adam([actor.log_alpha], lr=lr)
+        critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
+        resident_a = resident_c = {}
+    # without weights= the front ends re-pack their modules at every call: updates are seen right away either way
+    roll = FusedSACRollout(env, actor, **resident_a)
+    twin = FusedTwinCritic(env, critic_1t, critic_2t, **resident_c) if fused_targets else None
+    twin_online = FusedTwinCritic(env, critic_1, critic_2, **resident_c) if fused_critics else None
     gen = torch.Generator(device=dev).manual_seed(seed)
     render = not (fused_critics and fused_actor)  # somebody still reads the rendered states
-    history = []
     for it in range(iterations):
         traj = TrajectoryBuffer(chunk, N, A, device=dev, states=True)
         noise = torch.randn((chunk, N, A), generator=gen, device=dev)
@@ -99,8 +117,9 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
                 critic_loss = twin_online.critic_loss(buffer, idx, y)
             else:
                 critic_loss = F.mse_loss(critic_1(s, a), y) + F.mse_loss(critic_2(s, a), y)
-            critic_opt.zero_grad()
+            critic_opt.zero_grad()  # (the actor loss's backward left values in the critics' gradients)
             critic_loss.backward()
+            # fused: the targets follow here, not after the actor's update -- the critics do not change in between
             critic_opt.step()
             if fused_critics or fused_actor:
                 slots = buffer.physical(idx)
@@ -114,21 +133,34 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
             else:
                 q = torch.min(critic_1(s, a_new), critic_2(s, a_new))
             actor_loss = -(q - actor.log_alpha.exp().detach() * mean_lp).mean()
+            alpha_loss = (-actor.log_alpha.exp() * (mean_lp + actor.target_entropy).detach()).mean()
+            if fused_optim:  # the two losses share no parameter: one step takes both (and zeroes their gradients)
+                actor_loss.backward()
+                alpha_loss.backward()
+                actor_opt.step()
+                continue
             actor_opt.zero_grad()
             actor_loss.backward()
             actor_opt.step()
-            alpha_loss = (-actor.log_alpha.exp() * (mean_lp + actor.target_entropy).detach()).mean()
             alpha_opt.zero_grad()
             alpha_loss.backward()
             alpha_opt.step()
             soft_update(critic_1t, critic_1, rho)
             soft_update(critic_2t, critic_2, rho)
-        entry = {"iteration": it, "critic_loss": critic_loss.item(), "actor_loss": actor_loss.item(),
-                 "alpha_loss": alpha_loss.item(), "alpha": float(actor.log_alpha.detach().exp()), "buffer_size": buffer.size()}
+        yield {"iteration": it, "critic_loss": critic_loss.item(), "actor_loss": actor_loss.item(),
+               "alpha_loss": alpha_loss.item(), "alpha": float(actor.log_alpha.detach().exp()), "buffer_size": buffer.size()}
+
+
+def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
+         days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False,
+         fused_critics=False, fused_actor=False, fused_optim=False):
+    history = []
+    for entry in iterate(num_envs, window, hidden, iterations, chunk, batch, updates_per_chunk, max_size, days, bars, gamma,
+                         rho, lr, reward_scale, seed, fused_targets, fused_critics, fused_actor, fused_optim):
         history.append(entry)
-        if not quiet and it % 10 == 0:
-            print(f"iter {it:5d}  buffer {buffer.size():8d}  critic {entry['critic_loss']:.4g}  actor {entry['actor_loss']:.4g}  "
-                  f"alpha {entry['alpha']:.4g}")
+        if not quiet and entry["iteration"] % 10 == 0:
+            print(f"iter {entry['iteration']:5d}  buffer {entry['buffer_size']:8d}  critic {entry['critic_loss']:.4g}  "
+                  f"actor {entry['actor_loss']:.4g}  alpha {entry['alpha']:.4g}")
     return history
 
 
@@ -141,6 +173,7 @@ if __name__ == "__main__":
     ap.add_argument("--fused-targets", action="store_true")
     ap.add_argument("--fused-critics", action="store_true")
     ap.add_argument("--fused-actor", action="store_true")
+    ap.add_argument("--fused-optim", action="store_true")
     a = ap.parse_args()
     main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
-         fused_critics=a.fused_critics, fused_actor=a.fused_actor)
+         fused_critics=a.fused_critics, fused_actor=a.fused_actor, fused_optim=a.fused_optim)

@@ -198,6 +198,42 @@ LSTM_STREAMED_GRAD_SIGNATURES = {
                                             C.POINTER(FeLstmGrads), _vp]),
 }
 
+
+# include/finenvs_amd_optim.h: Adam, soft update and packing in one launch; the device-bias siblings (finenvs_amd/optim.py)
+class FeOptimSegment(C.Structure):
+    """struct fe_optim_segment of include/finenvs_amd_optim.h."""
+
+    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("target", _vp),
+                ("param2", _vp), ("grad2", _vp), ("exp_avg2", _vp), ("exp_avg_sq2", _vp), ("target2", _vp),
+                ("packed", _vp), ("packed_target", _vp), ("numel", _i64), ("first_block", _i64),
+                ("kind", _i32), ("H", _i32), ("cols", _i32), ("reserved", _i32),
+                ("one_minus_rho", C.c_float), ("rho", C.c_float)]
+
+
+class FeOptimDesc(C.Structure):
+    """struct fe_optim_desc of include/finenvs_amd_optim.h."""
+
+    _fields_ = [("segments", _vp), ("state", _vp), ("num_segments", _i32), ("mode", _i32), ("num_blocks", _i64),
+                ("soft_update", _i32), ("zero_grad", _i32), ("beta1", C.c_double), ("beta2", C.c_double), ("lr", C.c_double),
+                ("one_minus_beta1", C.c_float), ("beta2_f32", C.c_float), ("one_minus_beta2", C.c_float), ("eps", C.c_float)]
+
+
+OPTIM_SIGNATURES = {
+    "fe_net_update": (C.c_int, [C.POINTER(FeOptimDesc), _vp]),
+    # the by-value entries' siblings: the same argument lists with every C.c_float bias a device pointer
+    "fe_lstm_forward_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "fe_env_rollout_lstm_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "fe_env_rollout_lstm_split_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_env_rollout_sac_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_sac_forward_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "fe_sac_backward_p": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, C.POINTER(FeSacGrads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -224,7 +260,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
-                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES}.items():
+                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **OPTIM_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

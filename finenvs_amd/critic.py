@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .rollout import lstm_pack, lstm_row_order
+from .rollout import lstm_pack, lstm_row_order_on
 
 CRITIC_HIDDEN_SIZES = (32, 64, 128)
 
@@ -82,7 +82,7 @@ def pack_critic_weights(critic: nn.Module) -> Dict[str, torch.Tensor]:
     lstm = critic.lstm
     w_ih = lstm.weight_ih_l0.detach().float()
     whh, wx = lstm_pack(w_ih[:, :5], lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, H)
-    wx[:, 6] = w_ih[lstm_row_order(H).to(w_ih.device), 5]
+    wx[:, 6] = w_ih[lstm_row_order_on(H, w_ih.device), 5]
     last = critic.last_layer[0]
     return {
         "whh": whh, "wx": wx,
@@ -110,7 +110,7 @@ def empty_packed_grads(H: int, device) -> Dict[str, torch.Tensor]:
 def packed_grads_to_torch(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch.Tensor]:
     """fe_twin_q_backward's gradients (rows of the 4H-row tensors in ``lstm_row_order``) in the layout and row order of
     the critic's parameters (``critic_parameters``)."""
-    order = lstm_row_order(H).to(g["w_hh"].device)
+    order = lstm_row_order_on(H, g["w_hh"].device)
     inv = torch.empty_like(order)
     inv[order] = torch.arange(4 * H, device=order.device)
     return {"w_ih": g["w_ih"][inv], "w_hh": g["w_hh"][inv], "b_ih": g["b_ih"][inv], "b_hh": g["b_hh"][inv],
@@ -119,7 +119,7 @@ def packed_grads_to_torch(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch
 
 def torch_grads_to_packed(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch.Tensor]:
     """The inverse of ``packed_grads_to_torch``."""
-    order = lstm_row_order(H).to(g["w_hh"].device)
+    order = lstm_row_order_on(H, g["w_hh"].device)
     return {"w_ih": g["w_ih"][order], "w_hh": g["w_hh"][order], "b_ih": g["b_ih"][order], "b_hh": g["b_hh"][order],
             "w_out": g["w_out"].reshape(H), "b_out": g["b_out"].reshape(1)}
 
@@ -133,12 +133,15 @@ class _TwinQ(torch.autograd.Function):
         q1, q2 = fused.forward(src, pos, actions.detach())
         ctx.set_materialize_grads(False)  # an output nobody used gets None, not zeros: its critic does not run
         ctx.fused, ctx.packed, ctx.action_shape = fused, fused._packed, actions.shape
+        ctx.version = None if fused.weights is None else fused.weights.version
         ctx.save_for_backward(src, pos, actions.detach().reshape(-1).contiguous())
         return q1, q2
 
     @staticmethod
     def backward(ctx, g1, g2):
         fused = ctx.fused
+        if fused.weights is not None:
+            fused.weights.check_version(ctx.version)
         src, pos, act = ctx.saved_tensors
         env, H, B = fused.env, fused.H, int(src.numel())
         need = ctx.needs_input_grad
@@ -179,9 +182,14 @@ class FusedTwinCritic:
     """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
 
     The critics' parameters are re-packed on the device at every call (a few small launches, no host round trip), so an
-    optimizer step or a soft update is seen by the next call.  Both critics must live on the env's device."""
+    optimizer step or a soft update is seen by the next call.  Both critics must live on the env's device.
 
-    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module):
+    ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that both critics are registered with, as networks or as
+    targets.  Nothing is packed per call then: every launch reads that optimizer's packed buffers, which its ``step()``
+    keeps current.  Those buffers are rewritten in place: a ``weights.step()`` or ``weights.repack()`` between a
+    forward and its ``backward()`` is a RuntimeError."""
+
+    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module, weights=None):
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused twin critic runs one asset (the env has {env.num_assets}): the reference's critic "
                              "for A > 1 is one nn.LSTM(5A + A, H) over the whole env's window, not a per-(env, asset) pair "
@@ -191,6 +199,9 @@ class FusedTwinCritic:
             raise ValueError(f"the two critics must have the same hidden size (got {H1} and {H2})")
         self.env, self.critic_1, self.critic_2, self.H = env, critic_1, critic_2, H1
         self._check_devices()
+        self.weights = weights
+        if weights is not None:
+            weights.packed(critic_1), weights.packed(critic_2)  # ValueError if a critic is not registered with it
         self._lr32 = getattr(env, "_log_return_f32", None)
         if self._lr32 is None:
             self._lr32 = env.log_return_environments.float().contiguous()
@@ -204,7 +215,10 @@ class FusedTwinCritic:
 
     def _weights(self):
         self._check_devices()
-        w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
+        if self.weights is not None:
+            w = [self.weights.packed(c) for c in (self.critic_1, self.critic_2)]
+        else:
+            w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
         self._packed = w  # kept alive until the launch has been queued
         return [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
                 for x in w]

@@ -70,6 +70,7 @@
 #include "finenvs_amd_sac_grad.h"
 #include "finenvs_amd_lstm_grad.h"
 #include "finenvs_amd_lstm_grad_streamed.h"
+#include "finenvs_amd_optim.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -84,6 +85,7 @@
 #include "fe_sac_grad_kernels.h"
 #include "fe_lstm_grad_kernels.h"
 #include "fe_lstm_grad_streamed_kernels.h"
+#include "fe_optim_kernels.h"
 
 namespace {
 
@@ -924,10 +926,13 @@ static int launch_sac(fe_env *env, SacArgs &s, int64_t count, const char *who, v
     return launch_resident(env, kern, lds, p, &s, "SAC kernel", stream);
 }
 
-int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                        float bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
-                        const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
-                        int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+// The *_impl functions serve an entry that takes its output bias by value and its sibling of
+// include/finenvs_amd_optim.h that reads it through a device pointer (bout_p etc. non-null).
+static int rollout_lstm_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                             float bout, const float *bout_p, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src,
+                             double *obs_pos, const float *noise, float std, float *actions_out, float *means_out,
+                             double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
+                             void *stream) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm: states_src_out and states_pos_out go together");
     if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "fe_env_rollout_lstm: std must be >= 0 when noise is given");
@@ -937,10 +942,19 @@ int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, 
     if (int rc = require_bound(env, "fe_env_rollout_lstm")) return rc;
     LstmArgs r;
     r.lr32 = logret_f32; r.whh = whh; r.wx = wx; r.wout = wout; r.bout = bout; r.H = H; r.out_act = out_activation; r.K = K;
+    r.bout_p = bout_p;
     r.obs_src = obs_src; r.obs_pos = obs_pos; r.actions_out = actions_out; r.rew_out = rewards_out; r.done_out = dones_out;
     r.noise = noise; r.std = std; r.means_out = means_out; r.traj_src = states_src_out; r.traj_pos = states_pos_out;
     r.forward_only = 0;
     return launch_lstm(env, r, env->cfg.N, "fe_env_rollout_lstm", stream);
+}
+
+int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                        float bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                        const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                        int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    return rollout_lstm_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, K, obs_src, obs_pos, noise, std,
+                             actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream);
 }
 
 int64_t fe_lstm_split_workspace_floats(int32_t H, int64_t pairs) {
@@ -948,11 +962,11 @@ int64_t fe_lstm_split_workspace_floats(int32_t H, int64_t pairs) {
     return 3 * ((pairs + 31) / 32) * (int64_t)H * 32;  // h (two buffers) + c, fragment-major: [column tile][H/8][64][4]
 }
 
-int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                              float bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
-                              const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
-                              int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, float *workspace,
-                              void *stream) {
+static int rollout_lstm_split_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx,
+                                   const float *wout, float bout, const float *bout_p, int32_t H, int32_t out_activation,
+                                   int32_t K, int64_t *obs_src, double *obs_pos, const float *noise, float std,
+                                   float *actions_out, float *means_out, double *rewards_out, int32_t *dones_out,
+                                   int64_t *states_src_out, double *states_pos_out, float *workspace, void *stream) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: states_src_out and states_pos_out go together");
     if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: std must be >= 0 when noise is given");
@@ -977,7 +991,7 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
     const void *fk = with_bool(single, [](auto S) { return (const void *)fe_lstm_split_finish_kernel<decltype(S)::value>; });
     if (int rc = prepare_big_lds(env->device, fk, lds, "fe_env_rollout_lstm_split")) return rc;
     LstmSplitArgs s;
-    s.a.lr32 = logret_f32; s.a.whh = whh; s.a.wx = wx; s.a.wout = wout; s.a.bout = bout; s.a.H = H; s.a.out_act = out_activation;
+    s.a.lr32 = logret_f32; s.a.whh = whh; s.a.wx = wx; s.a.wout = wout; s.a.bout = bout; s.a.bout_p = bout_p; s.a.H = H; s.a.out_act = out_activation;
     s.a.K = 1; s.a.obs_src = obs_src; s.a.obs_pos = obs_pos; s.a.std = std; s.a.traj_src = states_src_out; s.a.traj_pos = states_pos_out;
     s.a.forward_only = 0;
     s.hbuf = workspace; s.cbuf = workspace + 2 * CT * (int64_t)H * 32; s.pairs = NA;
@@ -1014,9 +1028,19 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
     return launched("fe_env_rollout_lstm_split");
 }
 
-int fe_lstm_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout, float bout,
-                    int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
-                    float *out, void *stream) {
+int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                              float bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                              const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                              int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, float *workspace,
+                              void *stream) {
+    return rollout_lstm_split_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, K, obs_src, obs_pos,
+                                   noise, std, actions_out, means_out, rewards_out, dones_out, states_src_out,
+                                   states_pos_out, workspace, stream);
+}
+
+static int lstm_forward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                             float bout, const float *bout_p, int32_t H, int32_t out_activation, const int64_t *obs_src,
+                             const double *obs_pos, int64_t count, float *out, void *stream) {
     if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || !out || count < 0)
         return fail(FE_ERR_ARG, "fe_lstm_forward: bad argument");
     if (out_activation < 0 || out_activation > 2)
@@ -1024,11 +1048,19 @@ int fe_lstm_forward(fe_env *env, const float *logret_f32, const float *whh, cons
     if (count == 0) return FE_OK;
     LstmArgs r;
     r.lr32 = logret_f32; r.whh = whh; r.wx = wx; r.wout = wout; r.bout = bout; r.H = H; r.out_act = out_activation; r.K = 1;
+    r.bout_p = bout_p;
     r.obs_src = const_cast<int64_t *>(obs_src); r.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
     r.actions_out = out; r.rew_out = nullptr; r.done_out = nullptr;
     r.noise = nullptr; r.std = 0.0f; r.means_out = nullptr; r.traj_src = nullptr; r.traj_pos = nullptr;
     r.forward_only = 1;
     return launch_lstm(env, r, count, "fe_lstm_forward", stream);
+}
+
+int fe_lstm_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout, float bout,
+                    int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                    float *out, void *stream) {
+    return lstm_forward_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, obs_src, obs_pos, count, out,
+                             stream);
 }
 
 int fe_lstm_activations(const float *x, float *sigmoid_out, float *tanh_out, int64_t n, void *stream) {
@@ -1325,17 +1357,19 @@ int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int6
 
 // ---- include/finenvs_amd_sac.h: the SAC actor's head on the LSTM recurrence ----
 static void sac_args(SacArgs &s, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
-                     const float *wmu, float bmu, const float *wstd, float bstd, int32_t H) {
+                     const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p, const float *bstd_p,
+                     int32_t H) {
+    s.bmu_p = bmu_p; s.bstd_p = bstd_p;
     s.l.lr32 = logret_f32; s.l.whh = whh; s.l.wx = wx; s.l.wout = nullptr; s.l.bout = 0.0f; s.l.H = H; s.l.out_act = 0;
     s.l.std = 0.0f;
     s.wl = wl; s.bl = bl; s.wmu = wmu; s.bmu = bmu; s.wstd = wstd; s.bstd = bstd;
 }
 
-int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                       const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, int32_t K,
-                       int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out, float *means_out,
-                       float *stds_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
-                       double *states_pos_out, void *stream) {
+static int rollout_sac_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                            const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p,
+                            const float *bstd_p, int32_t H, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
+                            float *actions_out, float *means_out, float *stds_out, double *rewards_out, int32_t *dones_out,
+                            int64_t *states_src_out, double *states_pos_out, void *stream) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "fe_env_rollout_sac: states_src_out and states_pos_out go together");
     if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || !rewards_out ||
@@ -1343,7 +1377,7 @@ int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, c
         return fail(FE_ERR_ARG, "fe_env_rollout_sac: bad argument");
     if (int rc = require_bound(env, "fe_env_rollout_sac")) return rc;
     SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, H);
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, bmu_p, bstd_p, H);
     s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
     s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
     s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
@@ -1351,23 +1385,42 @@ int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, c
     return launch_sac(env, s, env->cfg.N, "fe_env_rollout_sac", stream);
 }
 
-int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
-                   const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, const int64_t *obs_src,
-                   const double *obs_pos, int64_t count, const float *noise, float *actions_out, float *log_probs_out,
-                   float *means_out, float *stds_out, void *stream) {
+int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                       const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, int32_t K,
+                       int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out, float *means_out,
+                       float *stds_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
+                       double *states_pos_out, void *stream) {
+    return rollout_sac_impl(env, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, nullptr, nullptr, H, K, obs_src, obs_pos,
+                            noise, actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out,
+                            stream);
+}
+
+static int sac_forward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                            const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p,
+                            const float *bstd_p, int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                            const float *noise, float *actions_out, float *log_probs_out, float *means_out, float *stds_out,
+                            void *stream) {
     if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0)
         return fail(FE_ERR_ARG, "fe_sac_forward: bad argument");
     if (!noise && (actions_out || log_probs_out))
         return fail(FE_ERR_ARG, "fe_sac_forward: actions_out and log_probs_out need noise");
     if (count == 0) return FE_OK;
     SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, H);
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, bmu_p, bstd_p, H);
     s.l.K = 1;
     s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
     s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
     s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
     s.stds_out = stds_out; s.logp_out = log_probs_out;
     return launch_sac(env, s, count, "fe_sac_forward", stream);
+}
+
+int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
+                   const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, const int64_t *obs_src,
+                   const double *obs_pos, int64_t count, const float *noise, float *actions_out, float *log_probs_out,
+                   float *means_out, float *stds_out, void *stream) {
+    return sac_forward_impl(env, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, nullptr, nullptr, H, obs_src, obs_pos,
+                            count, noise, actions_out, log_probs_out, means_out, stds_out, stream);
 }
 
 // ---- include/finenvs_amd_critic.h: the twin LSTM critics and their Bellman targets ----
@@ -1559,13 +1612,12 @@ int64_t fe_sac_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
     return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + sac_grad_stash_floats(H, W));
 }
 
-int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                    const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H,
-                    const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
-                    const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
-                    float *workspace, const fe_sac_grads *grads, void *stream) {
+static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                             const float *bl, const float *wmu, const float *wstd, float bstd, const float *bstd_p,
+                             int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                             const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                             float *workspace, const fe_sac_grads *grads, void *stream) {
     static const char *who = "fe_sac_backward";
-    (void)bmu;  // the gradient does not depend on it
     if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0 || !noise ||
         !actions || !stds || (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih || !grads->w_hh ||
         !grads->b_ih || !grads->b_hh || !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu || !grads->w_std ||
@@ -1588,7 +1640,7 @@ int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, cons
     SacGradArgs g;
     memset(&g, 0, sizeof(g));
     g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
-    g.whh = whh; g.wx = wx; g.wl = wl; g.bl = bl; g.wmu = wmu; g.wstd = wstd; g.bstd = bstd;
+    g.whh = whh; g.wx = wx; g.wl = wl; g.bl = bl; g.wmu = wmu; g.wstd = wstd; g.bstd = bstd; g.bstd_p = bstd_p;
     g.noise = noise; g.actions = actions; g.stds = stds; g.d_actions = d_actions; g.d_log_probs = d_log_probs;
     g.wt = workspace;
     g.part = g.wt + sac_grad_wt_floats(H);
@@ -1616,6 +1668,15 @@ int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, cons
     return launched("fe_sac_backward: reduction");
 }
 
+int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                    const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H,
+                    const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                    const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                    float *workspace, const fe_sac_grads *grads, void *stream) {
+    (void)bmu;  // the gradient does not depend on it
+    return sac_backward_impl(env, logret_f32, whh, wx, wl, bl, wmu, wstd, bstd, nullptr, H, obs_src, obs_pos, count, noise,
+                             actions, stds, d_actions, d_log_probs, workspace, grads, stream);
+}
 
 // ---- include/finenvs_amd_lstm_grad.h: the one-output LSTM head's backward pass ----
 // Workspace: [W_hh^T][partials of every workgroup][stash of every workgroup].
@@ -1787,6 +1848,89 @@ int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float 
         if (int rc = launched("fe_lstm_backward_streamed: final write")) return rc;
     }
     return FE_OK;
+}
+
+// ---- include/finenvs_amd_optim.h: the entries above with their output biases in device memory ----
+int fe_lstm_forward_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                      const float *bout, int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
+                      int64_t count, float *out, void *stream) {
+    if (!bout) return fail(FE_ERR_ARG, "fe_lstm_forward_p: bad argument");
+    return lstm_forward_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, obs_src, obs_pos, count, out,
+                             stream);
+}
+
+int fe_env_rollout_lstm_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                          const float *bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src,
+                          double *obs_pos, const float *noise, float std, float *actions_out, float *means_out,
+                          double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
+                          void *stream) {
+    if (!bout) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_p: bad argument");
+    return rollout_lstm_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, K, obs_src, obs_pos, noise, std,
+                             actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream);
+}
+
+int fe_env_rollout_lstm_split_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                                const float *bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src,
+                                double *obs_pos, const float *noise, float std, float *actions_out, float *means_out,
+                                double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
+                                float *workspace, void *stream) {
+    if (!bout) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split_p: bad argument");
+    return rollout_lstm_split_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, K, obs_src, obs_pos, noise,
+                                   std, actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out,
+                                   workspace, stream);
+}
+
+int fe_env_rollout_sac_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                         const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd,
+                         int32_t H, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out,
+                         float *means_out, float *stds_out, double *rewards_out, int32_t *dones_out,
+                         int64_t *states_src_out, double *states_pos_out, void *stream) {
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_env_rollout_sac_p: bad argument");
+    return rollout_sac_impl(env, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H, K, obs_src, obs_pos, noise,
+                            actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out,
+                            stream);
+}
+
+int fe_sac_forward_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                     const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd, int32_t H,
+                     const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise, float *actions_out,
+                     float *log_probs_out, float *means_out, float *stds_out, void *stream) {
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_sac_forward_p: bad argument");
+    return sac_forward_impl(env, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H, obs_src, obs_pos, count,
+                            noise, actions_out, log_probs_out, means_out, stds_out, stream);
+}
+
+int fe_sac_backward_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                      const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd, int32_t H,
+                      const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                      const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                      float *workspace, const fe_sac_grads *grads, void *stream) {
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_sac_backward_p: bad argument");
+    return sac_backward_impl(env, logret_f32, whh, wx, wl, bl, wmu, wstd, 0.0f, bstd, H, obs_src, obs_pos, count, noise,
+                             actions, stds, d_actions, d_log_probs, workspace, grads, stream);
+}
+
+// ---- include/finenvs_amd_optim.h: Adam, the soft update and the packing of every registered network, one launch ----
+int fe_net_update(const fe_optim_desc *desc, void *stream) {
+    if (!desc || !desc->segments || !desc->state || desc->num_segments < 1 || desc->num_blocks < 1 ||
+        desc->num_blocks > 0x7fffffffll)
+        return fail(FE_ERR_ARG, "fe_net_update: bad argument");
+    if (desc->mode != FE_OPTIM_STEP && desc->mode != FE_OPTIM_PACK && desc->mode != FE_OPTIM_ZERO_GRAD)
+        return fail(FE_ERR_ARG, "fe_net_update: mode must be FE_OPTIM_STEP, FE_OPTIM_PACK or FE_OPTIM_ZERO_GRAD (got %d)",
+                    (int)desc->mode);
+    if (desc->mode == FE_OPTIM_STEP &&
+        !(desc->beta1 >= 0.0 && desc->beta1 < 1.0 && desc->beta2 >= 0.0 && desc->beta2 < 1.0 && desc->lr >= 0.0 &&
+          desc->eps >= 0.0f))
+        return fail(FE_ERR_ARG, "fe_net_update: lr and eps must be >= 0 and the betas in [0, 1)");
+    DeviceGuard guard(device_of(desc->segments));
+    if (int rc = guard.status("fe_net_update: the segment table is not device memory")) return rc;
+    OptimArgs a;
+    a.seg = desc->segments; a.st = desc->state; a.num_segments = desc->num_segments; a.mode = desc->mode;
+    a.soft_update = desc->soft_update; a.zero_grad = desc->zero_grad;
+    a.beta1 = desc->beta1; a.beta2 = desc->beta2; a.lr = desc->lr;
+    a.omb1 = desc->one_minus_beta1; a.b2 = desc->beta2_f32; a.omb2 = desc->one_minus_beta2; a.eps = desc->eps;
+    hipLaunchKernelGGL(fe_net_update_kernel, dim3((unsigned)desc->num_blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return launched("fe_net_update");
 }
 
 }  // extern "C"

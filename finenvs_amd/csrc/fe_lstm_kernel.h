@@ -50,6 +50,7 @@ struct LstmArgs {
     int64_t *traj_src;   // (K + 1, N) or null: descriptors of the state the policy sees at every step (+ the last one)
     double *traj_pos;    // (K + 1, N*A)
     int32_t forward_only;  // fe_lstm_forward: evaluate the head on p.N given descriptors, no env step (K = 1, actions_out = the outputs)
+    const float *bout_p = nullptr;  // (1) on the device, or null: the output bias of the *_p entries, read instead of bout
 };
 
 template <int NT> struct LstmGeom {
@@ -101,6 +102,7 @@ struct SacArgs {
     float bmu, bstd;
     float *stds_out;    // (K, N*A) or null: softplus(std_layer(z))
     float *logp_out;    // forward only, with noise: (N*A) log_prob of tanh(u), or null
+    const float *bmu_p = nullptr, *bstd_p = nullptr;  // (1) each on the device, or null: read instead of bmu / bstd (*_p entries)
 };
 
 template <int NT> constexpr bool sac_wl_in_lds() { return NT != 2; }
@@ -318,7 +320,7 @@ __global__ __launch_bounds__(kLstmBlock, 2) void fe_rollout_lstm_big_kernel(cons
             float act = 0.0f;
             if (active) {
                 const float *hl = s_h + (size_t)(e * A + a) * HP;
-                float o = r.bout;
+                float o = r.bout_p ? *r.bout_p : r.bout;
 #pragma unroll 8
                 for (int u = 0; u < H; ++u) o = fmaf(s_wout[u], hl[u], o);
                 act = r.out_act == 0 ? lstm_tanh(o) : (r.out_act == 2 ? o : (o < -1.0f ? -1.0f : (o > 1.0f ? 1.0f : o)));
@@ -532,7 +534,7 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_split_finish_kernel(const Para
                 if (a == 0) r.traj_src[n] = r.obs_src[n];
             }
             const float4 *hp = s_hq + (size_t)(e * A + a) * (2 * NG);  // this pair's h_W, units ascending (staged above)
-            float o = r.bout;
+            float o = r.bout_p ? *r.bout_p : r.bout;
 #pragma unroll 4
             for (int g = 0; g < NG; ++g) {  // units 8g + 4 half + c
                 const float4 h0 = hp[2 * g], h1 = hp[2 * g + 1];

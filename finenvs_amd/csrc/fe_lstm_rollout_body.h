@@ -48,7 +48,7 @@
         }
         // the head's scalars and output pointers wait in LDS: as kernel arguments they would occupy SGPRs for the whole
         // launch, and the recurrence has none to spare (its SGPR spills cost VGPRs)
-        if (tid == 0) *reinterpret_cast<SacHeadLds *>(s_wout + sac_head_lds_offset(H)) = {hd.stds_out, hd.logp_out, hd.bmu, hd.bstd};
+        if (tid == 0) *reinterpret_cast<SacHeadLds *>(s_wout + sac_head_lds_offset(H)) = {hd.stds_out, hd.logp_out, hd.bmu_p ? *hd.bmu_p : hd.bmu, hd.bstd_p ? *hd.bstd_p : hd.bstd};
     }
 #endif
     // this wavefront's slice of the weights: A fragments, lane (row = lane & 31, k half = lane >> 5)
@@ -283,7 +283,7 @@
             // ---- output layer: the pair's accounting lane reduces its last hidden state ----
             if (active) {
                 const float *hl = s_h + (size_t)((W - 1) & 1) * G::SP * HP + (size_t)(e * A + a) * HP;
-                float o = r.bout;
+                float o = r.bout_p ? *r.bout_p : r.bout;
 #pragma unroll 8
                 for (int u = 0; u < H; ++u) o = fmaf(s_wout[u], hl[u], o);
                 act = r.out_act == 0 ? lstm_tanh(o) : (r.out_act == 2 ? o : (o < -1.0f ? -1.0f : (o > 1.0f ? 1.0f : o)));

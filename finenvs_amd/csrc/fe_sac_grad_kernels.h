@@ -58,6 +58,7 @@ struct SacGradArgs {
     int32_t W;
     // fe_sac_grad_reduce_kernel's outputs, torch row order and layout (include/finenvs_amd_sac_grad.h)
     float *g_wih, *g_whh, *g_bih, *g_bhh, *g_wl, *g_bl, *g_wmu, *g_bmu, *g_wstd, *g_bstd;
+    const float *bstd_p;  // (1) on the device, or null: read instead of bstd (fe_sac_backward_p)
 };
 
 // W_hh^T and W_l^T from the packed whh and the fragment-major wl (one thread per element)
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(kSacGradBlock) void fe_sac_grad_kernel(const SacGra
         // ---- the head's backward, one lane per pair (SAC/actor.py:51-61 differentiated) ----
         if (tid < 32) {
             const float *zr = zb + tid * HPF;
-            float q = g.bstd;
+            float q = g.bstd_p ? *g.bstd_p : g.bstd;
 #pragma unroll 4
             for (int u = 0; u < H; ++u) q = fmaf(s_wstd[u], zr[u], q);
             const float om = 1.0f - av * av;

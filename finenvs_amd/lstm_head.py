@@ -104,6 +104,7 @@ class _HeadValue(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         # the packed weights forward() ran with: backward packs nothing again and makes no copy to the host
         ctx.head, ctx.packed = head, (roll.whh, roll.wx, roll.wout)
+        ctx.version = None if head.weights is None else head.weights.version
         ctx.save_for_backward(src, pos, out)
         return out
 
@@ -124,6 +125,8 @@ class _HeadValue(torch.autograd.Function):
             floats = env._lib.fe_lstm_streamed_grad_workspace_floats if streamed else env._lib.fe_lstm_grad_workspace_floats
             ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
             whh, wx, wout = ctx.packed
+            if head.weights is not None:
+                head.weights.check_version(ctx.version)
             lg = _lib.FeLstmGrads(*(g.data_ptr() for g in grads))
             backward = env._lib.fe_lstm_backward_streamed if streamed else env._lib.fe_lstm_backward
             _lib.check(backward(
@@ -153,16 +156,29 @@ class FusedLSTMHead:
     ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent weights stream from L2.  It is an
     opt-in because that backward is several launches per LSTM time step and its workspace grows with the batch up to
     ``fe_lstm_streamed_grad_chunk_pairs`` pairs (2 GiB of activations), unlike the bounded one of H <= 128; H <= 128
-    runs the register-resident way either way."""
+    runs the register-resident way either way.
 
-    def __init__(self, env, module: nn.Module, streamed: bool = False):
+    ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that ``module`` is registered with, as a network or as a target.
+    The head and its rollout then read that optimizer's packed buffers and its output bias on the device: nothing is
+    packed per call, nothing is copied to the host, and ``refresh()`` does nothing -- ``weights.step()`` has already
+    written what the next call and the next ``rollout.run`` read.  Those buffers are rewritten in place, so a
+    ``weights.step()`` or ``weights.repack()`` between a forward and its ``backward()`` is a RuntimeError (torch's
+    version check for the same mistake); and ``self.rollout.set_weights(...)`` takes the rollout off the optimizer's
+    buffers, output bias included, until a new head is built."""
+
+    def __init__(self, env, module: nn.Module, streamed: bool = False, weights=None):
         self.H, self.output_activation = check_head(module, streamed)
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused LSTM head trains one asset (the env has {env.num_assets}), as the fused twin "
                              "critic does")
         self.env, self.module = env, module
         self._check_parameters()
+        self.weights = weights
+        packed = weights.packed(module) if weights is not None else None  # ValueError if the module is not registered
         self.rollout = FusedLSTMRollout.from_modules(env, module.lstm, module.last_layer[0], self.output_activation)
+        if packed is not None:
+            roll = self.rollout
+            roll.whh, roll.wx, roll.wout, roll.bout_dev = packed["whh"], packed["wx"], packed["wout"], packed["bout"]
 
     def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
         params = head_parameters(self.module)
@@ -174,7 +190,10 @@ class FusedLSTMHead:
 
     def refresh(self) -> None:
         """The module's current parameters into ``self.rollout``, packed on the device (``lstm_pack``).  One 4-byte copy
-        of the output bias goes to the host, ordered after any pending update: ``fe_lstm_forward`` takes it by value."""
+        of the output bias goes to the host, ordered after any pending update: ``fe_lstm_forward`` takes it by value.
+        With ``weights=`` nothing happens: the rollout reads the optimizer's buffers."""
+        if self.weights is not None:
+            return
         w_ih, w_hh, b_ih, b_hh, w_out, b_out = self._check_parameters()
         roll = self.rollout
         roll.whh, roll.wx = lstm_pack(w_ih, w_hh, b_ih, b_hh, self.H)

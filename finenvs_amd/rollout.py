@@ -450,11 +450,24 @@ def lstm_row_order(H: int) -> torch.Tensor:
     return gate * H + 8 * mt + 4 * half + b
 
 
+_ROW_ORDER_ON_DEVICE = {}
+
+
+def lstm_row_order_on(H: int, device) -> torch.Tensor:
+    """``lstm_row_order(H)`` on ``device``, copied there once: a copy from pageable host memory at every call would
+    stop the host until the device has caught up."""
+    key = (int(H), str(torch.device(device)))
+    order = _ROW_ORDER_ON_DEVICE.get(key)
+    if order is None:
+        order = _ROW_ORDER_ON_DEVICE[key] = lstm_row_order(H).to(device)
+    return order
+
+
 def lstm_pack(weight_ih, weight_hh, bias_ih, bias_hh, H: int):
     """``nn.LSTM``'s parameters as the register-resident kernels read them: (whh (4H, H), wx (4H, 8)) f32 on the
     parameters' device, rows in ``lstm_row_order``; wx = [w_ih (5) | b_ih + b_hh | 0 | 0]."""
     dev = weight_hh.device
-    order = lstm_row_order(H).to(dev)
+    order = lstm_row_order_on(H, dev)
     w_ih, w_hh = weight_ih.detach().float(), weight_hh.detach().float()
     bias = bias_ih.detach().float().reshape(4 * H) + bias_hh.detach().float().reshape(4 * H)  # one f32 add
     wx = torch.zeros((4 * H, 8), dtype=torch.float32, device=dev)
@@ -506,6 +519,7 @@ class FusedLSTMRollout(_FusedEvaluation):
             raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
         self.env, self.H, self.out_act = env, H, self.OUTPUT_ACTIVATIONS[output_activation]
         self.split, self._workspace = None, None
+        self.bout_dev = None  # (1) f32 on the device: read instead of ``bout`` (a FusedAdam's resident output bias)
         dev = env._dev
         self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
@@ -537,6 +551,7 @@ class FusedLSTMRollout(_FusedEvaluation):
         self.wx = wx.to(dev)
         self.wout = weight_out.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
         self.bout = float(bias_out)
+        self.bout_dev = None  # the caller's weights replace a FusedAdam's resident ones, the output bias included
 
     def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None,
                 check: bool = False) -> torch.Tensor:
@@ -559,8 +574,11 @@ class FusedLSTMRollout(_FusedEvaluation):
         elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
             raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
         if B:
-            _lib.check(env._lib.fe_lstm_forward(
-                env._handle, self._lr32.data_ptr(), self.whh.data_ptr(), self.wx.data_ptr(), self.wout.data_ptr(), self.bout,
+            resident = self.bout_dev is not None  # the bias through a device pointer: no value from the host
+            fwd = env._lib.fe_lstm_forward_p if resident else env._lib.fe_lstm_forward
+            _lib.check(fwd(
+                env._handle, self._lr32.data_ptr(), self.whh.data_ptr(), self.wx.data_ptr(), self.wout.data_ptr(),
+                self.bout_dev.data_ptr() if resident else self.bout,
                 self.H, self.out_act, src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), env._stream()))
         return out
 
@@ -603,8 +621,9 @@ class FusedLSTMRollout(_FusedEvaluation):
                 raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
             noise = noise.contiguous()
         self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
-        args = (env._handle, self._lr32.data_ptr(), self.whh.data_ptr(), self.wx.data_ptr(), self.wout.data_ptr(), self.bout,
-                self.H, self.out_act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
+        resident = self.bout_dev is not None
+        args = (env._handle, self._lr32.data_ptr(), self.whh.data_ptr(), self.wx.data_ptr(), self.wout.data_ptr(),
+                self.bout_dev.data_ptr() if resident else self.bout, self.H, self.out_act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
                 noise.data_ptr() if noise is not None else None, float(std) if noise is not None else 0.0,
                 actions.data_ptr() if actions is not None else None, self.means.data_ptr() if record_means else None,
                 rewards.data_ptr(), dones.data_ptr(), src_out.data_ptr() if src_out is not None else None,
@@ -616,9 +635,10 @@ class FusedLSTMRollout(_FusedEvaluation):
             if self._workspace is None:
                 n = int(env._lib.fe_lstm_split_workspace_floats(self.H, N * A))
                 self._workspace = torch.empty((n,), dtype=torch.float32, device=dev)
-            _lib.check(env._lib.fe_env_rollout_lstm_split(*args, self._workspace.data_ptr(), env._stream()))
+            split = env._lib.fe_env_rollout_lstm_split_p if resident else env._lib.fe_env_rollout_lstm_split
+            _lib.check(split(*args, self._workspace.data_ptr(), env._stream()))
         else:
-            _lib.check(env._lib.fe_env_rollout_lstm(*args, env._stream()))
+            _lib.check((env._lib.fe_env_rollout_lstm_p if resident else env._lib.fe_env_rollout_lstm)(*args, env._stream()))
         self._end_run()
         if trajectory is not None:
             trajectory.mark_filled(K)

@@ -157,6 +157,7 @@ class _SacSample(torch.autograd.Function):
         # the packed weights and the two bias floats forward() fetched: backward makes no second copy to the host
         # (an empty batch packs nothing and launches nothing, in either direction)
         ctx.roll, ctx.packed, ctx.biases = roll, getattr(roll, "_packed", None), getattr(roll, "_biases", None)
+        ctx.version = None if roll.weights is None else roll.weights.version
         ctx.save_for_backward(src, pos, noise, actions, stds)
         return actions, log_probs
 
@@ -176,10 +177,13 @@ class _SacSample(torch.autograd.Function):
             g_a, g_lp = (None if g is None else g.reshape(B).float().contiguous() for g in (g_a, g_lp))
             ws = torch.empty((int(env._lib.fe_sac_grad_workspace_floats(H, int(env.num_intervals), B)),),
                              dtype=torch.float32, device=dev)
-            w, (bmu, bstd) = ctx.packed, ctx.biases
+            w, (bmu, bstd) = ctx.packed, ctx.biases  # the biases: two floats, or two device addresses (weights=)
+            if roll.weights is not None:
+                roll.weights.check_version(ctx.version)
             sg = _lib.FeSacGrads(*(g.data_ptr() for g in grads))
             ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            _lib.check(env._lib.fe_sac_backward(
+            backward = env._lib.fe_sac_backward_p if roll.weights is not None else env._lib.fe_sac_backward
+            _lib.check(backward(
                 env._handle, roll._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(),
                 w["bl"].data_ptr(), w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, H, src.data_ptr(),
                 pos.data_ptr(), B, noise.data_ptr(), actions.data_ptr(), stds.data_ptr(), ptr(g_a), ptr(g_lp),
@@ -198,10 +202,18 @@ class FusedSACRollout(_FusedEvaluation):
 
     The actor's parameters are re-packed on the device at every ``run`` / ``forward`` (a few small launches and one
     8-byte copy of the two output biases to the host, which the C ABI takes by value), so an optimizer step on ``actor``
-    is seen by the next call.  The actor must live on the env's device."""
+    is seen by the next call.  The actor must live on the env's device.
 
-    def __init__(self, env, actor: nn.Module):
+    ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that ``actor`` is registered with.  ``run``, ``forward`` and
+    ``sample`` then read that optimizer's packed buffers and the two output biases on the device: nothing is packed
+    per call and nothing is copied to the host.  Those buffers are rewritten in place: a ``weights.step()`` or
+    ``weights.repack()`` between ``sample`` and its ``backward()`` is a RuntimeError."""
+
+    def __init__(self, env, actor: nn.Module, weights=None):
         self.H = check_actor(actor)
+        self.weights = weights
+        if weights is not None:
+            weights.packed(actor)  # ValueError if the actor is not registered with it
         if env.redraw != "device" and not env.evaluate:
             raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
         if actor.lstm.weight_hh_l0.device != torch.device(env._dev):
@@ -218,11 +230,16 @@ class FusedSACRollout(_FusedEvaluation):
         self.sync_from_env()
 
     def _weights(self):
-        w = pack_sac_weights(self.actor)
+        """The weight arguments of fe_env_rollout_sac / fe_sac_forward -- of their ``_p`` siblings with ``weights=``,
+        where the two biases are device addresses."""
+        w = self.weights.packed(self.actor) if self.weights is not None else pack_sac_weights(self.actor)
         if w["whh"].device != torch.device(self.env._dev):
             raise ValueError(f"the actor's parameters must live on the env's device {self.env._dev}")
-        # the two output biases are kernel arguments: one small copy to the host, ordered after any pending update
-        bmu, bstd = torch.cat([w["bmu"], w["bstd"]]).cpu().tolist()
+        if self.weights is not None:
+            bmu, bstd = w["bmu"].data_ptr(), w["bstd"].data_ptr()
+        else:
+            # the two output biases are kernel arguments: one small copy to the host, ordered after any pending update
+            bmu, bstd = torch.cat([w["bmu"], w["bstd"]]).cpu().tolist()
         self._packed, self._biases = w, (bmu, bstd)  # kept alive until the launch has been queued
         return (self._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(), w["bl"].data_ptr(),
                 w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, self.H)
@@ -272,7 +289,8 @@ class FusedSACRollout(_FusedEvaluation):
         self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
         self.stds = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_stds else None
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _lib.check(env._lib.fe_env_rollout_sac(
+        rollout = env._lib.fe_env_rollout_sac_p if self.weights is not None else env._lib.fe_env_rollout_sac
+        _lib.check(rollout(
             env._handle, *w, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(), ptr(noise), actions.data_ptr(),
             ptr(self.means), ptr(self.stds), rewards.data_ptr(), dones.data_ptr(), ptr(src_out), ptr(pos_out),
             env._stream()))
@@ -299,7 +317,8 @@ class FusedSACRollout(_FusedEvaluation):
         if B:
             self._check_epoch()
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            _lib.check(env._lib.fe_sac_forward(
+            forward = env._lib.fe_sac_forward_p if self.weights is not None else env._lib.fe_sac_forward
+            _lib.check(forward(
                 env._handle, *self._weights(), src.data_ptr(), pos.data_ptr(), B, ptr(noise), ptr(actions),
                 ptr(log_probs), means.data_ptr(), stds.data_ptr(), env._stream()))
         return actions, log_probs, means, stds
