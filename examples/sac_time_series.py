@@ -30,8 +30,16 @@ does the actor and the temperature.  The fused front ends read those packed buff
 re-packing the modules at every call, and the actor's two output biases stay on the device.  The arithmetic is
 torch's, one f32 rounding per operation: with the same seed the losses agree with the default path up to f32 rounding.
 
+With ``--graph-update`` (which implies the four flags above) the update part of an iteration is ONE hipGraph launch:
+the mini-batch is drawn on the device from the replay ring's cursor (``ReplayBuffer(cursor=True).draw``), every fused
+front end takes that ``ReplayDraw``, and ``GraphedUpdate`` (finenvs_amd/graphed.py) captures draw, targets, both
+backward passes and both optimizer steps once and replays them.  The rollout and ``buffer.extend`` stay outside the
+graph.  The first iteration that trains also runs the capture's three warm-up updates (real ones), and the losses are
+read from the device only for iterations that are logged.  The draws differ from the other paths' (Philox on the
+device instead of ``torch.randint``), so the losses are comparable in distribution, not number for number.
+
     python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
-                                       [--fused-critics] [--fused-actor] [--fused-optim]
+                                       [--fused-critics] [--fused-actor] [--fused-optim] [--graph-update]
 """
 import argparse
 import copy
@@ -46,6 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.critic import CriticLSTM, FusedTwinCritic  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
+from finenvs_amd.graphed import GraphedUpdate  # noqa: E402
 from finenvs_amd.optim import FusedAdam  # noqa: E402
 from finenvs_amd.replay import ReplayBuffer  # noqa: E402
 from finenvs_amd.sac import FusedSACRollout, SACActorLSTM  # noqa: E402
@@ -60,14 +69,17 @@ def soft_update(target, source, rho):
 
 def iterate(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
             days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, fused_targets=False,
-            fused_critics=False, fused_actor=False, fused_optim=False):
+            fused_critics=False, fused_actor=False, fused_optim=False, graph_update=False, log_every=1):
     """The training loop as a generator: one log entry per iteration that trained (tools/optim_bench.py steps two of
-    these alternately)."""
+    these alternately).  With ``graph_update`` an entry carries the losses only every ``log_every`` iterations and at
+    the last one: reading them waits for the device."""
+    if graph_update:
+        fused_targets = fused_critics = fused_actor = fused_optim = True
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
     dev, N, A = env.device, num_envs, 1
-    buffer = ReplayBuffer(env, max_size=max(max_size, chunk * N))
+    buffer = ReplayBuffer(env, max_size=max(max_size, chunk * N), cursor=graph_update, seed=seed)
     actor = SACActorLSTM(H=hidden, W=window).to(dev)
     critic_1, critic_2 = CriticLSTM(hidden, window).to(dev), CriticLSTM(hidden, window).to(dev)
     critic_1t, critic_2t = copy.deepcopy(critic_1), copy.deepcopy(critic_2)
@@ -89,12 +101,42 @@ def iterate(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=
     twin_online = FusedTwinCritic(env, critic_1, critic_2, **resident_c) if fused_critics else None
     gen = torch.Generator(device=dev).manual_seed(seed)
     render = not (fused_critics and fused_actor)  # somebody still reads the rendered states
+    graphed, draw = None, buffer.new_draw(batch) if graph_update else None
+
+    def update():  # what GraphedUpdate captures: no host integer of the ring, no .item()
+        for _ in range(updates_per_chunk):
+            buffer.draw(batch, out=draw)
+            y = twin.sac_targets(buffer, draw, roll, torch.randn((batch, 1), device=dev), gamma, actor.log_alpha,
+                                 reward_scale=reward_scale)
+            critic_loss = twin_online.critic_loss(buffer, draw, y)
+            critic_opt.zero_grad()
+            critic_loss.backward()
+            critic_opt.step()
+            a_new, lp = roll.sample(draw.state_src, draw.state_pos, torch.randn((batch, 1), device=dev))
+            mean_lp = lp.mean(dim=1, keepdim=True)
+            q = torch.min(*twin_online.q(draw.state_src, draw.state_pos, a_new))
+            actor_loss = -(q - actor.log_alpha.exp().detach() * mean_lp).mean()
+            alpha_loss = (-actor.log_alpha.exp() * (mean_lp + actor.target_entropy).detach()).mean()
+            actor_loss.backward()
+            alpha_loss.backward()
+            actor_opt.step()
+        return critic_loss.detach(), actor_loss.detach(), alpha_loss.detach(), actor.log_alpha.detach().exp()
+
     for it in range(iterations):
         traj = TrajectoryBuffer(chunk, N, A, device=dev, states=True)
         noise = torch.randn((chunk, N, A), generator=gen, device=dev)
         roll.run(chunk, noise=noise, trajectory=traj)
         buffer.extend(traj)
         if buffer.size() < batch:
+            continue
+        if graph_update:
+            if graphed is None:  # three warm-up updates (real ones) on this ring state, then the capture
+                graphed = GraphedUpdate(update, warmup=3)
+            losses = graphed.replay()
+            entry = {"iteration": it, "buffer_size": buffer.size()}
+            if it % log_every == 0 or it == iterations - 1:
+                entry.update(zip(("critic_loss", "actor_loss", "alpha_loss", "alpha"), (float(x) for x in losses)))
+            yield entry
             continue
         for _ in range(updates_per_chunk):
             if fused_targets:  # the same draws as below: get_mini_batch's indices, then rsample's normals
@@ -153,12 +195,13 @@ def iterate(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=
 
 def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256, updates_per_chunk=1, max_size=1_000_000,
          days=40, bars=120, gamma=0.99, rho=0.005, lr=3e-4, reward_scale=0.01, seed=0, quiet=False, fused_targets=False,
-         fused_critics=False, fused_actor=False, fused_optim=False):
+         fused_critics=False, fused_actor=False, fused_optim=False, graph_update=False, log_every=10):
     history = []
     for entry in iterate(num_envs, window, hidden, iterations, chunk, batch, updates_per_chunk, max_size, days, bars, gamma,
-                         rho, lr, reward_scale, seed, fused_targets, fused_critics, fused_actor, fused_optim):
+                         rho, lr, reward_scale, seed, fused_targets, fused_critics, fused_actor, fused_optim, graph_update,
+                         log_every):
         history.append(entry)
-        if not quiet and entry["iteration"] % 10 == 0:
+        if not quiet and entry["iteration"] % 10 == 0 and "critic_loss" in entry:
             print(f"iter {entry['iteration']:5d}  buffer {entry['buffer_size']:8d}  critic {entry['critic_loss']:.4g}  "
                   f"actor {entry['actor_loss']:.4g}  alpha {entry['alpha']:.4g}")
     return history
@@ -174,6 +217,8 @@ if __name__ == "__main__":
     ap.add_argument("--fused-critics", action="store_true")
     ap.add_argument("--fused-actor", action="store_true")
     ap.add_argument("--fused-optim", action="store_true")
+    ap.add_argument("--graph-update", action="store_true")
     a = ap.parse_args()
     main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
-         fused_critics=a.fused_critics, fused_actor=a.fused_actor, fused_optim=a.fused_optim)
+         fused_critics=a.fused_critics, fused_actor=a.fused_actor, fused_optim=a.fused_optim,
+         graph_update=a.graph_update)

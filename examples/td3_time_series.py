@@ -12,7 +12,15 @@ network's tensors and, on the delayed iterations, the soft update of their targe
 packed form, so their tensors are registered with ``add_tensor``.  With the same seed the losses agree with the default
 path up to f32 rounding.
 
+With ``--graph-update`` (which implies ``--fused-optim``) the update part of an iteration is ONE hipGraph launch: the
+mini-batch is drawn on the device from the replay ring's cursor (``ReplayBuffer(cursor=True).draw``), rendered from that
+``ReplayDraw`` (``get_mini_batch(indices=draw)``: head and size are read on the device), and ``GraphedUpdate``
+(finenvs_amd/graphed.py) captures the whole update.  The delayed actor update is a host-side alternation, so two graphs
+are captured, one with and one without the actor step; each capture runs one warm-up update (a real one) first.  The
+env steps and ``buffer.store`` stay outside the graphs; the losses are read only for iterations that are logged.
+
     python examples/td3_time_series.py [--envs 1024] [--window 16] [--iterations 200] [--batch 256] [--fused-optim]
+                                       [--graph-update]
 """
 import argparse
 import copy
@@ -27,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
+from finenvs_amd.graphed import GraphedUpdate  # noqa: E402
 from finenvs_amd.optim import FusedAdam  # noqa: E402
 from finenvs_amd.replay import ReplayBuffer  # noqa: E402
 
@@ -59,12 +68,13 @@ def soft_update(target, source, rho):
 
 def main(num_envs=1024, window=16, hidden=(256, 256), iterations=200, batch=256, max_size=1_000_000, days=40, bars=120,
          assets=1, gamma=0.99, rho=0.005, lr=3e-4, exploration_std=0.1, policy_std=0.2, policy_clip=0.5, policy_delay=2,
-         reward_scale=0.01, seed=0, quiet=False, fused_optim=False):
+         reward_scale=0.01, seed=0, quiet=False, fused_optim=False, graph_update=False, log_every=20):
+    fused_optim = fused_optim or graph_update
     torch.manual_seed(seed)
     prices, day_id, _ = synthetic.synthetic_series(days, assets, bars, 1234 + seed)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=num_envs, redraw="device", seed=seed)
     dev, N, A = env.device, num_envs, assets
-    buffer = ReplayBuffer(env, max_size=max(max_size, N))
+    buffer = ReplayBuffer(env, max_size=max(max_size, N), cursor=graph_update, seed=seed)
     obs_dim = window * 5 * A
     actor = mlp(obs_dim, A, hidden, nn.Tanh()).to(dev)
     critic_1, critic_2 = Critic(obs_dim, A, hidden).to(dev), Critic(obs_dim, A, hidden).to(dev)
@@ -87,6 +97,28 @@ def main(num_envs=1024, window=16, hidden=(256, 256), iterations=200, batch=256,
                                     torch.empty((N, A), dtype=torch.float64, device=dev))]
     obs = env.reset()
     eval_return, eval_returns, history = 0.0, [], []
+    draw = buffer.new_draw(batch) if graph_update else None
+    graphs = {}
+
+    def update(delayed):  # what GraphedUpdate captures: no host integer of the ring, no .item()
+        b = buffer.get_mini_batch(batch, indices=buffer.draw(batch, out=draw))
+        s, s2 = b["states"].flatten(1), b["next_states"].flatten(1)
+        r, d = b["rewards"] * reward_scale, b["dones"]
+        with torch.no_grad():
+            noise = (torch.randn_like(b["actions"]) * policy_std).clamp(-policy_clip, policy_clip)
+            a2 = (actor_t(s2) + noise).clamp(-1.0, 1.0)
+            y = r + gamma * (1.0 - d) * torch.min(critic_1t(s2, a2), critic_2t(s2, a2))
+        critic_loss = F.mse_loss(critic_1(s, b["actions"]), y) + F.mse_loss(critic_2(s, b["actions"]), y)
+        critic_opt.zero_grad()
+        critic_loss.backward()
+        critic_opt.step(soft_update=delayed)
+        if not delayed:
+            return (critic_loss.detach(),)
+        actor_loss = -critic_1(s, actor(s)).mean()
+        actor_loss.backward()
+        actor_opt.step()
+        return critic_loss.detach(), actor_loss.detach()
+
     for it in range(iterations):
         with torch.no_grad():
             actions = (actor(obs.float().flatten(1)) + torch.randn((N, A), device=dev) * explore).clamp(-1.0, 1.0)
@@ -98,6 +130,19 @@ def main(num_envs=1024, window=16, hidden=(256, 256), iterations=200, batch=256,
             eval_returns.append(eval_return)
             eval_return = 0.0
         if buffer.size() < batch:
+            continue
+        if graph_update:
+            delayed = it % policy_delay == 0
+            if delayed not in graphs:  # one warm-up update (a real one) on this ring state, then the capture
+                graphs[delayed] = GraphedUpdate(lambda delayed=delayed: update(delayed), warmup=1)
+            losses = graphs[delayed].replay()
+            entry = {"iteration": it, "buffer_size": buffer.size()}
+            if it % log_every == 0 or it == iterations - 1:
+                entry.update(zip(("critic_loss", "actor_loss"), (float(x) for x in losses)))
+                if not quiet:
+                    print(f"iter {it:5d}  buffer {buffer.size():8d}  critic {entry['critic_loss']:.4g}  "
+                          f"actor {entry.get('actor_loss', float('nan')):.4g}  eval episodes {len(eval_returns)}")
+            history.append(entry)
             continue
         b = buffer.get_mini_batch(batch)
         s, s2 = b["states"].flatten(1), b["next_states"].flatten(1)
@@ -141,5 +186,7 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--max-size", type=int, default=1_000_000)
     ap.add_argument("--fused-optim", action="store_true")
+    ap.add_argument("--graph-update", action="store_true")
     a = ap.parse_args()
-    main(a.envs, a.window, iterations=a.iterations, batch=a.batch, max_size=a.max_size, fused_optim=a.fused_optim)
+    main(a.envs, a.window, iterations=a.iterations, batch=a.batch, max_size=a.max_size, fused_optim=a.fused_optim,
+         graph_update=a.graph_update)

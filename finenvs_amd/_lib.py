@@ -234,6 +234,19 @@ OPTIM_SIGNATURES = {
                                     _vp, _vp, _vp, C.POINTER(FeSacGrads), _vp]),
 }
 
+# include/finenvs_amd_replay_cursor.h: the ring's cursor in device memory and the draw from it (finenvs_amd/replay.py)
+CURSOR_HEAD, CURSOR_SIZE, CURSOR_DRAWS, CURSOR_TICKET, CURSOR_WORDS = 0, 1, 2, 3, 4  # int64 words of fe_replay_cursor
+REPLAY_CURSOR_SIGNATURES = {
+    # fe_replay_append's list, then cursor, new_size, stream
+    "fe_replay_append_c": (C.c_int, [C.POINTER(FeReplayRing), _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp,
+                                     _i32, _vp, _vp, _vp, _i64, _vp]),
+    "fe_ring_draw": (C.c_int, [C.POINTER(FeReplayRing), _vp, C.c_uint64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the by-value entries' lists with `head, size` replaced by the cursor
+    "fe_twin_q_target_c": (C.c_int, [_vp, _vp, _cw, _cw, _i32, C.POINTER(FeReplayRing), _vp, _vp, _i64, _vp, _vp,
+                                     C.c_float, C.c_float, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "fe_replay_sample_c": (C.c_int, [_vp, C.POINTER(FeReplayRing), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -260,7 +273,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
-                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **OPTIM_SIGNATURES}.items():
+                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **OPTIM_SIGNATURES,
+                         **REPLAY_CURSOR_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .replay import as_draw
 from .rollout import lstm_pack, lstm_row_order_on
 
 CRITIC_HIDDEN_SIZES = (32, 64, 128)
@@ -270,9 +271,17 @@ class FusedTwinCritic:
         """``MSE(q1, y) + MSE(q2, y)`` of both critics (SAC/critic.py:30-45 compute_loss, once per critic) on the
         transitions ``indices`` (logical, (B,)) of ``buffer``: the ring's state descriptors and stored actions of those
         transitions, nothing rendered.  ``targets`` (B, 1) float32, e.g. from ``sac_targets`` / ``td3_targets``.  An
-        index outside ``[0, size)`` makes its values NaN (as ``fe_twin_q_target``)."""
+        index outside ``[0, size)`` makes its values NaN (as ``fe_twin_q_target``).  ``indices`` may be a ``ReplayDraw``
+        of a ``cursor=True`` buffer (no host integer enters then: capturable)."""
+        draw = as_draw(buffer, indices, "critic_loss")
         if indices is None:
             raise ValueError("critic_loss needs the indices of the sampled transitions")
+        if draw is not None:  # the draw's gathered descriptors and actions; its indices are in range by construction
+            self._indices(buffer, draw.indices, None)
+            B = int(draw.indices.numel())
+            y = self._vector(targets, B, "targets").reshape(B, 1)
+            q1, q2 = self.q(draw.state_src, draw.state_pos.reshape(B), draw.actions.reshape(B, 1))
+            return F.mse_loss(q1, y) + F.mse_loss(q2, y)
         idx = self._indices(buffer, indices, None)
         B = int(idx.numel())
         y = self._vector(targets, B, "targets").reshape(B, 1)
@@ -298,14 +307,16 @@ class FusedTwinCritic:
             raise ValueError(f"indices must be an integer tensor of logical indices on {buffer.device}")
         return indices.reshape(-1).to(torch.int64).contiguous()
 
-    def _next_descriptors(self, buffer, idx):
+    def _next_descriptors(self, buffer, idx, draw=None):
+        if draw is not None:
+            return draw.next_src, draw.next_pos
         # the actor half reads the sampled next states' descriptors (an out-of-range index wraps to some slot here; its
         # target is NaN all the same and fe_twin_q_target counts it)
         slots = buffer.physical(idx)
         return buffer.next_src[slots], buffer.next_pos[slots]
 
     def _targets(self, buffer, idx, next_actions, smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma,
-                 reward_scale) -> torch.Tensor:
+                 reward_scale, draw=None) -> torch.Tensor:
         env, B = self.env, int(idx.numel())
         dev = env._dev
         y = torch.empty((B, 1), dtype=torch.float32, device=dev)
@@ -314,11 +325,17 @@ class FusedTwinCritic:
         if B:
             c1, c2 = self._weights()
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            _lib.check(env._lib.fe_twin_q_target(
-                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
-                buffer.head, buffer.size(), idx.data_ptr(), B, next_actions.data_ptr(), ptr(smooth_noise),
-                float(smooth_std), float(smooth_clip), ptr(log_probs), ptr(alpha), float(gamma), float(reward_scale),
-                y.data_ptr(), q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
+            tail = (idx.data_ptr(), B, next_actions.data_ptr(), ptr(smooth_noise), float(smooth_std), float(smooth_clip),
+                    ptr(log_probs), ptr(alpha), float(gamma), float(reward_scale), y.data_ptr(), q1.data_ptr(),
+                    q2.data_ptr(), env._stream())
+            if draw is None:
+                _lib.check(env._lib.fe_twin_q_target(
+                    env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
+                    buffer.head, buffer.size(), *tail), env._lib)
+            else:  # head and size from the cursor, when the launches run
+                _lib.check(env._lib.fe_twin_q_target_c(
+                    env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
+                    buffer.cursor.data_ptr(), *tail), env._lib)
         self.last = {"indices": idx, "next_actions": next_actions.reshape(B, 1), "q1": q1, "q2": q2}
         return y
 
@@ -330,21 +347,24 @@ class FusedTwinCritic:
         ``noise`` (B, 1) standard normals -- by default ``torch.randn``, the draw ``rsample`` makes -- then both target
         critics and ``y = r + gamma * (1 - d) * (min(q1, q2) - alpha * log_prob)`` with ``alpha = log_alpha.exp()``,
         ``r`` the stored reward times ``reward_scale``.  (B, 1) float32.  ``indices=None`` draws ``batch_size`` of them as
-        ``get_mini_batch`` does; ``self.last`` keeps the indices, next actions, log-probabilities and values."""
+        ``get_mini_batch`` does; ``self.last`` keeps the indices, next actions, log-probabilities and values.
+        ``indices`` may be a ``ReplayDraw`` of a ``cursor=True`` buffer: its gathered next descriptors are used and the
+        ring's head and size are read from the cursor (``fe_twin_q_target_c``), so the call is capturable."""
         from .sac import FusedSACRollout
 
+        draw = as_draw(buffer, indices, "sac_targets")
         if not isinstance(actor_roll, FusedSACRollout):
             raise ValueError("actor_roll must be a FusedSACRollout (the SAC actor's head)")
         if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.device != torch.device(self.env._dev):
             raise ValueError(f"log_alpha must be a one-element tensor on {self.env._dev}")
-        idx = self._indices(buffer, indices, batch_size)
+        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
         B = int(idx.numel())
         if noise is None:
             noise = torch.randn((B, 1), device=self.env._dev)
-        src, pos = self._next_descriptors(buffer, idx)
+        src, pos = self._next_descriptors(buffer, idx, draw)
         actions, log_probs, _, _ = actor_roll.forward(src, pos, noise=noise.reshape(B, 1))
         alpha = log_alpha.detach().exp().float().reshape(1).contiguous()
-        y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale)
+        y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale, draw)
         self.last.update(log_probs=log_probs, alpha=alpha)
         return y
 
@@ -357,16 +377,17 @@ class FusedTwinCritic:
         both target critics and ``y = r + gamma * (1 - d) * min(q1, q2)``.  (B, 1) float32."""
         from .rollout import FusedLSTMRollout
 
+        draw = as_draw(buffer, indices, "td3_targets")
         if not isinstance(target_actor, FusedLSTMRollout) or target_actor.out_act != 0:
             raise ValueError('target_actor must be a FusedLSTMRollout with output_activation="tanh"')
-        idx = self._indices(buffer, indices, batch_size)
+        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
         B = int(idx.numel())
-        src, pos = self._next_descriptors(buffer, idx)
+        src, pos = self._next_descriptors(buffer, idx, draw)
         actions = target_actor.forward(src, pos)
         if noise is None:
             noise = torch.randn((B, 1), device=self.env._dev)
         noise = self._vector(noise, B, "noise")
-        return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale)
+        return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale, draw)
 
 
 # ---------------------------------------------------------------- the torch restatements (host or device)

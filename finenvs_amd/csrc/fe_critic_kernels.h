@@ -3,6 +3,7 @@
 #pragma once
 #include "fe_device_common.h"
 #include "fe_lstm_kernel.h"
+#include "fe_replay_kernels.h"
 
 namespace {
 
@@ -34,6 +35,7 @@ struct CriticArgs {
     const float *actions;       // (count) the action in slot 6
     const float *smooth_noise;  // (count) standard normals or null: TD3's target smoothing (TD3_agent.py:236-241)
     float smooth_std, smooth_clip;
+    const int64_t *cursor;      // the ring's cursor or null: start / size are read from it (fe_twin_q_target_c)
 };
 
 __device__ __forceinline__ float clamp_pm(float x, float lo, float hi) {  // torch.clamp, NaN propagating
@@ -52,8 +54,9 @@ __device__ __forceinline__ bool ring_slot(int64_t k, int64_t start, int64_t size
 // window: its value is overwritten by NaN in critic_store.
 __device__ __forceinline__ void critic_load_pair(const CriticArgs &cq, int64_t n, int64_t *src, double *pos, float *act) {
     if (cq.indices) {
-        int64_t slot;
-        const bool ok = ring_slot(cq.indices[n], cq.start, cq.size, cq.ring_C, slot);
+        int64_t slot, start = cq.start, size = cq.size;
+        ring_window(cq.cursor, cq.ring_C, start, size);
+        const bool ok = ring_slot(cq.indices[n], start, size, cq.ring_C, slot);
         *src = ok ? cq.ring_src[slot] : 0;
         *pos = ok ? cq.ring_pos[slot] : 0.0;
     } else {
@@ -71,7 +74,9 @@ __device__ __forceinline__ void critic_load_pair(const CriticArgs &cq, int64_t n
 __device__ __forceinline__ void critic_store(const CriticArgs &cq, int64_t n, float q) {
     if (cq.indices) {
         const int64_t k = cq.indices[n];
-        if (k < 0 || k >= cq.size) q = __builtin_nanf("");
+        int64_t start = cq.start, size = cq.size;
+        ring_window(cq.cursor, cq.ring_C, start, size);
+        if (k < 0 || k >= size) q = __builtin_nanf("");
     }
     cq.net[blockIdx.y].q_out[n] = q;
 }
@@ -105,13 +110,16 @@ struct TwinTargetArgs {
     float gamma, reward_scale;
     float *targets;
     unsigned long long *errors;
+    const int64_t *cursor;  // as CriticArgs'
 };
 
 __global__ __launch_bounds__(kBlock) void fe_twin_q_target_kernel(const TwinTargetArgs t) {
     const float qnan = __builtin_nanf("");
+    int64_t start = t.start, size = t.size;
+    ring_window(t.cursor, t.ring_C, start, size);
     for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < t.count; i += (int64_t)gridDim.x * kBlock) {
         int64_t slot;
-        const bool ok = ring_slot(t.indices[i], t.start, t.size, t.ring_C, slot);
+        const bool ok = ring_slot(t.indices[i], start, size, t.ring_C, slot);
         if (!ok) {
             atomicAdd(t.errors, 1ull);
             t.targets[i] = qnan;

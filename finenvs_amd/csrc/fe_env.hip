@@ -36,6 +36,7 @@
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
+//   fe_ring_draw_kernels.h  a mini-batch drawn and gathered from the ring's device cursor (capturable updates)
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
 //   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
@@ -71,6 +72,7 @@
 #include "finenvs_amd_lstm_grad.h"
 #include "finenvs_amd_lstm_grad_streamed.h"
 #include "finenvs_amd_optim.h"
+#include "finenvs_amd_replay_cursor.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -80,6 +82,7 @@
 #include "fe_aux_kernels.h"
 #include "fe_evo_kernels.h"
 #include "fe_replay_kernels.h"
+#include "fe_ring_draw_kernels.h"
 #include "fe_critic_kernels.h"
 #include "fe_critic_grad_kernels.h"
 #include "fe_sac_grad_kernels.h"
@@ -1282,10 +1285,11 @@ static ReplayRing replay_view(const fe_replay_ring *ring) {
     return r;
 }
 
-int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, int64_t num_envs, int64_t row_stride,
-                     int64_t first, int64_t count, const int64_t *state_src, const double *state_pos,
-                     const int64_t *next_src, const double *next_pos, const void *actions, int32_t actions_are_f64,
-                     const double *rewards, const int32_t *dones, void *stream) {
+// fe_replay_append and fe_replay_append_c: the same kernel, `cursor` null for the by-value entry.
+static int replay_append_impl(const fe_replay_ring *ring, int64_t head, int64_t steps, int64_t num_envs, int64_t row_stride,
+                              int64_t first, int64_t count, const int64_t *state_src, const double *state_pos,
+                              const int64_t *next_src, const double *next_pos, const void *actions, int32_t actions_are_f64,
+                              const double *rewards, const int32_t *dones, int64_t *cursor, int64_t new_size, void *stream) {
     if (!replay_ring_ok(ring) || !state_src || !state_pos || !next_src || !next_pos || !actions || !rewards || !dones)
         return fail(FE_ERR_ARG, "fe_replay_append: null argument");
     const int64_t C = ring->capacity;
@@ -1294,6 +1298,9 @@ int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, in
         return fail(FE_ERR_ARG, "fe_replay_append: bad range (steps %lld, num_envs %lld, row_stride %lld, first %lld, "
                     "count %lld, head %lld, capacity %lld)", (long long)steps, (long long)num_envs, (long long)row_stride,
                     (long long)first, (long long)count, (long long)head, (long long)C);
+    if (cursor && (new_size < count || new_size > C))
+        return fail(FE_ERR_ARG, "fe_replay_append_c: new_size %lld is not in [count %lld, capacity %lld]", (long long)new_size,
+                    (long long)count, (long long)C);
     DeviceGuard guard(device_of(ring->rewards));
     if (int rc = guard.status("fe_replay_append: the ring is not device memory")) return rc;
     const ReplayRing r = replay_view(ring);
@@ -1301,19 +1308,58 @@ int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, in
         with_bool(actions_are_f64 != 0, [&](auto F) {
             hipLaunchKernelGGL((fe_replay_append_kernel<decltype(S)::value, decltype(F)::value>), dim3(grid_for(count * r.A)),
                                dim3(kBlock), 0, (hipStream_t)stream, r, head, first, count, num_envs, row_stride, state_src,
-                               state_pos, next_src, next_pos, actions, rewards, dones);
+                               state_pos, next_src, next_pos, actions, rewards, dones, cursor, new_size);
         });
     });
     return launched("fe_replay_append");
 }
 
-int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
-                     int64_t count, float *states, float *next_states, float *actions, float *rewards, float *dones,
-                     void *stream) {
+int fe_replay_append(const fe_replay_ring *ring, int64_t head, int64_t steps, int64_t num_envs, int64_t row_stride,
+                     int64_t first, int64_t count, const int64_t *state_src, const double *state_pos,
+                     const int64_t *next_src, const double *next_pos, const void *actions, int32_t actions_are_f64,
+                     const double *rewards, const int32_t *dones, void *stream) {
+    return replay_append_impl(ring, head, steps, num_envs, row_stride, first, count, state_src, state_pos, next_src, next_pos,
+                              actions, actions_are_f64, rewards, dones, nullptr, 0, stream);
+}
+
+int fe_replay_append_c(const fe_replay_ring *ring, int64_t head, int64_t steps, int64_t num_envs, int64_t row_stride,
+                       int64_t first, int64_t count, const int64_t *state_src, const double *state_pos,
+                       const int64_t *next_src, const double *next_pos, const void *actions, int32_t actions_are_f64,
+                       const double *rewards, const int32_t *dones, int64_t *cursor, int64_t new_size, void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_replay_append_c: null cursor");
+    return replay_append_impl(ring, head, steps, num_envs, row_stride, first, count, state_src, state_pos, next_src, next_pos,
+                              actions, actions_are_f64, rewards, dones, cursor, new_size, stream);
+}
+
+int fe_ring_draw(const fe_replay_ring *ring, int64_t *cursor, uint64_t seed, int64_t count, int64_t *indices_out,
+                 int64_t *state_src, double *state_pos, int64_t *next_src, double *next_pos, float *actions,
+                 float *rewards, float *dones, void *stream) {
+    if (!replay_ring_ok(ring) || !cursor || !indices_out || count < 0)
+        return fail(FE_ERR_ARG, "fe_ring_draw: bad argument");
+    if (ring->capacity >= (int64_t)1 << 32)
+        return fail(FE_ERR_ARG, "fe_ring_draw: capacity %lld does not fit the 32-bit multiply-shift draw", (long long)ring->capacity);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(device_of(ring->rewards));
+    if (int rc = guard.status("fe_ring_draw: the ring is not device memory")) return rc;
+    RingDrawArgs d;
+    d.r = replay_view(ring);
+    d.errors = reinterpret_cast<unsigned long long *>(ring->errors);
+    d.cursor = cursor; d.seed = seed; d.count = count; d.idx = indices_out;
+    d.s_src = state_src; d.s_pos = state_pos; d.n_src = next_src; d.n_pos = next_pos;
+    d.act = actions; d.rew = rewards; d.done = dones;
+    hipLaunchKernelGGL(fe_ring_draw_kernel, dim3(grid_for(count * d.r.A)), dim3(kBlock), 0, (hipStream_t)stream, d);
+    return launched("fe_ring_draw");
+}
+
+// fe_replay_sample and fe_replay_sample_c: the same kernel, `cursor` null for the by-value entry (head / size ignored
+// and unchecked with a cursor: they are read on the device).
+static int replay_sample_impl(fe_env *env, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *cursor,
+                              const int64_t *indices, int64_t count, float *states, float *next_states, float *actions,
+                              float *rewards, float *dones, void *stream) {
     if (!env || !replay_ring_ok(ring) || !indices || !states || !next_states || !actions || !rewards || !dones || count < 0)
         return fail(FE_ERR_ARG, "fe_replay_sample: bad argument");
     const int64_t C = ring->capacity;
-    if (size < 1 || size > C || head < 0 || head >= C)
+    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
         return fail(FE_ERR_ARG, "fe_replay_sample: size %lld / head %lld do not describe a non-empty ring of %lld slots",
                     (long long)size, (long long)head, (long long)C);
     if (ring->num_assets != env->p.A)
@@ -1342,17 +1388,31 @@ int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int6
     const int64_t grid = p.num_tiles < 8 * (int64_t)env->cus ? p.num_tiles : 8 * (int64_t)env->cus;
     const size_t lds = replay_lds_bytes((int)EB, A);
     const ReplayRing r = replay_view(ring);
-    const int64_t start = ((head - size) % C + C) % C;
+    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
     unsigned long long *err = reinterpret_cast<unsigned long long *>(ring->errors);
     // the sampled states are f32 observations
     with_layout(/*f32=*/true, vec_width(p.env_elems, 4), [&](auto, auto V) {
         with_bool(A == 1, [&](auto S) {
             hipLaunchKernelGGL((fe_replay_sample_kernel<decltype(V)::value, decltype(S)::value>), dim3((unsigned)grid),
                                dim3(kBlock), lds, (hipStream_t)stream, p, r, indices, start, size, states, next_states,
-                               actions, rewards, dones, err);
+                               actions, rewards, dones, err, cursor);
         });
     });
     return launched("fe_replay_sample");
+}
+
+int fe_replay_sample(fe_env *env, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
+                     int64_t count, float *states, float *next_states, float *actions, float *rewards, float *dones,
+                     void *stream) {
+    return replay_sample_impl(env, ring, head, size, nullptr, indices, count, states, next_states, actions, rewards, dones,
+                              stream);
+}
+
+int fe_replay_sample_c(fe_env *env, const fe_replay_ring *ring, const int64_t *cursor, const int64_t *indices,
+                       int64_t count, float *states, float *next_states, float *actions, float *rewards, float *dones,
+                       void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_replay_sample_c: null cursor");
+    return replay_sample_impl(env, ring, 0, 0, cursor, indices, count, states, next_states, actions, rewards, dones, stream);
 }
 
 // ---- include/finenvs_amd_sac.h: the SAC actor's head on the LSTM recurrence ----
@@ -1483,11 +1543,13 @@ int fe_twin_q_forward(fe_env *env, const float *logret_f32, const fe_critic_weig
     return launch_twin_q(env, cq, count, "fe_twin_q_forward", stream);
 }
 
-int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                     int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
-                     int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
-                     float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
-                     float *targets_out, float *q1_out, float *q2_out, void *stream) {
+// fe_twin_q_target and fe_twin_q_target_c: the same kernels, `cursor` null for the by-value entry (head / size ignored
+// and unchecked with a cursor: they are read on the device).
+static int twin_q_target_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                              int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *cursor,
+                              const int64_t *indices, int64_t count, const float *next_actions, const float *smooth_noise,
+                              float smooth_std, float smooth_clip, const float *log_probs, const float *alpha, float gamma,
+                              float reward_scale, float *targets_out, float *q1_out, float *q2_out, void *stream) {
     if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
         !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
         return fail(FE_ERR_ARG, "fe_twin_q_target: bad argument");
@@ -1496,18 +1558,18 @@ int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weigh
         return fail(FE_ERR_ARG, "fe_twin_q_target: smooth_noise (TD3) and log_probs (SAC) are exclusive");
     if (int rc = critic_check(env, c1, c2, H, "fe_twin_q_target")) return rc;
     const int64_t C = ring->capacity;
-    if (size < 1 || size > C || head < 0 || head >= C)
+    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
         return fail(FE_ERR_ARG, "fe_twin_q_target: size %lld / head %lld do not describe a non-empty ring of %lld slots",
                     (long long)size, (long long)head, (long long)C);
     if (ring->num_assets != 1) return fail(FE_ERR_ARG, "fe_twin_q_target: the ring holds %d assets, the env 1", (int)ring->num_assets);
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
-    const int64_t start = ((head - size) % C + C) % C;
+    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
     CriticArgs cq;
     critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
     cq.indices = indices; cq.ring_src = ring->next_src; cq.ring_pos = ring->next_pos;
-    cq.ring_C = C; cq.start = start; cq.size = size;
+    cq.ring_C = C; cq.start = start; cq.size = size; cq.cursor = cursor;
     cq.actions = next_actions; cq.smooth_noise = smooth_noise; cq.smooth_std = smooth_std; cq.smooth_clip = smooth_clip;
     if (int rc = launch_twin_q(env, cq, count, "fe_twin_q_target: critics", stream)) return rc;
     TwinTargetArgs t;
@@ -1515,8 +1577,30 @@ int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weigh
     t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
     t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
     t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
+    t.cursor = cursor;
     hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
     return launched("fe_twin_q_target: epilogue");
+}
+
+int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                     int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
+                     int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
+                     float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
+                     float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
+                              smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out,
+                              q1_out, q2_out, stream);
+}
+
+int fe_twin_q_target_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                       int32_t H, const fe_replay_ring *ring, const int64_t *cursor, const int64_t *indices,
+                       int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
+                       float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
+                       float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_c: null cursor");
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions, smooth_noise,
+                              smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out, q1_out, q2_out,
+                              stream);
 }
 
 // ---- include/finenvs_amd_critic_grad.h: the twin critics' backward pass ----

@@ -20,8 +20,23 @@ struct ReplayRing {
     int32_t A;
 };
 
+// The ring's cursor in device memory (struct fe_replay_cursor of include/finenvs_amd_replay_cursor.h) as int64 words.
+constexpr int kCursorHead = 0, kCursorSize = 1, kCursorDraws = 2, kCursorTicket = 3;
+
+// Where logical index 0 lives and how many indices there are, by value (cursor == null) or from the cursor: the address is
+// the same in every lane, so these are two scalar loads.  A launch that reads the cursor is ordered after the append that
+// wrote it by the stream.
+__device__ __forceinline__ void ring_window(const int64_t *__restrict__ cursor, int64_t C, int64_t &start, int64_t &size) {
+    if (cursor) {
+        size = cursor[kCursorSize];
+        start = cursor[kCursorHead] - size;
+        if (start < 0) start += C;
+    }
+}
+
 // Append `count` transitions j = first .. first + count - 1 of a step-major source (j = t * N + n, source element
 // e = t * ld + n) to ring slots (head + j - first) mod C.  One lane per (transition, asset); f64 actions are cast to f32.
+// With a cursor (fe_replay_append_c) one thread then writes the ring's new head and size into it.
 template <bool SINGLE, bool ACT_F64>
 __global__ __launch_bounds__(kBlock) void fe_replay_append_kernel(const ReplayRing r, int64_t head, int64_t first,
                                                                   int64_t count, int64_t N, int64_t ld,
@@ -31,7 +46,8 @@ __global__ __launch_bounds__(kBlock) void fe_replay_append_kernel(const ReplayRi
                                                                   const double *__restrict__ n_pos,
                                                                   const void *__restrict__ actions,
                                                                   const double *__restrict__ rewards,
-                                                                  const int32_t *__restrict__ dones) {
+                                                                  const int32_t *__restrict__ dones,
+                                                                  int64_t *__restrict__ cursor, int64_t new_size) {
     const int A = SINGLE ? 1 : r.A;
     const int64_t total = count * A;
     for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
@@ -54,6 +70,12 @@ __global__ __launch_bounds__(kBlock) void fe_replay_append_kernel(const ReplayRi
             r.done[slot] = (float)dones[e];
         }
     }
+    if (cursor && blockIdx.x == 0 && threadIdx.x == 0) {  // after this thread's transitions; nobody reads it in this launch
+        int64_t h = head + count;
+        if (h >= r.C) h -= r.C;
+        cursor[kCursorHead] = h;
+        cursor[kCursorSize] = new_size;
+    }
 }
 
 // Bytes of one descriptor tile (src[EB] + pos[EB * A]) in LDS.
@@ -64,14 +86,17 @@ __host__ __device__ inline size_t replay_lds_bytes(int EB, int A) { return 4 * (
 
 // Minibatch of p.N logical indices, as f32: states / next_states (B, W, 5A) through stream_tile (the render kernel's
 // phase 2), actions (B, A), rewards (B), dones (B).  Logical index i in [0, size) is ring slot (start + i) mod C.  An
-// index outside [0, size) reads nothing of the ring: its rows are NaN and it counts into errors[0].
+// index outside [0, size) reads nothing of the ring: its rows are NaN and it counts into errors[0].  With a cursor
+// (fe_replay_sample_c) start and size are the cursor's.
 template <int VEC, bool SINGLE>
 __global__ __launch_bounds__(kBlock) void fe_replay_sample_kernel(const Params p, const ReplayRing r,
                                                                   const int64_t *__restrict__ indices, int64_t start,
                                                                   int64_t size, float *states, float *next_states,
                                                                   float *actions, float *rewards, float *dones,
-                                                                  unsigned long long *errors) {
+                                                                  unsigned long long *errors,
+                                                                  const int64_t *__restrict__ cursor) {
     extern __shared__ __align__(16) unsigned char smem[];
+    ring_window(cursor, r.C, start, size);
     const int A = SINGLE ? 1 : p.A;
     const int EB = p.EB;
     const TileLds ls = carve_lds(smem + 4 * kStageBytes, EB, EB * A);

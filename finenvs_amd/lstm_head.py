@@ -267,15 +267,21 @@ def td3_actor_loss(head: FusedLSTMHead, buffer, indices: torch.Tensor, twin) -> 
     """``Actor.compute_loss`` (TD3/actor.py:50-56) on the transitions ``indices`` (logical, (B,)) of ``buffer``:
     ``-twin.q(src, pos, head(src, pos))[0].mean()`` on the ring's state descriptors, nothing rendered (the reference
     passes its first critic).  ``backward()`` also accumulates into that critic's ``.grad`` unless it is frozen (as in
-    torch); an index outside ``[0, size)`` makes the loss NaN."""
+    torch); an index outside ``[0, size)`` makes the loss NaN.  ``indices`` may be a ``ReplayDraw`` of a ``cursor=True``
+    buffer (no host integer enters then: capturable)."""
     from .critic import FusedTwinCritic
+    from .replay import as_draw
 
+    draw = as_draw(buffer, indices, "td3_actor_loss")
     if not isinstance(twin, FusedTwinCritic) or twin.env is not head.env:
         raise ValueError("twin must be a FusedTwinCritic of this head's env")
     if indices is None:
         raise ValueError("td3_actor_loss needs the indices of the sampled transitions")
-    idx = twin._indices(buffer, indices, None)
+    idx = twin._indices(buffer, indices if draw is None else draw.indices, None)
     B = int(idx.numel())
+    if draw is not None:  # the draw's gathered descriptors; its indices are in range by construction
+        src, pos = draw.state_src, draw.state_pos.reshape(B)
+        return -twin.q(src, pos, head(src, pos))[0].mean()
     slots = buffer.physical(idx)
     src, pos = buffer.state_src[slots], buffer.state_pos[slots].reshape(B)
     q = twin.q(src, pos, head(src, pos))[0]

@@ -14,15 +14,23 @@ OPB's row i (the i-th oldest retained transition; within one store, env order) a
 ``(head - size + i) mod max_size`` -- ``physical_index`` below, which the CPU tests check against the reference.
 
 One divergence from OPB: a single store of more than ``max_size`` transitions (num_envs > max_size) is refused (OPB
-would keep its last ``max_size`` rows)."""
+would keep its last ``max_size`` rows).
+
+``ReplayBuffer(env, max_size, cursor=True)`` also keeps ``head``, ``size`` and a draw counter in 32 bytes of device
+memory (the CURSOR, include/finenvs_amd_replay_cursor.h): every store mirrors the host's integers into it, and
+``draw(B)`` draws a mini-batch's logical indices on the device from it and gathers their descriptors in one launch
+(``fe_ring_draw``).  Nothing on that path depends on a host integer, so an update iteration captured as a hipGraph
+(finenvs_amd/graphed.py) follows the ring while transitions are stored between its replays."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
+from .rng import philox_u32
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -34,6 +42,43 @@ def physical_index(indices, head: int, size: int, capacity: int):
     """Ring slot of logical index i (the i-th oldest of the ``size`` retained transitions): (head - size + i) mod C.
     Works on ints, numpy arrays and torch tensors alike."""
     return (indices + (head - size) % capacity) % capacity
+
+
+def draw_indices(seed: int, first_draw: int, size: int, count: int) -> List[int]:
+    """Host mirror of ``fe_ring_draw``'s index rule: draw ``first_draw + b`` of the stream ``seed`` is logical index
+    ``(philox_u32(seed, first_draw + b) * size) >> 32`` (``rng.redraw_day``'s multiply-shift), in ``[0, size)``."""
+    size, first = int(size), int(first_draw)
+    if size < 1:
+        raise ValueError(f"cannot draw from {size} transitions")
+    return [(philox_u32(seed, first + b) * size) >> 32 for b in range(int(count))]
+
+
+@dataclass
+class ReplayDraw:
+    """One mini-batch drawn on the device (``ReplayBuffer.draw``): the B logical ``indices`` (B,) int64 and the
+    transitions gathered at them -- ``state_src`` (B,) int64 / ``state_pos`` (B, A) float64, ``next_src`` / ``next_pos``,
+    ``actions`` (B, A), ``rewards`` (B,), ``dones`` (B,) float32.  The fused consumers take it where they take
+    ``indices``."""
+
+    indices: torch.Tensor
+    state_src: torch.Tensor
+    state_pos: torch.Tensor
+    next_src: torch.Tensor
+    next_pos: torch.Tensor
+    actions: torch.Tensor
+    rewards: torch.Tensor
+    dones: torch.Tensor
+
+
+def as_draw(buffer, indices, who: str) -> Optional[ReplayDraw]:
+    """``indices`` if it is a ``ReplayDraw`` (of a ``cursor=True`` buffer: ValueError otherwise, before any device
+    work), else None."""
+    if not isinstance(indices, ReplayDraw):
+        return None
+    if getattr(buffer, "cursor", None) is None:
+        raise ValueError(f"{who}: a ReplayDraw needs a ReplayBuffer(cursor=True) -- this buffer keeps head and size on "
+                         "the host only; pass draw.indices to use the by-value path")
+    return indices
 
 
 class RingIndex:
@@ -113,9 +158,14 @@ def check_transition(N: int, A: int, device, states, actions, rewards, next_stat
 # ---------------------------------------------------------------- the ring
 class ReplayBuffer:
     """OPB's ``Buffer`` for a ``TimeSeriesEnv``: ``store`` / ``get_mini_batch`` / ``size`` with the reference's
-    signatures; states are descriptor pairs ``(obs_src (N,) int64, obs_pos (N, A) float64)``."""
+    signatures; states are descriptor pairs ``(obs_src (N,) int64, obs_pos (N, A) float64)``.
 
-    def __init__(self, env, max_size: int = 1_000_000):
+    ``cursor=True``: the ring's ``head`` / ``size`` are mirrored into ``self.cursor`` ((4,) int64 on the device: head,
+    size, draws, ticket) by every store (``fe_replay_append_c``) and ``draw`` samples from it; ``seed`` fixes the draw
+    stream.  ``self.draws`` is the HOST's mirror of the draw counter, advanced by B per ``draw`` call: a replayed
+    graph that contains a draw advances only the device's counter (``self.cursor[2]``)."""
+
+    def __init__(self, env, max_size: int = 1_000_000, cursor: bool = False, seed: int = 0):
         self.env = env
         self.N, self.A, self.W = int(env.num_envs), int(env.num_assets), int(env.num_intervals)
         self._ring = RingIndex(max_size)
@@ -137,6 +187,9 @@ class ReplayBuffer:
             C_, A, 0, self.state_src.data_ptr(), self.state_pos.data_ptr(), self.next_src.data_ptr(),
             self.next_pos.data_ptr(), self.actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(),
             self.errors.data_ptr())
+        self.cursor = torch.zeros((_lib.CURSOR_WORDS,), dtype=torch.int64, device=dev) if cursor else None
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.draws = 0
 
     # ---------------------------------------------------------------- bookkeeping
     @property
@@ -155,6 +208,8 @@ class ReplayBuffer:
 
     def clear(self) -> None:
         self._ring.clear()
+        if self.cursor is not None:  # head and size; the draw counter goes on
+            self.cursor[:_lib.CURSOR_DRAWS].zero_()
 
     def physical(self, indices):
         """Ring slots of logical indices (see ``physical_index``)."""
@@ -200,11 +255,52 @@ class ReplayBuffer:
     def _append(self, steps, N, ld, first, count, s_src, s_pos, n_src, n_pos, act, rew, done) -> None:
         # transitions before `first` would have been overwritten: the kept ones go to the slots they would occupy
         head = (self.head + first) % self.max_size
-        _lib.check(self._lib.fe_replay_append(
-            C.byref(self._desc), head, steps, N, ld, first, count, s_src.data_ptr(), s_pos.data_ptr(),
-            n_src.data_ptr(), n_pos.data_ptr(), act.data_ptr(), int(act.dtype is torch.float64), rew.data_ptr(),
-            done.data_ptr(), self._stream()), self._lib)
+        args = (C.byref(self._desc), head, steps, N, ld, first, count, s_src.data_ptr(), s_pos.data_ptr(),
+                n_src.data_ptr(), n_pos.data_ptr(), act.data_ptr(), int(act.dtype is torch.float64), rew.data_ptr(),
+                done.data_ptr())
+        if self.cursor is None:
+            _lib.check(self._lib.fe_replay_append(*args, self._stream()), self._lib)
+        else:  # the same launch leaves the new head and size in the cursor
+            new_size = min(self.size() + first + count, self.max_size)
+            _lib.check(self._lib.fe_replay_append_c(*args, self.cursor.data_ptr(), new_size, self._stream()), self._lib)
         self._ring.advance(first + count)
+
+    # ---------------------------------------------------------------- the draw on the device
+    def new_draw(self, size: int) -> ReplayDraw:
+        """Uninitialised tensors of a ``size``-transition draw, for ``draw(size, out=)``: nothing is launched."""
+        B, A, dev = int(size), self.A, self.device
+        if B < 0:
+            raise ValueError(f"cannot draw {B} transitions")
+        return ReplayDraw(torch.empty((B,), dtype=torch.int64, device=dev),
+                          torch.empty((B,), dtype=torch.int64, device=dev),
+                          torch.empty((B, A), dtype=torch.float64, device=dev),
+                          torch.empty((B,), dtype=torch.int64, device=dev),
+                          torch.empty((B, A), dtype=torch.float64, device=dev),
+                          torch.empty((B, A), dtype=torch.float32, device=dev),
+                          torch.empty((B,), dtype=torch.float32, device=dev),
+                          torch.empty((B,), dtype=torch.float32, device=dev))
+
+    def draw(self, size: int, out: Optional[ReplayDraw] = None) -> ReplayDraw:
+        """A mini-batch of ``size`` transitions drawn on the device, in one launch (``fe_ring_draw``): index b is
+        ``draw_indices(self.seed, draws, size(), B)[b]`` with ``draws`` the device's counter, which the launch advances
+        by B.  ``out``: a previous draw of the same B whose tensors are written again (what a captured graph needs).
+        Capturable: nothing here reads ``head`` or ``size()`` on the host except the refusal of an empty ring."""
+        if self.cursor is None:
+            raise ValueError("draw() needs ReplayBuffer(cursor=True)")
+        self._ring.check_sample()
+        B, A, dev = int(size), self.A, self.device
+        if B < 0:
+            raise ValueError(f"cannot draw {B} transitions")
+        if out is None:
+            out = self.new_draw(B)
+        elif not isinstance(out, ReplayDraw) or tuple(out.indices.shape) != (B,) or out.indices.device != dev:
+            raise ValueError(f"out must be a ReplayDraw of {B} transitions on {dev}")
+        _lib.check(self._lib.fe_ring_draw(
+            C.byref(self._desc), self.cursor.data_ptr(), self.seed, B, out.indices.data_ptr(), out.state_src.data_ptr(),
+            out.state_pos.data_ptr(), out.next_src.data_ptr(), out.next_pos.data_ptr(), out.actions.data_ptr(),
+            out.rewards.data_ptr(), out.dones.data_ptr(), self._stream()), self._lib)
+        self.draws += B
+        return out
 
     # ---------------------------------------------------------------- sampling (OPB:68-77)
     def get_mini_batch(self, size: int, indices: Optional[torch.Tensor] = None, check: bool = False
@@ -212,8 +308,12 @@ class ReplayBuffer:
         """OPB's mini-batch: {"states" (B, W, 5A), "actions" (B, A), "rewards" (B, 1), "next_states" (B, W, 5A),
         "dones" (B, 1)}, all float32, in one launch.  ``indices`` (B,) logical indices; by default the very draw OPB:69
         makes, ``torch.randint(0, self.size(), (size,), device=...)``, so the same torch seed picks the same transitions.
-        An index outside [0, size()) yields NaN rows; ``check=True`` then raises (one host sync)."""
+        An index outside [0, size()) yields NaN rows; ``check=True`` then raises (one host sync).  ``indices`` may be
+        a ``ReplayDraw`` of this buffer: head and size are then read from the cursor (``fe_replay_sample_c``)."""
+        draw = as_draw(self, indices, "get_mini_batch")
         self._ring.check_sample()
+        if draw is not None:
+            indices = draw.indices
         if indices is None:
             indices = torch.randint(0, self.size(), (int(size),), device=self.device)
         else:
@@ -234,10 +334,14 @@ class ReplayBuffer:
         if check:
             self.errors.zero_()
         if B:
-            _lib.check(self._lib.fe_replay_sample(
-                self.env._handle, C.byref(self._desc), self.head, self.size(), indices.data_ptr(), B,
-                out["states"].data_ptr(), out["next_states"].data_ptr(), out["actions"].data_ptr(),
-                out["rewards"].data_ptr(), out["dones"].data_ptr(), self._stream()), self._lib)
+            outs = (out["states"].data_ptr(), out["next_states"].data_ptr(), out["actions"].data_ptr(),
+                    out["rewards"].data_ptr(), out["dones"].data_ptr(), self._stream())
+            if draw is None:
+                _lib.check(self._lib.fe_replay_sample(
+                    self.env._handle, C.byref(self._desc), self.head, self.size(), indices.data_ptr(), B, *outs), self._lib)
+            else:
+                _lib.check(self._lib.fe_replay_sample_c(
+                    self.env._handle, C.byref(self._desc), self.cursor.data_ptr(), indices.data_ptr(), B, *outs), self._lib)
         if check:
             bad = int(self.errors.item())
             if bad:

@@ -366,23 +366,31 @@ class FusedSACRollout(_FusedEvaluation):
         examples/sac_time_series.py writes the detached form ``-(q - alpha.detach() * mean_log_probs).mean()``: the same
         value and the same actor gradients, without that stray temperature gradient.  ``backward()`` of the actor loss
         also accumulates into the critics' ``.grad`` unless they are frozen (as in torch); an index outside
-        ``[0, size)`` makes the actor loss NaN."""
+        ``[0, size)`` makes the actor loss NaN.  ``indices`` may be a ``ReplayDraw`` of a ``cursor=True`` buffer (no
+        host integer enters then: capturable)."""
         from .critic import FusedTwinCritic
+        from .replay import as_draw
 
+        draw = as_draw(buffer, indices, "actor_losses")
         if not isinstance(twin, FusedTwinCritic) or twin.env is not self.env:
             raise ValueError("twin must be a FusedTwinCritic of this rollout's env")
         if indices is None:
             raise ValueError("actor_losses needs the indices of the sampled transitions")
-        idx = twin._indices(buffer, indices, None)
+        idx = twin._indices(buffer, indices if draw is None else draw.indices, None)
         B = int(idx.numel())
         if noise is None:
             noise = torch.randn((B, 1), device=self.env._dev)
-        slots = buffer.physical(idx)
-        src, pos = buffer.state_src[slots], buffer.state_pos[slots].reshape(B)
-        actions, log_probs = self.sample(src, pos, noise)
-        q = torch.min(*twin.q(src, pos, actions))
-        valid = ((idx >= 0) & (idx < buffer.size())).reshape(B, 1)
-        q = torch.where(valid, q, torch.full((), float("nan"), device=q.device))
+        if draw is not None:  # the draw's gathered descriptors; its indices are in range by construction
+            src, pos = draw.state_src, draw.state_pos.reshape(B)
+            actions, log_probs = self.sample(src, pos, noise)
+            q = torch.min(*twin.q(src, pos, actions))
+        else:
+            slots = buffer.physical(idx)
+            src, pos = buffer.state_src[slots], buffer.state_pos[slots].reshape(B)
+            actions, log_probs = self.sample(src, pos, noise)
+            q = torch.min(*twin.q(src, pos, actions))
+            valid = ((idx >= 0) & (idx < buffer.size())).reshape(B, 1)
+            q = torch.where(valid, q, torch.full((), float("nan"), device=q.device))
         mean_log_probs = log_probs.mean(dim=1, keepdim=True)
         log_alpha = self.actor.log_alpha
         actor_loss = -(q + -log_alpha.exp() * mean_log_probs).mean()
