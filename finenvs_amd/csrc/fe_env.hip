@@ -25,7 +25,7 @@
 // iterations with 4 (f64) / 6 (f32) workgroups per CU, and the first tile's table
 // loads are issued before its accounting.
 //
-// One translation unit, fourteen files:
+// One translation unit, these files:
 //   fe_device_common.h    constants / build knobs, Params, Philox, sleeve accounting, LDS tile layout, input loads
 //   fe_store_policy.h     host only: which launches of a large single-asset env stream past the Infinity Cache
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
@@ -38,6 +38,7 @@
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_ring_draw_kernels.h  a mini-batch drawn and gathered from the ring's device cursor (capturable updates)
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
+//   fe_bptt_tile.h            the stages of one backward-through-time tile that the three backward passes below share
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
 //   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
 //   fe_lstm_grad_kernels.h    the one-output LSTM head's backward pass (PPO actor / critic, TD3 actor) and its reduction
@@ -878,6 +879,29 @@ static int launch_resident(const fe_env *env, const void *kern, size_t lds, Para
     return launched(what, hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kLstmBlock), args, lds, (hipStream_t)stream));
 }
 
+// The fused backward passes (fe_bptt_tile.h): 32-pair tiles, and the workgroups that own partials and a stash in the
+// workspace -- one per tile up to `cap`, the kernel's resident count on an MI355X.
+struct GradTiles { int64_t tiles, max_groups; };
+static GradTiles grad_tiles(int64_t count, int64_t cap) {
+    const int64_t tiles = (count + 31) / 32;
+    return {tiles, tiles < cap ? tiles : cap};
+}
+
+// Their main pass: resident kBpttBlock-thread workgroups, at most max_groups per grid row (`rows` rows share the
+// device), each looping over its tiles.  `g` is the kernel's one argument, *groups its field for the row length.
+// `what` names the kernel in a preparation error, `step` the launch.
+static int launch_grad(const fe_env *env, const void *kern, size_t lds, int64_t max_groups, int rows, void *g,
+                       int64_t *groups, const char *what, const char *step, void *stream) {
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kBpttBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, what);
+    int64_t resident = (int64_t)env->cus * per_cu / rows;
+    if (resident < 1) resident = 1;
+    *groups = max_groups < resident ? max_groups : resident;
+    void *args[] = {g};
+    return launched(step, hipLaunchKernel(kern, dim3((unsigned)*groups, rows), dim3(kBpttBlock), args, lds, (hipStream_t)stream));
+}
+
 // Shared by fe_env_rollout_lstm and fe_lstm_forward: geometry, kernel choice, launch.  `count` = envs (rollout) or
 // descriptors (forward).
 static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who, void *stream) {
@@ -1607,9 +1631,8 @@ int fe_twin_q_target_c(fe_env *env, const float *logret_f32, const fe_critic_wei
 // Workspace: [wt of each critic][partials of each critic][stash of each critic][da of each critic].
 int64_t fe_twin_q_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
     if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t groups = tiles < critic_grad_max_groups(H) ? tiles : critic_grad_max_groups(H);
-    return 2 * (critic_grad_wt_floats(H) + groups * (critic_grad_part_floats(H) + critic_grad_stash_floats(H, W))) +
+    const int64_t groups = grad_tiles(count, critic_grad_max_groups(H)).max_groups;
+    return 2 * (critic_grad_wt_floats(H) + groups * (critic_grad_part_floats(H) + bptt_stash_floats(H, W))) +
            2 * count;
 }
 
@@ -1634,8 +1657,7 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t max_groups = tiles < critic_grad_max_groups(H) ? tiles : critic_grad_max_groups(H);
+    const auto [tiles, max_groups] = grad_tiles(count, critic_grad_max_groups(H));
     CriticGradArgs g;
     memset(&g, 0, sizeof(g));
     g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos; g.actions = actions;
@@ -1645,14 +1667,14 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
     const float *dq[2] = {dq1, dq2};
     float *wt = workspace, *part = wt + 2 * critic_grad_wt_floats(H);
     float *stash = part + 2 * max_groups * critic_grad_part_floats(H);
-    float *da = stash + 2 * max_groups * critic_grad_stash_floats(H, W);
+    float *da = stash + 2 * max_groups * bptt_stash_floats(H, W);
     for (int i = 0; i < 2; ++i) {
         if (!dq[i]) continue;
         CriticGradNet &n = g.net[g.ncrit];
         n.whh = cw[i]->whh; n.wx = cw[i]->wx; n.wout = cw[i]->wout; n.dq = dq[i];
         n.wt = wt + g.ncrit * critic_grad_wt_floats(H);
         n.part = part + g.ncrit * max_groups * critic_grad_part_floats(H);
-        n.stash = stash + g.ncrit * max_groups * critic_grad_stash_floats(H, W);
+        n.stash = stash + g.ncrit * max_groups * bptt_stash_floats(H, W);
         n.da = da + g.ncrit * count;
         if (cg[i]) {
             n.g_wih = cg[i]->w_ih; n.g_whh = cg[i]->w_hh; n.g_bih = cg[i]->b_ih; n.g_bhh = cg[i]->b_hh;
@@ -1669,16 +1691,9 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
     if (int rc = launched("fe_twin_q_backward: weight transpose")) return rc;
     const void *kern = H == 32 ? (const void *)fe_critic_grad_kernel<1>
                                : (H == 64 ? (const void *)fe_critic_grad_kernel<2> : (const void *)fe_critic_grad_kernel<4>);
-    const size_t lds = critic_grad_lds_bytes(H);
-    int per_cu = 0;
-    const hipError_t he = prepare_kernel(env->device, kern, kCriticGradBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "critic gradient kernel: hipFuncSetAttribute / occupancy query");
-    int64_t resident = (int64_t)env->cus * per_cu / g.ncrit;
-    if (resident < 1) resident = 1;
-    g.groups = max_groups < resident ? max_groups : resident;
-    void *args[] = {&g};
-    if (int rc = launched("fe_twin_q_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups, g.ncrit),
-                                                                          dim3(kCriticGradBlock), args, lds, (hipStream_t)stream)))
+    if (int rc = launch_grad(env, kern, critic_grad_lds_bytes(H), max_groups, g.ncrit, &g, &g.groups,
+                             "critic gradient kernel: hipFuncSetAttribute / occupancy query", "fe_twin_q_backward: backward",
+                             stream))
         return rc;
     const int64_t elems = 4LL * H * (H + 32) + H + 1;
     const int64_t work = elems > count ? elems : count;
@@ -1691,9 +1706,8 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
 // Workspace: [W_hh^T | W_l^T][partials of every workgroup][stash of every workgroup].
 int64_t fe_sac_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
     if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t groups = tiles < sac_grad_max_groups(H) ? tiles : sac_grad_max_groups(H);
-    return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + sac_grad_stash_floats(H, W));
+    const int64_t groups = grad_tiles(count, sac_grad_max_groups(H)).max_groups;
+    return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + bptt_stash_floats(H, W));
 }
 
 static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
@@ -1719,8 +1733,7 @@ static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t max_groups = tiles < sac_grad_max_groups(H) ? tiles : sac_grad_max_groups(H);
+    const auto [tiles, max_groups] = grad_tiles(count, sac_grad_max_groups(H));
     SacGradArgs g;
     memset(&g, 0, sizeof(g));
     g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
@@ -1737,15 +1750,8 @@ static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *
     if (int rc = launched("fe_sac_backward: weight transpose")) return rc;
     const void *kern = H == 32 ? (const void *)fe_sac_grad_kernel<1>
                                : (H == 64 ? (const void *)fe_sac_grad_kernel<2> : (const void *)fe_sac_grad_kernel<4>);
-    int per_cu = 0;
-    const hipError_t he = prepare_kernel(env->device, kern, kSacGradBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "SAC gradient kernel: hipFuncSetAttribute / occupancy query");
-    int64_t resident = (int64_t)env->cus * per_cu;
-    if (resident < 1) resident = 1;
-    g.groups = max_groups < resident ? max_groups : resident;
-    void *args[] = {&g};
-    if (int rc = launched("fe_sac_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups), dim3(kSacGradBlock),
-                                                                       args, lds, (hipStream_t)stream)))
+    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
+                             "SAC gradient kernel: hipFuncSetAttribute / occupancy query", "fe_sac_backward: backward", stream))
         return rc;
     hipLaunchKernelGGL(fe_sac_grad_reduce_kernel, dim3(grid_for(sac_grad_part_floats(H))), dim3(kBlock), 0,
                        (hipStream_t)stream, g, H);
@@ -1766,9 +1772,8 @@ int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, cons
 // Workspace: [W_hh^T][partials of every workgroup][stash of every workgroup].
 int64_t fe_lstm_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
     if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t groups = tiles < lstm_grad_max_groups(H) ? tiles : lstm_grad_max_groups(H);
-    return lstm_grad_wt_floats(H) + groups * (lstm_grad_part_floats(H) + lstm_grad_stash_floats(H, W));
+    const int64_t groups = grad_tiles(count, lstm_grad_max_groups(H)).max_groups;
+    return lstm_grad_wt_floats(H) + groups * (lstm_grad_part_floats(H) + bptt_stash_floats(H, W));
 }
 
 int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
@@ -1797,8 +1802,7 @@ int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, con
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
-    const int64_t tiles = (count + 31) / 32;
-    const int64_t max_groups = tiles < lstm_grad_max_groups(H) ? tiles : lstm_grad_max_groups(H);
+    const auto [tiles, max_groups] = grad_tiles(count, lstm_grad_max_groups(H));
     LstmGradArgs g;
     memset(&g, 0, sizeof(g));
     g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
@@ -1814,15 +1818,9 @@ int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, con
     if (int rc = launched("fe_lstm_backward: weight transpose")) return rc;
     const void *kern = H == 32 ? (const void *)fe_lstm_grad_kernel<1>
                                : (H == 64 ? (const void *)fe_lstm_grad_kernel<2> : (const void *)fe_lstm_grad_kernel<4>);
-    int per_cu = 0;
-    const hipError_t he = prepare_kernel(env->device, kern, kLstmGradBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query");
-    int64_t resident = (int64_t)env->cus * per_cu;
-    if (resident < 1) resident = 1;
-    g.groups = max_groups < resident ? max_groups : resident;
-    void *args[] = {&g};
-    if (int rc = launched("fe_lstm_backward: backward", hipLaunchKernel(kern, dim3((unsigned)g.groups), dim3(kLstmGradBlock),
-                                                                        args, lds, (hipStream_t)stream)))
+    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
+                             "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query", "fe_lstm_backward: backward",
+                             stream))
         return rc;
     hipLaunchKernelGGL(fe_lstm_grad_reduce_kernel, dim3(grid_for(lstm_grad_part_floats(H))), dim3(kBlock), 0,
                        (hipStream_t)stream, g, H);

@@ -2,33 +2,23 @@
 // one-output LSTM head (PPO's actor and critic, TD3's actor) on observation descriptors
 // (include/finenvs_amd_lstm_grad.h).
 #pragma once
-#include "fe_device_common.h"
-#include "fe_lstm_kernel.h"
+#include "fe_bptt_tile.h"
 
 namespace {
 
 // ---- d(loss) / d(parameters) of LSTMNetwork((5, H, 1), W, Tanh | Identity) (networks/lstm.py:28-57) ----
-// fe_sac_grad_kernel with a one-output head: no W_l stage, no W_l^T.  One workgroup (4 wavefronts) runs grid-strided
-// 32-pair tiles.  Per tile:
-//   forward   the recurrence of fe_lstm_forward recomputed with the SAME contraction (gate rows in packed order on the
-//             M side of v_mfma_f32_32x32x2_f32, the 32 pairs on N, k order x then h, lstm_act2, the same cell update):
-//             activated gates and c_t into the workgroup's stash, [h_{t-1} | x_t] as well, h_t to LDS;
+// The tile of fe_bptt_tile.h with a one-output head and a 5-wide input:
 //   head      in-lane, one lane per pair, from the forward's own y = outputs[n] and g = d_outputs[n]:
 //               dp = g (1 - y^2) (tanh) or g (none);   dh_W = w_out dp;   d w_out += dp h_W,  d b_out += dp;
-//   backward  t = W-1 .. 0 as fe_sac_grad_kernel: dz_t in-lane, then dh_{t-1} = W_hh^T dz_t on the matrix cores
-//             (W_hh^T from the pack kernel).  The input has no learnt column, so dx_t is never formed;
-//   weights   [dW_hh | dW_x] += dz [h_{t-1} | x_t]^T, x_t = (4 log-returns, position, 1 for the bias, 0 ...).
-// Every workgroup writes its own partial sums; fe_lstm_grad_reduce_kernel adds them in workgroup order and writes them in
-// torch's row order and layout (the inverse of lstm_row_order applied while writing).  No float atomics.
-constexpr int kLstmGradBlock = 256;
+//   backward  dh_{t-1} = W_hh^T dz_t only: the input has no learnt column, so dx_t is never formed.
+// fe_lstm_grad_reduce_kernel writes the sums in torch's row order and layout (the inverse of lstm_row_order applied
+// while writing).
+constexpr int kLstmGradBlock = kBpttBlock;
 
 // the resident workgroup count of fe_lstm_grad_kernel on an MI355X (256 CUs; at H = 128 the LDS admits one per CU)
 __host__ __device__ constexpr int64_t lstm_grad_max_groups(int H) { return H == 128 ? 256 : 512; }
 // [4H x (H + 32) LSTM tiles][d w_out (H) | d b_out | pad]
 __host__ __device__ constexpr int64_t lstm_grad_part_floats(int H) { return 4LL * H * (H + 32) + H + 32; }
-__host__ __device__ constexpr int64_t lstm_grad_stash_floats(int H, int W) {
-    return (int64_t)W * (160LL * H + 32LL * (H + 32));
-}
 // W_hh^T (H, 4H)
 __host__ __device__ constexpr int64_t lstm_grad_wt_floats(int H) { return 4LL * H * H; }
 // LDS of one workgroup: 22 528 B at H = 32, 43 136 B at 64, 84 352 B at 128 (one workgroup per CU there)
@@ -47,7 +37,7 @@ struct LstmGradArgs {
     const float *d_outputs;        // (count) upstream gradient
     float *wt;     // (H, 4H) W_hh^T in packed gate-row order
     float *part;   // (groups, lstm_grad_part_floats(H))
-    float *stash;  // (groups, lstm_grad_stash_floats(H, W))
+    float *stash;  // (groups, bptt_stash_floats(H, W))
     int64_t count, num_tiles, groups;
     int32_t W, out_act;
     // fe_lstm_grad_reduce_kernel's outputs, torch row order and layout (include/finenvs_amd_lstm_grad.h)
@@ -65,8 +55,8 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_grad_pack_kernel(const LstmGra
 
 template <int NT>
 __global__ __launch_bounds__(kLstmGradBlock) void fe_lstm_grad_kernel(const LstmGradArgs g) {
-    constexpr int H = 32 * NT, MT = H / 8, MPW = MT / 4, NG = H / 8, G4 = 4 * H, ZT = H / 32;
-    constexpr int HPF = H + 4, G4P = G4 + 4, NTO = H / 32 + 1, VN = H + 32;
+    constexpr int H = 32 * NT, MPW = H / 32, G4 = 4 * H, ZT = H / 32;
+    constexpr int HPF = H + 4, G4P = G4 + 4, VN = H + 32;
     constexpr int PV = 4 * H * VN;  // the head's vector in the partials
     static_assert(2 * 32 * HPF <= 32 * G4P, "the h double buffer shares the dz buffer");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -79,7 +69,7 @@ __global__ __launch_bounds__(kLstmGradBlock) void fe_lstm_grad_kernel(const Lstm
     int64_t *s_src = reinterpret_cast<int64_t *>(s_xh + 32);  // [32]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
     float *part = g.part + blockIdx.x * lstm_grad_part_floats(H);
-    float *stash = g.stash + blockIdx.x * lstm_grad_stash_floats(H, W);
+    float *stash = g.stash + blockIdx.x * bptt_stash_floats(H, W);
     float *vst = stash + (int64_t)W * 160 * H;  // [W][32][VN]: [h_{t-1} | x_t | 0] per pair
     for (int i = tid; i < H; i += kLstmGradBlock) s_wout[i] = g.wout[i];
 
@@ -102,12 +92,7 @@ __global__ __launch_bounds__(kLstmGradBlock) void fe_lstm_grad_kernel(const Lstm
             s_dp[tid] = dp;
         }
         __syncthreads();
-        for (int i = tid; i < W * 32 * 32; i += kLstmGradBlock) {  // x_t and h_{-1} = 0 into the stash
-            const int t = i >> 10, p = (i >> 5) & 31, j = i & 31;
-            const float v = j < 4 ? g.lr32[s_src[p] + 4 * t + j] : (j == 4 ? s_xh[p].x : (j == 5 ? 1.0f : 0.0f));
-            vst[((int64_t)t * 32 + p) * VN + H + j] = v;
-        }
-        for (int i = tid; i < 32 * H; i += kLstmGradBlock) vst[(i / H) * VN + i % H] = 0.0f;
+        bptt_stash_inputs<H, false>(vst, g.lr32, s_src, s_xh, W, tid);
 
         // ---- forward: fe_lstm_forward's recurrence, the activations into the stash ----
         float cst[MPW][4];
@@ -118,64 +103,7 @@ __global__ __launch_bounds__(kLstmGradBlock) void fe_lstm_grad_kernel(const Lstm
         const float *xsrc = g.lr32 + s_src[col];
         const float4 xhc = s_xh[col];
         for (int t = 0; t < W; ++t) {
-            const float *hprev = s_x + ((t + 1) & 1) * 32 * HPF;
-            float *hnext = s_x + (t & 1) * 32 * HPF;
-            float *slot = stash + (int64_t)t * 160 * H;
-            const float4 xc = half == 0 ? *reinterpret_cast<const float4 *>(xsrc + 4 * t) : xhc;
-#pragma unroll
-            for (int i = 0; i < MPW; ++i) {
-                const int mt = wave + 4 * i;
-                const size_t R = (size_t)32 * mt + col;
-                const float4 wxv = *reinterpret_cast<const float4 *>(g.wx + R * 8 + 4 * half);
-                f32x16 acc;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) acc[rr] = 0.0f;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    const float xs = m == 0 ? xc.x : (m == 1 ? xc.y : (m == 2 ? xc.z : xc.w));
-                    const float ws = m == 0 ? wxv.x : (m == 1 ? wxv.y : (m == 2 ? wxv.z : wxv.w));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, xs, acc, 0, 0, 0);
-                }
-                if (t > 0) {
-#pragma unroll 4
-                    for (int gg = 0; gg < NG; ++gg) {
-                        const float4 wv = *reinterpret_cast<const float4 *>(g.whh + R * H + 8 * gg + 4 * half);
-                        const float4 hb = *reinterpret_cast<const float4 *>(hprev + col * HPF + 8 * gg + 4 * half);
-#pragma unroll
-                        for (int m = 0; m < 4; ++m) {
-                            const float ws = m == 0 ? wv.x : (m == 1 ? wv.y : (m == 2 ? wv.z : wv.w));
-                            const float hs = m == 0 ? hb.x : (m == 1 ? hb.y : (m == 2 ? hb.z : hb.w));
-                            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, hs, acc, 0, 0, 0);
-                        }
-                    }
-                }
-                // the cell update of fe_lstm_rollout_body.h: acc[4b + gate] is unit 8 mt + 4 half + b of pair col
-                float hv[4], og[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const v2f sif = lstm_act2<false, false>((v2f){acc[4 * b + 0], acc[4 * b + 1]});
-                    const v2f tgo = lstm_act2<true, false>((v2f){acc[4 * b + 2], acc[4 * b + 3]});
-                    const float t1 = sif.y * cst[i][b];
-                    const float t2 = sif.x * tgo.x;
-                    cst[i][b] = t1 + t2;
-                    og[b] = tgo.y;
-                    float *gs = slot + (mt * 16 + 4 * b) * 64 + lane;
-                    gs[0] = sif.x;
-                    gs[64] = sif.y;
-                    gs[128] = tgo.x;
-                    gs[192] = tgo.y;
-                    slot[128 * H + (mt * 4 + b) * 64 + lane] = cst[i][b];
-                }
-#pragma unroll
-                for (int b = 0; b < 4; b += 2) {
-                    const v2f tc = lstm_act2<true, true>((v2f){cst[i][b], cst[i][b + 1]});
-                    hv[b] = og[b] * tc.x;
-                    hv[b + 1] = og[b + 1] * tc.y;
-                }
-                const float4 h4 = make_float4(hv[0], hv[1], hv[2], hv[3]);
-                *reinterpret_cast<float4 *>(hnext + col * HPF + 8 * mt + 4 * half) = h4;
-                if (t + 1 < W) *reinterpret_cast<float4 *>(vst + ((int64_t)(t + 1) * 32 + col) * VN + 8 * mt + 4 * half) = h4;
-            }
+            bptt_forward_step<H>(t, W, g.whh, g.wx, xsrc, xhc, s_x, stash, vst, cst, wave, lane, col, half);
             __syncthreads();  // h_t is complete
         }
 
@@ -199,86 +127,16 @@ __global__ __launch_bounds__(kLstmGradBlock) void fe_lstm_grad_kernel(const Lstm
 #pragma unroll
             for (int b = 0; b < 4; ++b) dc[i][b] = 0.0f;
         for (int t = W - 1; t >= 0; --t) {
-            float *slot = stash + (int64_t)t * 160 * H;
-            const float *pslot = stash + (int64_t)(t - 1) * 160 * H;
-#pragma unroll
-            for (int i = 0; i < MPW; ++i) {
-                const int mt = wave + 4 * i;
-                const float4 dh4 = *reinterpret_cast<const float4 *>(s_dh + col * HPF + 8 * mt + 4 * half);
-                const float dh[4] = {dh4.x, dh4.y, dh4.z, dh4.w};
-                float cc[4], cp[4];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    cc[b] = slot[128 * H + (mt * 4 + b) * 64 + lane];
-                    cp[b] = t > 0 ? pslot[128 * H + (mt * 4 + b) * 64 + lane] : 0.0f;
-                }
-#pragma unroll
-                for (int b = 0; b < 4; b += 2) {
-                    const v2f tc = lstm_act2<true, true>((v2f){cc[b], cc[b + 1]});
-#pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {
-                        const int u = b + bb;
-                        const float tcu = bb == 0 ? tc.x : tc.y;
-                        const float *gs = slot + (mt * 16 + 4 * u) * 64 + lane;
-                        const float ig = gs[0], fg = gs[64], gg = gs[128], og = gs[192];
-                        const float dcc = dc[i][u] + dh[u] * og * (1.0f - tcu * tcu);
-                        const float4 dz = make_float4(dcc * gg * ig * (1.0f - ig), dcc * cp[u] * fg * (1.0f - fg),
-                                                      dcc * ig * (1.0f - gg * gg), dh[u] * tcu * og * (1.0f - og));
-                        dc[i][u] = dcc * fg;
-                        *reinterpret_cast<float4 *>(s_x + col * G4P + 32 * mt + 8 * u + 4 * half) = dz;
-                    }
-                }
-            }
+            bptt_dz_step<H, HPF>(t, s_dh, s_x, stash, dc, wave, lane, col, half);
             __syncthreads();  // dz_t is complete; dh_t and the gates of step t are read
-            for (int i = tid; i < 32 * G4 / 4; i += kLstmGradBlock) {  // dz_t to the stash, [pair][R], over the gates
-                const int p = i / (G4 / 4), r4 = i - p * (G4 / 4);
-                reinterpret_cast<float4 *>(slot)[i] = *reinterpret_cast<const float4 *>(s_x + p * G4P + 4 * r4);
-            }
+            bptt_dz_to_stash<H>(t, s_x, stash, tid);
             // dh_{t-1} = W_hh^T dz_t: units on M, pairs on N, k = R (not needed before the first step)
-            for (int ut = wave; t > 0 && ut < ZT; ut += 4) {
-                const float *wrow = g.wt + (size_t)(32 * ut + col) * G4 + 4 * half;
-                const float *zrow = s_x + col * G4P + 4 * half;
-                f32x16 acc;
-#pragma unroll
-                for (int rr = 0; rr < 16; ++rr) acc[rr] = 0.0f;
-#pragma unroll 4
-                for (int gg = 0; gg < G4 / 8; ++gg) {
-                    const float4 wv = *reinterpret_cast<const float4 *>(wrow + 8 * gg);
-                    const float4 zv = *reinterpret_cast<const float4 *>(zrow + 8 * gg);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) {
-                        const float ws = m == 0 ? wv.x : (m == 1 ? wv.y : (m == 2 ? wv.z : wv.w));
-                        const float zs = m == 0 ? zv.x : (m == 1 ? zv.y : (m == 2 ? zv.z : zv.w));
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, zs, acc, 0, 0, 0);
-                    }
-                }
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    *reinterpret_cast<float4 *>(s_dh + col * HPF + 32 * ut + 8 * b + 4 * half) =
-                        make_float4(acc[4 * b], acc[4 * b + 1], acc[4 * b + 2], acc[4 * b + 3]);
-            }
+            if (t > 0) bptt_wt_contract<G4, G4P, HPF>(g.wt, s_x, s_dh, ZT, wave, col, half);
             __syncthreads();  // dh_{t-1} is complete; dz_t is read
         }
 
         // ---- weight gradients: [dW_hh | dW_x] += dz [h | x]^T over the tile's 32 W (pair, step) columns ----
-        for (int ot = wave; ot < MT * NTO; ot += 4) {
-            const int mt = ot / NTO, nt = ot - mt * NTO;
-            f32x16 acc;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) acc[rr] = 0.0f;
-            for (int t = 0; t < W; ++t) {
-                const float *za = stash + (int64_t)t * 160 * H + 32 * mt + col;
-                const float *vb = vst + (int64_t)t * 32 * VN + 32 * nt + col;
-#pragma unroll
-                for (int kk = 0; kk < 16; ++kk) {
-                    const int p = 2 * kk + half;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(za[p * G4], vb[p * VN], acc, 0, 0, 0);
-                }
-            }
-            float *pt = part + ot * 1024 + lane;
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) pt[rr * 64] = first ? acc[rr] : pt[rr * 64] + acc[rr];
-        }
+        bptt_weight_grads<H>(stash, vst, part, W, first, wave, lane, col, half);
         __syncthreads();  // the stash and LDS are free for the next tile
     }
 }
