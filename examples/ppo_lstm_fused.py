@@ -7,7 +7,7 @@ user code (agents are out of this repo's scope): clipped-surrogate PPO with an L
 like finenvs/agents/PPO/{PPO_agent,continuous_actor,critic}.py.
 
     python examples/ppo_lstm_fused.py [--envs 4096] [--steps 16] [--iters 5] [--hidden 64] [--window 4] [--fused-update]
-                                      [--fused-optim]
+                                      [--fused-optim] [--graph-update]
 
 What runs where:
     rollout   : FusedLSTMRollout.run(K, noise, std, trajectory)       one launch per K steps, nothing written but
@@ -21,6 +21,10 @@ What runs where:
                 --fused-optim (implies --fused-update): FusedAdam of finenvs_amd/optim.py -- Adam and the packing of a
                 head in one launch per step (fe_net_update); the heads and their rollouts read its packed buffers and
                 its output bias on the device, so nothing is re-packed per call and refresh() has nothing to do
+                --graph-update (implies --fused-optim): PPOUpdate of finenvs_amd/ppo.py -- values, returns, the epochs'
+                shuffles drawn and gathered on the device (fe_ppo_minibatch), both losses with their gradients one
+                launch each, every optimizer step -- captured once by GraphedUpdate and replayed as one hipGraph
+                launch per iteration (the first iteration's update is the eager warm-up call)
 """
 import argparse
 import math
@@ -36,7 +40,9 @@ from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
 from finenvs_amd.lstm_head import FusedLSTMHead, ppo_actor_loss, ppo_critic_loss  # noqa: E402
 from finenvs_amd.lstm_head import LSTMHead as TrainableLSTMHead  # noqa: E402
+from finenvs_amd.graphed import GraphedUpdate  # noqa: E402
 from finenvs_amd.optim import FusedAdam  # noqa: E402
+from finenvs_amd.ppo import PPOUpdate  # noqa: E402
 from finenvs_amd.rollout import FusedLSTMRollout  # noqa: E402
 from finenvs_amd.stats import EpisodeStats  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
@@ -57,7 +63,8 @@ class LSTMHead(torch.nn.Module):
 
 
 def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatches=4, seed=0, quiet=False,
-         fused_update=False, fused_optim=False):
+         fused_update=False, fused_optim=False, graph_update=False):
+    fused_optim = fused_optim or graph_update
     fused_update = fused_update or fused_optim
     torch.manual_seed(seed)
     dev = "cuda:0"
@@ -91,13 +98,41 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
         value_head = FusedLSTMRollout.from_modules(env, critic.lstm, critic.last, output_activation="none")
     gen = torch.Generator(device=dev).manual_seed(seed)
     clip, ent_coef, gamma = 0.2, 0.01, 0.99
+    update = graph = None
+    if graph_update:  # the whole train() as one object: captured after its first (eager) call, replayed from then on
+        update = PPOUpdate(env, traj, actor_head, critic_head, log_std, opt_a, opt_c, epochs=epochs, minibatches=minibatches,
+                           clip_epsilon=clip, entropy_coefficient=ent_coef, gamma=gamma, seed=seed)
     history = []
+
+    def finish(it, loss_c, rewards, std):  # the end of an iteration: the chunk handed back, the episode log read
+        traj.clear()
+        log = stats.read(reset=True)
+        history.append((float(loss_c.detach()), float(rewards.mean()), log))
+        if not quiet:
+            print(f"iter {it}: critic loss {history[-1][0]:.4f}  mean step reward {history[-1][1]:+.5f}  std {std:.3f}  "
+                  f"finished episodes {log['num_training_episodes']}", flush=True)
+
     t0 = time.perf_counter()
     for it in range(iters):
         # ---- rollout: K env steps, one launch (agent.step + env.step + agent.store, K times) ----
         std = float(log_std.detach().exp())
         noise = torch.randn((steps, envs, 1), generator=gen, device=dev)
         actions, rewards, dones = roll.run(steps, noise=noise, std=std, record_means=True, trajectory=traj)
+        if graph_update:
+            update.load_means(roll.means)
+            if graph is None:  # one real update (the warm-up call), then the capture, which executes nothing
+                calls = []
+
+                def train():
+                    calls.append(update.train())
+                    return calls[-1]
+
+                graph = GraphedUpdate(train, warmup=1)
+                loss_c = calls[0][1]  # the warm-up call's loss; calls[1] are the static outputs the replays fill
+            else:
+                loss_c = graph.replay()[1]
+            finish(it, loss_c, rewards, std)
+            continue
         with torch.no_grad():
             old_logp = torch.distributions.Normal(roll.means, std).log_prob(actions)           # (K, N, 1)
             # ---- values of the K stored states and of the bootstrap state: the critic on their descriptors ----
@@ -143,12 +178,7 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
             for head, net in ((roll, actor), (value_head, critic)):  # the updated networks go back into the kernels
                 head.set_weights(net.lstm.weight_ih_l0, net.lstm.weight_hh_l0, net.lstm.bias_ih_l0, net.lstm.bias_hh_l0,
                                  net.last.weight, float(net.last.bias.detach()))
-        traj.clear()
-        log = stats.read(reset=True)
-        history.append((float(loss_c.detach()), float(rewards.mean()), log))
-        if not quiet:
-            print(f"iter {it}: critic loss {history[-1][0]:.4f}  mean step reward {history[-1][1]:+.5f}  std {std:.3f}  "
-                  f"finished episodes {log['num_training_episodes']}", flush=True)
+        finish(it, loss_c, rewards, std)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if not quiet:
@@ -169,5 +199,9 @@ if __name__ == "__main__":
     ap.add_argument("--fused-update", action="store_true",
                     help="train both heads on descriptors with the fused backward (every --hidden; the chunked "
                          "streamed-weight backward at 256 and above)")
+    ap.add_argument("--graph-update", action="store_true",
+                    help="implies --fused-optim: the whole update (device shuffle, fused losses, optimizer steps) captured "
+                         "once and replayed as one graph launch per iteration")
     a = ap.parse_args()
-    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update, fused_optim=a.fused_optim)
+    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update, fused_optim=a.fused_optim,
+         graph_update=a.graph_update)

@@ -247,6 +247,20 @@ REPLAY_CURSOR_SIGNATURES = {
     "fe_replay_sample_c": (C.c_int, [_vp, C.POINTER(FeReplayRing), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# include/finenvs_amd_ppo.h: PPO's mini-batch from a keyed permutation, its epoch counter and losses (finenvs_amd/ppo.py)
+PPO_PERM_SALT = 0x50504F5045524D31  # FE_PPO_PERM_SALT
+PPO_CURSOR_EPOCH, PPO_CURSOR_ERRORS, PPO_CURSOR_WORDS = 0, 1, 2
+PPO_MAX_COLUMNS = 4
+_f64 = C.c_double
+PPO_SIGNATURES = {
+    "fe_ppo_minibatch": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _vp, C.c_uint64, _i64, _i64, _i64,
+                                   _vp, _vp, _vp, _vp, _vp]),
+    "fe_ppo_epochs_advance": (C.c_int, [_vp, _i64, _vp]),
+    "fe_ppo_loss_workspace_doubles": (_i64, [_i64]),
+    "fe_ppo_actor_loss": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "fe_ppo_value_loss": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -274,7 +288,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **OPTIM_SIGNATURES,
-                         **REPLAY_CURSOR_SIGNATURES}.items():
+                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

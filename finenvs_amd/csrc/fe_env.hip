@@ -37,6 +37,7 @@
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_ring_draw_kernels.h  a mini-batch drawn and gathered from the ring's device cursor (capturable updates)
+//   fe_ppo_kernels.h     PPO's mini-batch drawn from a keyed permutation and gathered, and its two losses with gradients
 //   fe_critic_kernels.h   twin LSTM critics (SAC / TD3) on the rollout body's recurrence, and their Bellman-target epilogue
 //   fe_bptt_tile.h            the stages of one backward-through-time tile that the three backward passes below share
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
@@ -74,6 +75,7 @@
 #include "finenvs_amd_lstm_grad_streamed.h"
 #include "finenvs_amd_optim.h"
 #include "finenvs_amd_replay_cursor.h"
+#include "finenvs_amd_ppo.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
@@ -84,6 +86,7 @@
 #include "fe_evo_kernels.h"
 #include "fe_replay_kernels.h"
 #include "fe_ring_draw_kernels.h"
+#include "fe_ppo_kernels.h"
 #include "fe_critic_kernels.h"
 #include "fe_critic_grad_kernels.h"
 #include "fe_sac_grad_kernels.h"
@@ -2013,6 +2016,92 @@ int fe_net_update(const fe_optim_desc *desc, void *stream) {
     a.omb1 = desc->one_minus_beta1; a.b2 = desc->beta2_f32; a.omb2 = desc->one_minus_beta2; a.eps = desc->eps;
     hipLaunchKernelGGL(fe_net_update_kernel, dim3((unsigned)desc->num_blocks), dim3(kBlock), 0, (hipStream_t)stream, a);
     return launched("fe_net_update");
+}
+
+
+// ---- include/finenvs_amd_ppo.h: PPO's mini-batch, epoch counter and losses ----
+int fe_ppo_minibatch(const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t T, int64_t N,
+                     int64_t C, int32_t A, const float *const *columns, float *const *columns_out, int32_t num_columns,
+                     int64_t *cursor, uint64_t seed, int64_t epoch_offset, int64_t M, int64_t m, int64_t *indices_out,
+                     int64_t *obs_src_out, double *obs_pos_out, float *actions_out, void *stream) {
+    if (!obs_src || !obs_pos || !actions || !cursor || !indices_out)
+        return fail(FE_ERR_ARG, "fe_ppo_minibatch: null trajectory, cursor or indices_out");
+    if (T < 1 || N < 1 || C < N || A < 1) return fail(FE_ERR_ARG, "fe_ppo_minibatch: need T >= 1, N >= 1, C >= N, A >= 1");
+    const int64_t lim = (int64_t)1 << 32;
+    if (T >= lim || N >= lim || T * N >= lim)
+        return fail(FE_ERR_ARG, "fe_ppo_minibatch: T * N = %lld x %lld samples do not fit the 32-bit permutation",
+                    (long long)T, (long long)N);
+    const int64_t n = T * N;
+    if (M < 1 || M > n || m < 0 || m >= M)
+        return fail(FE_ERR_ARG, "fe_ppo_minibatch: mini-batch %lld of %lld over %lld samples", (long long)m, (long long)M, (long long)n);
+    if (epoch_offset < 0) return fail(FE_ERR_ARG, "fe_ppo_minibatch: epoch_offset < 0");
+    if (num_columns < 0 || num_columns > FE_PPO_MAX_COLUMNS || (num_columns > 0 && !columns))
+        return fail(FE_ERR_ARG, "fe_ppo_minibatch: at most %d columns", FE_PPO_MAX_COLUMNS);
+    for (int c = 0; c < num_columns; ++c)
+        if (!columns[c]) return fail(FE_ERR_ARG, "fe_ppo_minibatch: column %d is null", c);
+    DeviceGuard guard(device_of(obs_src));
+    if (int rc = guard.status("fe_ppo_minibatch: the trajectory is not device memory")) return rc;
+    PpoMinibatchArgs d;
+    d.obs_src = obs_src; d.obs_pos = obs_pos; d.actions = actions;
+    for (int c = 0; c < kPpoMaxColumns; ++c) {
+        d.col[c] = c < num_columns ? columns[c] : nullptr;
+        d.col_out[c] = c < num_columns && columns_out ? columns_out[c] : nullptr;
+    }
+    d.cursor = cursor; d.key = seed ^ FE_PPO_PERM_SALT; d.epoch_offset = epoch_offset;
+    d.T = T; d.N = N; d.C = C; d.n = n; d.B = n / M; d.first = m * d.B; d.A = A;
+    int k = 0;  // bit_length(n - 1)
+    while (k < 32 && ((uint64_t)(n - 1) >> k) != 0) ++k;
+    if (k < 1) k = 1;
+    d.hb = (k + 1) / 2;
+    d.idx = indices_out; d.src_out = obs_src_out; d.pos_out = obs_pos_out; d.act_out = actions_out;
+    hipLaunchKernelGGL(fe_ppo_minibatch_kernel, dim3(grid_for(d.B * A)), dim3(kBlock), 0, (hipStream_t)stream, d);
+    return launched("fe_ppo_minibatch");
+}
+
+int fe_ppo_epochs_advance(int64_t *cursor, int64_t count, void *stream) {
+    if (!cursor || count < 0) return fail(FE_ERR_ARG, "fe_ppo_epochs_advance: bad argument");
+    DeviceGuard guard(device_of(cursor));
+    if (int rc = guard.status("fe_ppo_epochs_advance: the cursor is not device memory")) return rc;
+    hipLaunchKernelGGL(fe_ppo_epochs_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, cursor, count);
+    return launched("fe_ppo_epochs_advance");
+}
+
+static int ppo_loss_grid(int64_t count) {
+    const int64_t g = (count + kBlock - 1) / kBlock;
+    return (int)(g < kPpoLossMaxGrid ? g : kPpoLossMaxGrid);
+}
+
+int64_t fe_ppo_loss_workspace_doubles(int64_t count) {
+    if (count < 1) return -1;
+    return 1 + 2 * (int64_t)ppo_loss_grid(count);
+}
+
+int fe_ppo_actor_loss(const float *means, const float *log_std, const float *actions, const float *old_log_probs,
+                      const float *advantages, int64_t count, double clip_epsilon, double entropy_coefficient,
+                      float *loss, float *g_means, float *g_log_std, double *workspace, void *stream) {
+    if (!means || !log_std || !actions || !old_log_probs || !advantages || !loss || !g_means || !g_log_std || !workspace ||
+        count < 1 || !(clip_epsilon >= 0.0))
+        return fail(FE_ERR_ARG, "fe_ppo_actor_loss: bad argument");
+    DeviceGuard guard(device_of(means));
+    if (int rc = guard.status("fe_ppo_actor_loss: means is not device memory")) return rc;
+    PpoLossArgs d{};
+    d.x = means; d.log_std = log_std; d.actions = actions; d.old_lp = old_log_probs; d.y = advantages; d.count = count;
+    d.lo = 1.0 - clip_epsilon; d.hi = 1.0 + clip_epsilon; d.ent_coef = entropy_coefficient;
+    d.loss = loss; d.g_x = g_means; d.g_log_std = g_log_std; d.ws = workspace;
+    hipLaunchKernelGGL(fe_ppo_actor_loss_kernel, dim3(ppo_loss_grid(count)), dim3(kBlock), 0, (hipStream_t)stream, d);
+    return launched("fe_ppo_actor_loss");
+}
+
+int fe_ppo_value_loss(const float *values, const float *returns, int64_t count, float *loss, float *g_values,
+                      double *workspace, void *stream) {
+    if (!values || !returns || !loss || !g_values || !workspace || count < 1)
+        return fail(FE_ERR_ARG, "fe_ppo_value_loss: bad argument");
+    DeviceGuard guard(device_of(values));
+    if (int rc = guard.status("fe_ppo_value_loss: values is not device memory")) return rc;
+    PpoLossArgs d{};
+    d.x = values; d.y = returns; d.count = count; d.loss = loss; d.g_x = g_values; d.ws = workspace;
+    hipLaunchKernelGGL(fe_ppo_value_loss_kernel, dim3(ppo_loss_grid(count)), dim3(kBlock), 0, (hipStream_t)stream, d);
+    return launched("fe_ppo_value_loss");
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ identity) and TD3's ``ActorLSTM`` (TD3/actor.py:83-94, tanh).  Its submodule nam
 ``FusedLSTMHead`` evaluates such a module on observation descriptors (C ABI ``fe_lstm_forward``) as a differentiable
 function of its six parameters (C ABI ``fe_lstm_backward``, include/finenvs_amd_lstm_grad.h): no observation is
 rendered in either direction.  It owns the ``FusedLSTMRollout`` that acts with the same parameters in the kernel.
-``ppo_actor_loss`` / ``ppo_critic_loss`` / ``td3_actor_loss`` are the reference's three losses on that output.  Scope:
+``ppo_actor_loss`` / ``ppo_critic_loss`` / ``td3_actor_loss`` are the reference's three losses on that output; with
+``fused=True`` the two PPO losses and their gradients are one launch each (include/finenvs_amd_ppo.h).  Scope:
 one asset, H in {32, 64, 128}; with ``streamed=True`` also H in {256, 512, 1024} (C ABI ``fe_lstm_backward_streamed``,
 include/finenvs_amd_lstm_grad_streamed.h).
 """
@@ -245,22 +246,137 @@ def _column(t: torch.Tensor, B: int, name: str) -> torch.Tensor:
     return t.reshape(B, 1)
 
 
+def ppo_loss_workspace(B: int, device) -> torch.Tensor:
+    """A zeroed workspace for one fused loss launch on ``B`` samples (``fe_ppo_loss_workspace_doubles``).  A launch
+    leaves it as it found it, so a caller that keeps it (``PPOUpdate``) allocates once."""
+    n = int(_lib.load().fe_ppo_loss_workspace_doubles(int(B)))
+    if n < 1:
+        raise ValueError(f"a loss launch needs at least one sample (got {B})")
+    return torch.zeros((n,), dtype=torch.float64, device=device)
+
+
+def _loss_workspace(workspace, B: int, device) -> torch.Tensor:
+    """The caller's workspace if it can hold a launch on ``B`` samples (ValueError otherwise), or a fresh one."""
+    if workspace is None:
+        return ppo_loss_workspace(B, device)
+    need = int(_lib.load().fe_ppo_loss_workspace_doubles(int(B)))
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.float64 or workspace.device != device \
+            or not workspace.is_contiguous() or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous float64 tensor of at least {need} elements on {device} "
+                         "(ppo_loss_workspace(B, device))")
+    return workspace
+
+
+def _loss_input(t: torch.Tensor, B: int) -> torch.Tensor:
+    return t.detach().reshape(B).to(dtype=torch.float32).contiguous()
+
+
+class _FusedActorLoss(torch.autograd.Function):
+    """``torch_ppo_actor_loss`` as one launch (C ABI ``fe_ppo_actor_loss``, include/finenvs_amd_ppo.h): the forward also
+    writes d loss / d means and d loss / d log_std, the backward scales them by ``grad_output``."""
+
+    @staticmethod
+    def forward(ctx, means, log_std, actions, old_log_probs, advantages, clip_epsilon, entropy_coefficient, workspace):
+        B, dev = int(means.numel()), means.device
+        if B < 1:
+            raise ValueError("the fused PPO loss needs at least one sample")
+        if log_std.numel() != 1 or log_std.dtype is not torch.float32 or log_std.device != dev:
+            raise ValueError("the fused PPO actor loss takes one float32 log_std on the means' device (A = 1)")
+        lib = _lib.load()
+        m, a, o, adv = (_loss_input(t, B) for t in (means, actions, old_log_probs, advantages))
+        if any(t.device != dev for t in (a, o, adv)):
+            raise ValueError("actions, old_log_probs and advantages must live on the means' device")
+        ws = _loss_workspace(workspace, B, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        g_means = torch.empty((B,), dtype=torch.float32, device=dev)
+        g_log_std = torch.empty((1,), dtype=torch.float32, device=dev)
+        _lib.check(lib.fe_ppo_actor_loss(
+            m.data_ptr(), log_std.detach().contiguous().data_ptr(), a.data_ptr(), o.data_ptr(), adv.data_ptr(), B,
+            float(clip_epsilon), float(entropy_coefficient), loss.data_ptr(), g_means.data_ptr(), g_log_std.data_ptr(),
+            ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), lib)
+        ctx.save_for_backward(g_means, g_log_std)
+        ctx.shapes = (tuple(means.shape), tuple(log_std.shape))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        g_means, g_log_std = ctx.saved_tensors
+        out = [None] * 8
+        if ctx.needs_input_grad[0]:
+            out[0] = (g_means * g_loss).reshape(ctx.shapes[0])
+        if ctx.needs_input_grad[1]:
+            out[1] = (g_log_std * g_loss).reshape(ctx.shapes[1])
+        return tuple(out)
+
+
+class _FusedValueLoss(torch.autograd.Function):
+    """``torch_ppo_critic_loss`` as one launch (C ABI ``fe_ppo_value_loss``): the forward also writes d loss / d values."""
+
+    @staticmethod
+    def forward(ctx, values, returns, workspace):
+        B, dev = int(values.numel()), values.device
+        if B < 1:
+            raise ValueError("the fused PPO loss needs at least one sample")
+        lib = _lib.load()
+        v, r = _loss_input(values, B), _loss_input(returns, B)
+        if r.device != dev:
+            raise ValueError("returns must live on the values' device")
+        ws = _loss_workspace(workspace, B, dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        g_values = torch.empty((B,), dtype=torch.float32, device=dev)
+        _lib.check(lib.fe_ppo_value_loss(v.data_ptr(), r.data_ptr(), B, loss.data_ptr(), g_values.data_ptr(), ws.data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream), lib)
+        ctx.save_for_backward(g_values)
+        ctx.shape = tuple(values.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (g_values,) = ctx.saved_tensors
+        return ((g_values * g_loss).reshape(ctx.shape) if ctx.needs_input_grad[0] else None), None, None
+
+
+def fused_ppo_actor_loss(means: torch.Tensor, log_std: torch.Tensor, actions: torch.Tensor, old_log_probs: torch.Tensor,
+                         advantages: torch.Tensor, clip_epsilon: float = 0.2, entropy_coefficient: float = 0.01,
+                         workspace: torch.Tensor = None) -> torch.Tensor:
+    """``torch_ppo_actor_loss`` on device tensors as ONE launch, differentiable in ``means`` and ``log_std`` (one
+    action per sample): evaluated in f64 from the f32 inputs and rounded once, so it agrees with the torch expression
+    to f32 rounding, not bit for bit.  ``workspace``: a kept ``ppo_loss_workspace(B, device)``; allocated if None."""
+    return _FusedActorLoss.apply(means, log_std, actions, old_log_probs, advantages, clip_epsilon, entropy_coefficient,
+                                 workspace)
+
+
+def fused_ppo_critic_loss(values: torch.Tensor, returns: torch.Tensor, workspace: torch.Tensor = None) -> torch.Tensor:
+    """``torch_ppo_critic_loss`` on device tensors as ONE launch, differentiable in ``values``."""
+    return _FusedValueLoss.apply(values, returns, workspace)
+
+
 def ppo_actor_loss(head: FusedLSTMHead, log_std: torch.Tensor, src: torch.Tensor, pos: torch.Tensor, actions: torch.Tensor,
                    old_log_probs: torch.Tensor, advantages: torch.Tensor, clip_epsilon: float = 0.2,
-                   entropy_coefficient: float = 0.01) -> torch.Tensor:
+                   entropy_coefficient: float = 0.01, fused: bool = False, workspace: torch.Tensor = None) -> torch.Tensor:
     """``compute_actor_loss`` (PPO/continuous_actor.py:59-78) on B state descriptors, nothing rendered: the clipped
     surrogate of ``Normal(head(src, pos), exp(log_std))`` plus the entropy bonus, negated.  ``actions``,
-    ``old_log_probs``, ``advantages``: B elements each.  ``log_std`` gets its gradient from autograd."""
+    ``old_log_probs``, ``advantages``: B elements each.  ``log_std`` gets its gradient from autograd.
+
+    ``fused=True``: the loss and its gradients from one launch (``fused_ppo_actor_loss``) instead of some thirty
+    element-wise ones; ``backward()`` accumulates into ``log_std.grad`` and the head's ``.grad`` as before.
+    ``workspace``: see ``fused_ppo_actor_loss``."""
     B = int(src.numel())
-    return torch_ppo_actor_loss(head(src, pos), log_std, _column(actions, B, "actions"),
-                                _column(old_log_probs, B, "old_log_probs"), _column(advantages, B, "advantages"),
-                                clip_epsilon, entropy_coefficient)
+    cols = (_column(actions, B, "actions"), _column(old_log_probs, B, "old_log_probs"), _column(advantages, B, "advantages"))
+    if fused:
+        return fused_ppo_actor_loss(head(src, pos), log_std, *cols, clip_epsilon, entropy_coefficient, workspace)
+    return torch_ppo_actor_loss(head(src, pos), log_std, *cols, clip_epsilon, entropy_coefficient)
 
 
-def ppo_critic_loss(head: FusedLSTMHead, src: torch.Tensor, pos: torch.Tensor, returns: torch.Tensor) -> torch.Tensor:
+def ppo_critic_loss(head: FusedLSTMHead, src: torch.Tensor, pos: torch.Tensor, returns: torch.Tensor, fused: bool = False,
+                    workspace: torch.Tensor = None) -> torch.Tensor:
     """``compute_critic_loss`` (PPO/critic.py:26-32) on B state descriptors: the mean squared error of
-    ``head(src, pos)`` against ``returns`` (B elements)."""
-    return torch_ppo_critic_loss(head(src, pos), _column(returns, int(src.numel()), "returns"))
+    ``head(src, pos)`` against ``returns`` (B elements).  ``fused=True``: loss and gradient from one launch
+    (``fused_ppo_critic_loss``)."""
+    ret = _column(returns, int(src.numel()), "returns")
+    if fused:
+        return fused_ppo_critic_loss(head(src, pos), ret, workspace)
+    return torch_ppo_critic_loss(head(src, pos), ret)
 
 
 def td3_actor_loss(head: FusedLSTMHead, buffer, indices: torch.Tensor, twin) -> torch.Tensor:
