@@ -162,6 +162,17 @@ CRITIC_GRAD_SIGNATURES = {
 }
 
 
+# include/finenvs_amd_critic_streamed.h: the twin critics at H = 256 / 512 / 1024 (FeCriticWeights / FeCriticGrads again);
+# each entry takes the argument list of its register-resident namesake
+CRITIC_STREAMED_SIGNATURES = {
+    "fe_twin_q_forward_streamed": CRITIC_SIGNATURES["fe_twin_q_forward"],
+    "fe_twin_q_target_streamed": CRITIC_SIGNATURES["fe_twin_q_target"],
+    "fe_twin_q_target_streamed_c": (C.c_int, [_vp, _vp, _cw, _cw, _i32, C.POINTER(FeReplayRing), _vp, _vp, _i64, _vp, _vp,
+                                              C.c_float, C.c_float, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
+    "fe_twin_q_streamed_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_twin_q_backward_streamed": CRITIC_GRAD_SIGNATURES["fe_twin_q_backward"],
+}
+
 # include/finenvs_amd_sac_grad.h: the SAC actor's backward pass (finenvs_amd/sac.py; same library)
 class FeSacGrads(C.Structure):
     """struct fe_sac_grads of include/finenvs_amd_sac_grad.h."""
@@ -287,7 +298,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
     lib = C.CDLL(p)
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
-                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **OPTIM_SIGNATURES,
+                         **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
+                         **OPTIM_SIGNATURES,
                          **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res

@@ -12,7 +12,9 @@ next states are never rendered.  The actor half runs on the same descriptors in 
 ``FusedLSTMRollout.forward``.  The gradient half runs on descriptors too: ``FusedTwinCritic.q`` is the values as a
 differentiable function of the actions and both critics' parameters (C ABI ``fe_twin_q_backward``,
 include/finenvs_amd_critic_grad.h), and ``critic_loss`` the critics' MSE on replayed transitions.  Scope: one asset (the reference's multi-asset critic is ``nn.LSTM(5A + A, H)`` over the
-whole env, not a per-pair network) and H in {32, 64, 128}.
+whole env, not a per-pair network) and H in {32, 64, 128}; with ``streamed=True`` also H in {256, 512, 1024} (C ABI
+``fe_twin_q_forward_streamed`` / ``fe_twin_q_target_streamed`` / ``fe_twin_q_backward_streamed``,
+include/finenvs_amd_critic_streamed.h).
 """
 from __future__ import annotations
 
@@ -25,9 +27,10 @@ import torch.nn.functional as F
 
 from . import _lib
 from .replay import as_draw
-from .rollout import lstm_pack, lstm_row_order_on
+from .rollout import lstm_fragment_major, lstm_pack, lstm_row_order_on
 
 CRITIC_HIDDEN_SIZES = (32, 64, 128)
+CRITIC_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
 
 
 def match_actions_dim_with_states(states: torch.Tensor, actions: torch.Tensor) -> Tuple[torch.Tensor, int]:
@@ -56,8 +59,9 @@ class CriticLSTM(nn.Module):
         return self.last_layer(out[:, -1, :])
 
 
-def check_critic(critic: nn.Module) -> int:
-    """The hidden size of a critic the fused twin critic can run; ValueError otherwise."""
+def check_critic(critic: nn.Module, streamed: bool = False) -> int:
+    """The hidden size of a critic the fused twin critic can run; ValueError otherwise.  ``streamed``: H may also be 256,
+    512 or 1024 (the streamed kernels of include/finenvs_amd_critic_streamed.h)."""
     lstm = getattr(critic, "lstm", None)
     if not isinstance(lstm, nn.LSTM):
         raise ValueError("the fused critic needs a module with an nn.LSTM `lstm`")
@@ -65,8 +69,12 @@ def check_critic(critic: nn.Module) -> int:
         raise ValueError("the fused critic needs nn.LSTM(6, H, num_layers=1, batch_first=True) (5 observation features "
                          "and one action: A = 1)")
     H = int(lstm.hidden_size)
-    if H not in CRITIC_HIDDEN_SIZES:
-        raise ValueError(f"the fused critic supports H in {CRITIC_HIDDEN_SIZES} (got {H})")
+    if streamed and H not in CRITIC_HIDDEN_SIZES + CRITIC_STREAMED_HIDDEN_SIZES:
+        raise ValueError(f"the fused critic supports H in {CRITIC_HIDDEN_SIZES + CRITIC_STREAMED_HIDDEN_SIZES} (got {H})")
+    if not streamed and H not in CRITIC_HIDDEN_SIZES:
+        raise ValueError(f"the fused critic supports H in {CRITIC_HIDDEN_SIZES} (got {H})"
+                         + ("; pass streamed=True for the streamed kernels of H in "
+                            f"{CRITIC_STREAMED_HIDDEN_SIZES}" if H in CRITIC_STREAMED_HIDDEN_SIZES else ""))
     last = getattr(critic, "last_layer", None)
     if not isinstance(last, nn.Sequential) or len(last) != 2 or not isinstance(last[0], nn.Linear) \
             or not isinstance(last[1], nn.Identity) or last[0].in_features != H or last[0].out_features != 1 \
@@ -78,11 +86,14 @@ def check_critic(critic: nn.Module) -> int:
 def pack_critic_weights(critic: nn.Module) -> Dict[str, torch.Tensor]:
     """The critic's current parameters as fe_twin_q_forward reads them (f32, on the parameters' device, no host sync):
     whh / wx as ``lstm_pack`` of the five observation inputs (slot 5 = b_ih + b_hh) plus slot 6 = the action's input
-    weight ``w_ih[:, 5]``; ``wout`` (H) and ``bout`` (1)."""
-    H = check_critic(critic)
+    weight ``w_ih[:, 5]``; ``wout`` (H) and ``bout`` (1).  At H > 128 ``whh`` is fragment-major
+    (``lstm_fragment_major``), as the streamed kernels read it."""
+    H = check_critic(critic, streamed=True)
     lstm = critic.lstm
     w_ih = lstm.weight_ih_l0.detach().float()
     whh, wx = lstm_pack(w_ih[:, :5], lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, H)
+    if H > 128:
+        whh = lstm_fragment_major(whh, H)
     wx[:, 6] = w_ih[lstm_row_order_on(H, w_ih.device), 5]
     last = critic.last_layer[0]
     return {
@@ -103,8 +114,10 @@ def critic_parameters(critic: nn.Module) -> Tuple[torch.Tensor, ...]:
 
 
 def empty_packed_grads(H: int, device) -> Dict[str, torch.Tensor]:
-    """Buffers for one critic's gradients as fe_twin_q_backward writes them (include/finenvs_amd_critic_grad.h)."""
-    shapes = {"w_ih": (4 * H, 6), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,), "w_out": (H,), "b_out": (1,)}
+    """Buffers for one critic's gradients as fe_twin_q_backward writes them (include/finenvs_amd_critic_grad.h).  At
+    H > 128 the same buffers, ``w_out`` (1, H): fe_twin_q_backward_streamed writes torch's row order and layout."""
+    shapes = {"w_ih": (4 * H, 6), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,),
+              "w_out": (1, H) if H > 128 else (H,), "b_out": (1,)}
     return {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in GRAD_KEYS}
 
 
@@ -127,13 +140,14 @@ def torch_grads_to_packed(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch
 
 class _TwinQ(torch.autograd.Function):
     """(q1, q2) of ``FusedTwinCritic`` as a differentiable function of the actions and the twelve parameters: the
-    forward is ``fe_twin_q_forward``, the backward ``fe_twin_q_backward`` (the same activations, recomputed)."""
+    forward is ``fe_twin_q_forward``, the backward ``fe_twin_q_backward`` (the same activations, recomputed); at
+    H > 128 their ``_streamed`` namesakes, whose gradients arrive in torch's row order."""
 
     @staticmethod
     def forward(ctx, fused, src, pos, actions, *params):
         q1, q2 = fused.forward(src, pos, actions.detach())
         ctx.set_materialize_grads(False)  # an output nobody used gets None, not zeros: its critic does not run
-        ctx.fused, ctx.packed, ctx.action_shape = fused, fused._packed, actions.shape
+        ctx.fused, ctx.packed, ctx.action_shape = fused, getattr(fused, "_packed", None), actions.shape  # (none yet: B = 0)
         ctx.version = None if fused.weights is None else fused.weights.version
         ctx.save_for_backward(src, pos, actions.detach().reshape(-1).contiguous())
         return q1, q2
@@ -156,23 +170,31 @@ class _TwinQ(torch.autograd.Function):
         dq = [None if g is None else g.reshape(B).float().contiguous() for g in dq]
         grads = [empty_packed_grads(H, dev) if dq[c] is not None and need_w[c] else None for c in range(2)]
         da = torch.empty((B,), dtype=torch.float32, device=dev) if need_a else None
-        ws = torch.empty((int(env._lib.fe_twin_q_grad_workspace_floats(H, int(env.num_intervals), B)),),
-                         dtype=torch.float32, device=dev)
-        cw = [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
-              for x in ctx.packed]
+        streamed = H > 128
+        floats = env._lib.fe_twin_q_streamed_grad_workspace_floats if streamed else env._lib.fe_twin_q_grad_workspace_floats
+        ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
         cg = [None if g is None else _lib.FeCriticGrads(*(g[k].data_ptr() for k in GRAD_KEYS)) for g in grads]
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
-        _lib.check(env._lib.fe_twin_q_backward(
-            env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), H, src.data_ptr(), pos.data_ptr(),
-            act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
-            env._stream()), env._lib)
+        backward = env._lib.fe_twin_q_backward_streamed if streamed else env._lib.fe_twin_q_backward
+        if B == 0:  # nothing to launch (an empty tensor has no address to pass): the sums over an empty batch are zeros
+            for g in grads:
+                if g is not None:
+                    for t in g.values():
+                        t.zero_()
+        else:
+            cw = [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
+                  for x in ctx.packed]
+            _lib.check(backward(
+                env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), H, src.data_ptr(), pos.data_ptr(),
+                act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
+                env._stream()), env._lib)
         if need_a:
             out[3] = da.reshape(ctx.action_shape)
         for c in range(2):
             if grads[c] is None:
                 continue
-            t = packed_grads_to_torch(grads[c], H)
+            t = grads[c] if streamed else packed_grads_to_torch(grads[c], H)
             for k, key in enumerate(GRAD_KEYS):
                 if need[4 + 6 * c + k]:
                     out[4 + 6 * c + k] = t[key]
@@ -188,17 +210,24 @@ class FusedTwinCritic:
     ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that both critics are registered with, as networks or as
     targets.  Nothing is packed per call then: every launch reads that optimizer's packed buffers, which its ``step()``
     keeps current.  Those buffers are rewritten in place: a ``weights.step()`` or ``weights.repack()`` between a
-    forward and its ``backward()`` is a RuntimeError."""
+    forward and its ``backward()`` is a RuntimeError.
 
-    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module, weights=None):
+    ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent weights stream from L2
+    (include/finenvs_amd_critic_streamed.h).  It is an opt-in because that backward is several launches per LSTM time
+    step and per critic, and its workspace grows with the batch, up to ``fe_lstm_streamed_grad_chunk_pairs`` pairs
+    (2 GiB of activations; the two critics share it), unlike the bounded one of H <= 128; H <= 128 runs the
+    register-resident way whether or not ``streamed`` is passed."""
+
+    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module, weights=None, streamed: bool = False):
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused twin critic runs one asset (the env has {env.num_assets}): the reference's critic "
                              "for A > 1 is one nn.LSTM(5A + A, H) over the whole env's window, not a per-(env, asset) pair "
                              "network")
-        H1, H2 = check_critic(critic_1), check_critic(critic_2)
+        H1, H2 = check_critic(critic_1, streamed), check_critic(critic_2, streamed)
         if H1 != H2:
             raise ValueError(f"the two critics must have the same hidden size (got {H1} and {H2})")
         self.env, self.critic_1, self.critic_2, self.H = env, critic_1, critic_2, H1
+        self.streamed = H1 > 128  # which entries run: a function of H alone
         self._check_devices()
         self.weights = weights
         if weights is not None:
@@ -242,7 +271,8 @@ class FusedTwinCritic:
         q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
         if B:
             c1, c2 = self._weights()
-            _lib.check(env._lib.fe_twin_q_forward(
+            entry = env._lib.fe_twin_q_forward_streamed if self.streamed else env._lib.fe_twin_q_forward
+            _lib.check(entry(
                 env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, src.data_ptr(), pos.data_ptr(),
                 act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
         return q1, q2
@@ -328,12 +358,15 @@ class FusedTwinCritic:
             tail = (idx.data_ptr(), B, next_actions.data_ptr(), ptr(smooth_noise), float(smooth_std), float(smooth_clip),
                     ptr(log_probs), ptr(alpha), float(gamma), float(reward_scale), y.data_ptr(), q1.data_ptr(),
                     q2.data_ptr(), env._stream())
+            lib = env._lib
             if draw is None:
-                _lib.check(env._lib.fe_twin_q_target(
+                entry = lib.fe_twin_q_target_streamed if self.streamed else lib.fe_twin_q_target
+                _lib.check(entry(
                     env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
                     buffer.head, buffer.size(), *tail), env._lib)
             else:  # head and size from the cursor, when the launches run
-                _lib.check(env._lib.fe_twin_q_target_c(
+                entry = lib.fe_twin_q_target_streamed_c if self.streamed else lib.fe_twin_q_target_c
+                _lib.check(entry(
                     env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
                     buffer.cursor.data_ptr(), *tail), env._lib)
         self.last = {"indices": idx, "next_actions": next_actions.reshape(B, 1), "q1": q1, "q2": q2}

@@ -43,6 +43,7 @@
 //   fe_critic_grad_kernels.h  the twin critics' backward pass through time and its deterministic reduction
 //   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
 //   fe_lstm_grad_kernels.h    the one-output LSTM head's backward pass (PPO actor / critic, TD3 actor) and its reduction
+//   fe_critic_streamed_kernels.h  the twin critics at H = 256 / 512 / 1024: streamed values, targets and backward pass
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
 //                         headers in include/
@@ -73,6 +74,7 @@
 #include "finenvs_amd_sac_grad.h"
 #include "finenvs_amd_lstm_grad.h"
 #include "finenvs_amd_lstm_grad_streamed.h"
+#include "finenvs_amd_critic_streamed.h"
 #include "finenvs_amd_optim.h"
 #include "finenvs_amd_replay_cursor.h"
 #include "finenvs_amd_ppo.h"
@@ -92,6 +94,7 @@
 #include "fe_sac_grad_kernels.h"
 #include "fe_lstm_grad_kernels.h"
 #include "fe_lstm_grad_streamed_kernels.h"
+#include "fe_critic_streamed_kernels.h"
 #include "fe_optim_kernels.h"
 
 namespace {
@@ -1931,6 +1934,227 @@ int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float 
         if (int rc = launched("fe_lstm_backward_streamed: weight gradients")) return rc;
         hipLaunchKernelGGL(fe_lstm_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
         if (int rc = launched("fe_lstm_backward_streamed: final write")) return rc;
+    }
+    return FE_OK;
+}
+
+// ---- include/finenvs_amd_critic_streamed.h: the twin critics at H = 256 / 512 / 1024 ----
+static int critic_streamed_check(const fe_env *env, int32_t H, const char *who) {
+    if (!lstm_sgrad_hidden_ok(H))
+        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); H = 32, 64 and 128 run the register-resident "
+                    "entries of finenvs_amd_critic.h / finenvs_amd_critic_grad.h", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only (the reference's critic for A > 1 "
+                    "is one nn.LSTM(5A + A, H) over the whole env, not a per-(env, asset) pair network)", who, (int)env->p.A);
+    if (critic_sgrad_forward_lds_bytes(H) > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H,
+                    critic_sgrad_forward_lds_bytes(H), kMaxLds);
+    return FE_OK;
+}
+
+// One launch of the recurrence over a.g.pp / 32 tiles: at most the resident workgroups, each looping over its tiles.
+static int launch_critic_sgrad_forward(fe_env *env, const void *kern, CriticSGradArgs &a, int32_t H, const char *who,
+                                       hipStream_t st) {
+    const size_t lds = critic_sgrad_forward_lds_bytes(H);
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, "streamed critic kernel: hipFuncSetAttribute / occupancy query");
+    int64_t resident = (int64_t)env->cus * per_cu;
+    if (resident < 1) resident = 1;
+    const int64_t tiles = a.g.pp / 32;
+    void *args[] = {&a};
+    return launched(who, hipLaunchKernel(kern, dim3((unsigned)(tiles < resident ? tiles : resident)), dim3(kLstmBlock),
+                                         args, lds, st));
+}
+
+// The forward-only recurrence for both critics, one after the other (a: descriptors, actions and ring already set).
+static int launch_twin_q_streamed(fe_env *env, CriticSGradArgs &a, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                                  int32_t H, int64_t count, float *q1_out, float *q2_out, const char *who, void *stream) {
+    const void *kern = critic_sgrad_forward_kernel_for<false>(H);
+    const fe_critic_weights *c[2] = {c1, c2};
+    float *q[2] = {q1_out, q2_out};
+    a.g.W = env->p.W; a.g.cnt = count; a.g.pp = (count + 31) / 32 * 32;
+    for (int i = 0; i < 2; ++i) {
+        a.g.whh = c[i]->whh; a.g.wx = c[i]->wx; a.g.wout = c[i]->wout; a.bout = c[i]->bout; a.q_out = q[i];
+        if (int rc = launch_critic_sgrad_forward(env, kern, a, H, who, (hipStream_t)stream)) return rc;
+    }
+    return FE_OK;
+}
+
+int fe_twin_q_forward_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                               const fe_critic_weights *c2, int32_t H, const int64_t *obs_src, const double *obs_pos,
+                               const float *actions, int64_t count, float *q1_out, float *q2_out, void *stream) {
+    static const char *who = "fe_twin_q_forward_streamed";
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !obs_src || !obs_pos || !actions ||
+        !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = critic_streamed_check(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    CriticSGradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g.lr32 = logret_f32; a.g.obs_src = obs_src; a.g.obs_pos = obs_pos; a.actions = actions;
+    return launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, who, stream);
+}
+
+// fe_twin_q_target_streamed and fe_twin_q_target_streamed_c: `cursor` null for the by-value entry (as twin_q_target_impl).
+static int twin_q_target_streamed_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                                       const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, int64_t head,
+                                       int64_t size, const int64_t *cursor, const int64_t *indices, int64_t count,
+                                       const float *next_actions, const float *smooth_noise, float smooth_std,
+                                       float smooth_clip, const float *log_probs, const float *alpha, float gamma,
+                                       float reward_scale, float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    static const char *who = "fe_twin_q_target_streamed";
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
+        !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (log_probs && !alpha) return fail(FE_ERR_ARG, "%s: log_probs (SAC) need alpha", who);
+    if (smooth_noise && log_probs)
+        return fail(FE_ERR_ARG, "%s: smooth_noise (TD3) and log_probs (SAC) are exclusive", who);
+    if (int rc = critic_streamed_check(env, H, who)) return rc;
+    const int64_t C = ring->capacity;
+    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
+        return fail(FE_ERR_ARG, "%s: size %lld / head %lld do not describe a non-empty ring of %lld slots", who,
+                    (long long)size, (long long)head, (long long)C);
+    if (ring->num_assets != 1) return fail(FE_ERR_ARG, "%s: the ring holds %d assets, the env 1", who, (int)ring->num_assets);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
+    CriticSGradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g.lr32 = logret_f32; a.actions = next_actions;
+    a.indices = indices; a.ring_src = ring->next_src; a.ring_pos = ring->next_pos;
+    a.ring_C = C; a.start = start; a.size = size; a.cursor = cursor;
+    a.smooth_noise = smooth_noise; a.smooth_std = smooth_std; a.smooth_clip = smooth_clip;
+    if (int rc = launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, "fe_twin_q_target_streamed: critics", stream))
+        return rc;
+    TwinTargetArgs t;
+    t.q1 = q1_out; t.q2 = q2_out; t.indices = indices; t.ring_rew = ring->rewards; t.ring_done = ring->dones;
+    t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
+    t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
+    t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
+    t.cursor = cursor;
+    hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
+    return launched("fe_twin_q_target_streamed: epilogue");
+}
+
+int fe_twin_q_target_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                              const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, int64_t head,
+                              int64_t size, const int64_t *indices, int64_t count, const float *next_actions,
+                              const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
+                              const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
+                              float *q2_out, void *stream) {
+    return twin_q_target_streamed_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
+                                       smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale,
+                                       targets_out, q1_out, q2_out, stream);
+}
+
+int fe_twin_q_target_streamed_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                                const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, const int64_t *cursor,
+                                const int64_t *indices, int64_t count, const float *next_actions,
+                                const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
+                                const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
+                                float *q2_out, void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_streamed_c: null cursor");
+    return twin_q_target_streamed_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions,
+                                       smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale,
+                                       targets_out, q1_out, q2_out, stream);
+}
+
+// The workspace of fe_lstm_backward_streamed, used by one critic after the other; d_actions is written in place.
+int64_t fe_twin_q_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    return fe_lstm_streamed_grad_workspace_floats(H, W, count);
+}
+
+int fe_twin_q_backward_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                                const fe_critic_weights *c2, int32_t H, const int64_t *obs_src, const double *obs_pos,
+                                const float *actions, int64_t count, const float *dq1, const float *dq2,
+                                float *workspace, const fe_critic_grads *grads1, const fe_critic_grads *grads2,
+                                float *d_actions, void *stream) {
+    static const char *who = "fe_twin_q_backward_streamed";
+    if (!env || !logret_f32 || !obs_src || !obs_pos || !actions || !workspace || count < 0 ||
+        (dq1 && (!critic_weights_ok(c1) || (grads1 && !critic_grads_ok(grads1)) || (!grads1 && !d_actions))) ||
+        (dq2 && (!critic_weights_ok(c2) || (grads2 && !critic_grads_ok(grads2)) || (!grads2 && !d_actions))))
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = critic_streamed_check(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (!dq1 && !dq2) {
+        if (!d_actions) return FE_OK;
+        return launched(who, hipMemsetAsync(d_actions, 0, (size_t)count * sizeof(float), st));
+    }
+    const int W = env->p.W;
+    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
+    const void *kern = critic_sgrad_forward_kernel_for<true>(H);
+    const fe_critic_weights *cw[2] = {c1, c2};
+    const fe_critic_grads *cg[2] = {grads1, grads2};
+    const float *dq[2] = {dq1, dq2};
+    int ran = 0;  // critics that have written d_actions
+    for (int i = 0; i < 2; ++i) {
+        if (!dq[i]) continue;
+        CriticSGradArgs a;
+        memset(&a, 0, sizeof(a));
+        LstmSGradArgs &g = a.g;
+        g.lr32 = logret_f32; g.whh = cw[i]->whh; g.wx = cw[i]->wx; g.wout = cw[i]->wout; g.W = W; g.out_act = 2;
+        g.wt = workspace;  // the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest pass (pp pairs)
+        g.part = g.wt + lstm_sgrad_wt_floats(H);
+        g.hpart = g.part + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H);
+        g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+        if (cg[i]) {
+            g.g_wih = cg[i]->w_ih; g.g_whh = cg[i]->w_hh; g.g_bih = cg[i]->b_ih; g.g_bhh = cg[i]->b_hh;
+            g.g_wout = cg[i]->w_out; g.g_bout = cg[i]->b_out;
+        }
+        a.da_add = ran > 0;
+        hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
+        if (int rc = launched("fe_twin_q_backward_streamed: weight transpose")) return rc;
+        // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
+        for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+            g.cnt = count - c0 < chunk ? count - c0 : chunk;
+            g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
+            g.splits = lstm_sgrad_splits(H, W, g.pp);
+            g.cst = g.gates + (int64_t)W * g.pp * 4 * H;
+            g.vst = g.cst + (int64_t)W * g.pp * H;
+            g.hw = g.vst + (int64_t)W * g.pp * (H + 32);
+            g.dh = g.hw + g.pp * H;
+            g.dc = g.dh + g.pp * H;
+            g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0; g.d_outputs = dq[i] + c0;
+            g.first = c0 == 0;
+            a.actions = actions + c0;
+            a.da = d_actions ? d_actions + c0 : nullptr;
+            const int64_t tiles = g.pp / 32;
+            if (int rc = launch_critic_sgrad_forward(env, kern, a, H, "fe_twin_q_backward_streamed: recurrence", st)) return rc;
+            hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
+            if (int rc = launched("fe_twin_q_backward_streamed: head")) return rc;
+            for (int t = W - 1; t >= 0; --t) {
+                g.t = t;
+                hipLaunchKernelGGL(fe_lstm_sgrad_dz_kernel, dim3(grid_for(g.pp * (H / 4))), dim3(kBlock), 0, st, g, H);
+                if (t > 0)
+                    hipLaunchKernelGGL(fe_lstm_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles),
+                                       dim3(kBlock), 0, st, g, H);
+                // a launch that fails fails the first time: stop before queueing 2 W launches behind it
+                if (t == W - 1) {
+                    if (int rc = launched("fe_twin_q_backward_streamed: backward through time")) return rc;
+                }
+            }
+            if (a.da) {
+                const int64_t blocks = (g.cnt + kBlock / 64 - 1) / (kBlock / 64);
+                hipLaunchKernelGGL(fe_critic_sgrad_da_kernel, dim3((unsigned)capped_grid(blocks)), dim3(kBlock),
+                                   (size_t)4 * H * sizeof(float), st, a, H);
+                if (int rc = launched("fe_twin_q_backward_streamed: d_actions")) return rc;
+            }
+            if (!cg[i]) continue;  // frozen: no weight contraction, no final write
+            hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
+                               dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
+                               st, g, H);
+            if (int rc = launched("fe_twin_q_backward_streamed: weight gradients")) return rc;
+            hipLaunchKernelGGL(fe_critic_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
+            if (int rc = launched("fe_twin_q_backward_streamed: final write")) return rc;
+        }
+        if (d_actions) ++ran;
     }
     return FE_OK;
 }

@@ -147,8 +147,8 @@ class _Segment:
 
 
 def network_kind(module: nn.Module) -> Tuple[str, int]:
-    """("head" | "critic" | "actor", H) of a module ``FusedAdam.add`` takes: what ``check_head`` (H up to 1024),
-    ``check_critic`` or ``check_actor`` accept; ValueError otherwise."""
+    """("head" | "critic" | "actor", H) of a module ``FusedAdam.add`` takes: what ``check_head``,
+    ``check_critic`` (both with H up to 1024) or ``check_actor`` accept; ValueError otherwise."""
     from .critic import check_critic
     from .lstm_head import check_head
     from .sac import check_actor
@@ -160,7 +160,7 @@ def network_kind(module: nn.Module) -> Tuple[str, int]:
     if hasattr(module, "mu_layer") and hasattr(module, "std_layer"):
         return "actor", check_actor(module)
     if lstm.input_size == 6:
-        return "critic", check_critic(module)
+        return "critic", check_critic(module, streamed=True)
     return "head", check_head(module, streamed=True)[0]
 
 

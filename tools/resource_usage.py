@@ -1,6 +1,9 @@
 """Register / scratch table of every kernel in the product library (gfx950 cross-compile, no GPU needed).
 
-    python tools/resource_usage.py [-DKNOB=V ...] [--out profiles/r03_resource_usage.txt]
+    python tools/resource_usage.py [-DKNOB=V ...] [--only PREFIX] [--out profiles/r03_resource_usage.txt]
+
+``--only PREFIX`` keeps the kernels whose name starts with PREFIX (profiles/critic_streamed_resource_usage.txt:
+``--only fe_critic_sgrad_``).
 
 Compiles finenvs_amd/csrc/fe_env.hip with -Rpass-analysis=kernel-resource-usage (to a scratch .so under /tmp, the
 product library is not touched) and prints one line per kernel.  tests/test_resource_usage.py asserts on the same
@@ -86,7 +89,11 @@ def format_table(rows):
 
 if __name__ == "__main__":
     defs = [a for a in sys.argv[1:] if a.startswith("-D")]
-    text = format_table(kernel_table(defs))
+    rows = kernel_table(defs)
+    if "--only" in sys.argv:
+        prefix = sys.argv[sys.argv.index("--only") + 1]
+        rows = [r for r in rows if r["name"].startswith(prefix)]
+    text = format_table(rows)
     if "--out" in sys.argv:
         path = sys.argv[sys.argv.index("--out") + 1]
         head = "# hipcc -O3 -ffp-contract=off --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage " + " ".join(defs) + "\n"
