@@ -33,6 +33,9 @@
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
 //   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA), and with the SAC actor's head
 //   fe_lstm_rollout_body.h  the register-resident rollout's body, included by both of those kernels
+//   fe_lstm_stream_tile.h   one row-tile group of the streamed recurrence at H = 256 / 512 / 1024, included by the large-H
+//                           rollout kernel and by fe_lstm_stream_sgrad_body.h
+//   fe_lstm_stream_sgrad_body.h  the tile loop of the streamed head's and the streamed critics' recurrence kernels
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
 //   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
@@ -142,6 +145,13 @@ int launched(const char *who, hipError_t he) {
 }
 
 int launched(const char *who) { return launched(who, hipGetLastError()); }
+
+// ... of stage `what` of entry `who`: reported as "<who>: <what> launch: <HIP error>"
+int launched(const char *who, const char *what) {
+    char step[96];
+    snprintf(step, sizeof(step), "%s: %s", who, what);
+    return launched(step);
+}
 
 }  // namespace
 
@@ -1849,6 +1859,79 @@ int64_t fe_lstm_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t cou
            lstm_sgrad_head_blocks(pp) * (H + 32) + pp * (lstm_sgrad_pair_floats(H, W) + 3LL * H);
 }
 
+// ---- what fe_lstm_backward_streamed and fe_twin_q_backward_streamed (and the streamed critics' forward) share ----
+// wt | part | hpart | gates from the workspace: the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest
+// pass (pp pairs).  g.W is set.
+static void sgrad_carve(LstmSGradArgs &g, float *workspace, int32_t H, int64_t pp) {
+    g.wt = workspace;
+    g.part = g.wt + lstm_sgrad_wt_floats(H);
+    g.hpart = g.part + lstm_sgrad_splits(H, g.W, pp) * lstm_sgrad_part_floats(H);
+    g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+}
+
+// The chunk that starts at pair c0 of `count`: its sizes, its buffers behind g.gates, and whether it is the first.
+static void sgrad_chunk(LstmSGradArgs &g, int32_t H, int64_t c0, int64_t count, int64_t chunk) {
+    const int64_t W = g.W;
+    g.cnt = count - c0 < chunk ? count - c0 : chunk;
+    g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
+    g.splits = lstm_sgrad_splits(H, g.W, g.pp);
+    g.cst = g.gates + W * g.pp * 4 * H;
+    g.vst = g.cst + W * g.pp * H;
+    g.hw = g.vst + W * g.pp * (H + 32);
+    g.dh = g.hw + g.pp * H;
+    g.dc = g.dh + g.pp * H;
+    g.first = c0 == 0;
+}
+
+// One launch of a recurrence kernel (kLstmBlock threads, `a` its one argument) over `tiles` 32-pair tiles: at most the
+// resident workgroups, each looping over its tiles.  `what` names the kernel in a preparation error, `step` the launch.
+static int launch_sgrad_forward(const fe_env *env, const void *kern, size_t lds, void *a, int64_t tiles, const char *what,
+                                const char *step, hipStream_t st) {
+    int per_cu = 0;
+    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
+    if (he != hipSuccess) return hip_fail(he, what);
+    int64_t resident = (int64_t)env->cus * per_cu;
+    if (resident < 1) resident = 1;
+    void *args[] = {a};
+    return launched(step, hipLaunchKernel(kern, dim3((unsigned)(tiles < resident ? tiles : resident)), dim3(kLstmBlock),
+                                          args, lds, st));
+}
+
+// A chunk after its recurrence: head -> (dz [, dh]) x W -> [d_actions] -> [weight contraction -> final write], every launch
+// reported as "<who>: <stage>".  `da`: the critic's argument block around g when d_actions are wanted, else null.
+// `final_kernel` null: a frozen critic.
+static int sgrad_backward_chunk(const char *who, LstmSGradArgs &g, int32_t H, const CriticSGradArgs *da,
+                                void (*final_kernel)(LstmSGradArgs, int32_t), hipStream_t st) {
+    const int W = g.W;
+    const int64_t tiles = g.pp / 32;
+    hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
+    if (int rc = launched(who, "head")) return rc;
+    for (int t = W - 1; t >= 0; --t) {
+        g.t = t;
+        hipLaunchKernelGGL(fe_lstm_sgrad_dz_kernel, dim3(grid_for(g.pp * (H / 4))), dim3(kBlock), 0, st, g, H);
+        if (t > 0)
+            hipLaunchKernelGGL(fe_lstm_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles),
+                               dim3(kBlock), 0, st, g, H);
+        // a launch that fails fails the first time: stop before queueing 2 W launches behind it
+        if (t == W - 1) {
+            if (int rc = launched(who, "backward through time")) return rc;
+        }
+    }
+    if (da) {
+        const int64_t blocks = (g.cnt + kBlock / 64 - 1) / (kBlock / 64);
+        hipLaunchKernelGGL(fe_critic_sgrad_da_kernel, dim3((unsigned)capped_grid(blocks)), dim3(kBlock),
+                           (size_t)4 * H * sizeof(float), st, *da, H);
+        if (int rc = launched(who, "d_actions")) return rc;
+    }
+    if (!final_kernel) return FE_OK;  // frozen: no weight contraction, no final write
+    hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
+                       dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
+                       st, g, H);
+    if (int rc = launched(who, "weight gradients")) return rc;
+    hipLaunchKernelGGL(final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
+    return launched(who, "final write");
+}
+
 int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
                               int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
                               int64_t count, const float *outputs, const float *d_outputs, float *workspace,
@@ -1880,10 +1963,7 @@ int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float 
     LstmSGradArgs g;
     memset(&g, 0, sizeof(g));
     g.lr32 = logret_f32; g.whh = whh; g.wx = wx; g.wout = wout; g.W = W; g.out_act = out_activation;
-    g.wt = workspace;  // the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest pass (pp pairs)
-    g.part = g.wt + lstm_sgrad_wt_floats(H);
-    g.hpart = g.part + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H);
-    g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+    sgrad_carve(g, workspace, H, pp);
     g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_out;
     g.g_bout = grads->b_out;
     hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
@@ -1891,49 +1971,16 @@ int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float 
     const void *kern = H == 256 ? (const void *)fe_lstm_sgrad_forward_kernel<4>
                                 : (H == 512 ? (const void *)fe_lstm_sgrad_forward_kernel<8>
                                             : (const void *)fe_lstm_sgrad_forward_kernel<16>);
-    int per_cu = 0;
-    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "streamed LSTM head gradient kernel: hipFuncSetAttribute / occupancy query");
-    int64_t resident = (int64_t)env->cus * per_cu;
-    if (resident < 1) resident = 1;
     // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
     for (int64_t c0 = 0; c0 < count; c0 += chunk) {
-        g.cnt = count - c0 < chunk ? count - c0 : chunk;
-        g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
-        g.splits = lstm_sgrad_splits(H, W, g.pp);
-        g.cst = g.gates + (int64_t)W * g.pp * 4 * H;
-        g.vst = g.cst + (int64_t)W * g.pp * H;
-        g.hw = g.vst + (int64_t)W * g.pp * (H + 32);
-        g.dh = g.hw + g.pp * H;
-        g.dc = g.dh + g.pp * H;
+        sgrad_chunk(g, H, c0, count, chunk);
         g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0;
         g.outputs = outputs ? outputs + c0 : nullptr; g.d_outputs = d_outputs + c0;
-        g.first = c0 == 0;
-        const int64_t tiles = g.pp / 32;
-        void *args[] = {&g};
-        if (int rc = launched("fe_lstm_backward_streamed: recurrence",
-                              hipLaunchKernel(kern, dim3((unsigned)(tiles < resident ? tiles : resident)),
-                                              dim3(kLstmBlock), args, lds, st)))
+        if (int rc = launch_sgrad_forward(env, kern, lds, &g, g.pp / 32,
+                                          "streamed LSTM head gradient kernel: hipFuncSetAttribute / occupancy query",
+                                          "fe_lstm_backward_streamed: recurrence", st))
             return rc;
-        hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
-        if (int rc = launched("fe_lstm_backward_streamed: head")) return rc;
-        for (int t = W - 1; t >= 0; --t) {
-            g.t = t;
-            hipLaunchKernelGGL(fe_lstm_sgrad_dz_kernel, dim3(grid_for(g.pp * (H / 4))), dim3(kBlock), 0, st, g, H);
-            if (t > 0)
-                hipLaunchKernelGGL(fe_lstm_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles),
-                                   dim3(kBlock), 0, st, g, H);
-            // a launch that fails fails the first time: stop before queueing 2 W launches behind it
-            if (t == W - 1) {
-                if (int rc = launched("fe_lstm_backward_streamed: backward through time")) return rc;
-            }
-        }
-        hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
-                           dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
-                           st, g, H);
-        if (int rc = launched("fe_lstm_backward_streamed: weight gradients")) return rc;
-        hipLaunchKernelGGL(fe_lstm_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
-        if (int rc = launched("fe_lstm_backward_streamed: final write")) return rc;
+        if (int rc = sgrad_backward_chunk(who, g, H, nullptr, fe_lstm_sgrad_final_kernel, st)) return rc;
     }
     return FE_OK;
 }
@@ -1952,20 +1999,7 @@ static int critic_streamed_check(const fe_env *env, int32_t H, const char *who) 
     return FE_OK;
 }
 
-// One launch of the recurrence over a.g.pp / 32 tiles: at most the resident workgroups, each looping over its tiles.
-static int launch_critic_sgrad_forward(fe_env *env, const void *kern, CriticSGradArgs &a, int32_t H, const char *who,
-                                       hipStream_t st) {
-    const size_t lds = critic_sgrad_forward_lds_bytes(H);
-    int per_cu = 0;
-    const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
-    if (he != hipSuccess) return hip_fail(he, "streamed critic kernel: hipFuncSetAttribute / occupancy query");
-    int64_t resident = (int64_t)env->cus * per_cu;
-    if (resident < 1) resident = 1;
-    const int64_t tiles = a.g.pp / 32;
-    void *args[] = {&a};
-    return launched(who, hipLaunchKernel(kern, dim3((unsigned)(tiles < resident ? tiles : resident)), dim3(kLstmBlock),
-                                         args, lds, st));
-}
+static const char *const kCriticSGradPrepare = "streamed critic kernel: hipFuncSetAttribute / occupancy query";
 
 // The forward-only recurrence for both critics, one after the other (a: descriptors, actions and ring already set).
 static int launch_twin_q_streamed(fe_env *env, CriticSGradArgs &a, const fe_critic_weights *c1, const fe_critic_weights *c2,
@@ -1976,7 +2010,9 @@ static int launch_twin_q_streamed(fe_env *env, CriticSGradArgs &a, const fe_crit
     a.g.W = env->p.W; a.g.cnt = count; a.g.pp = (count + 31) / 32 * 32;
     for (int i = 0; i < 2; ++i) {
         a.g.whh = c[i]->whh; a.g.wx = c[i]->wx; a.g.wout = c[i]->wout; a.bout = c[i]->bout; a.q_out = q[i];
-        if (int rc = launch_critic_sgrad_forward(env, kern, a, H, who, (hipStream_t)stream)) return rc;
+        if (int rc = launch_sgrad_forward(env, kern, critic_sgrad_forward_lds_bytes(H), &a, a.g.pp / 32, kCriticSGradPrepare, who,
+                                          (hipStream_t)stream))
+            return rc;
     }
     return FE_OK;
 }
@@ -2100,10 +2136,7 @@ int fe_twin_q_backward_streamed(fe_env *env, const float *logret_f32, const fe_c
         memset(&a, 0, sizeof(a));
         LstmSGradArgs &g = a.g;
         g.lr32 = logret_f32; g.whh = cw[i]->whh; g.wx = cw[i]->wx; g.wout = cw[i]->wout; g.W = W; g.out_act = 2;
-        g.wt = workspace;  // the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest pass (pp pairs)
-        g.part = g.wt + lstm_sgrad_wt_floats(H);
-        g.hpart = g.part + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H);
-        g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+        sgrad_carve(g, workspace, H, pp);
         if (cg[i]) {
             g.g_wih = cg[i]->w_ih; g.g_whh = cg[i]->w_hh; g.g_bih = cg[i]->b_ih; g.g_bhh = cg[i]->b_hh;
             g.g_wout = cg[i]->w_out; g.g_bout = cg[i]->b_out;
@@ -2113,46 +2146,15 @@ int fe_twin_q_backward_streamed(fe_env *env, const float *logret_f32, const fe_c
         if (int rc = launched("fe_twin_q_backward_streamed: weight transpose")) return rc;
         // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
         for (int64_t c0 = 0; c0 < count; c0 += chunk) {
-            g.cnt = count - c0 < chunk ? count - c0 : chunk;
-            g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
-            g.splits = lstm_sgrad_splits(H, W, g.pp);
-            g.cst = g.gates + (int64_t)W * g.pp * 4 * H;
-            g.vst = g.cst + (int64_t)W * g.pp * H;
-            g.hw = g.vst + (int64_t)W * g.pp * (H + 32);
-            g.dh = g.hw + g.pp * H;
-            g.dc = g.dh + g.pp * H;
+            sgrad_chunk(g, H, c0, count, chunk);
             g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0; g.d_outputs = dq[i] + c0;
-            g.first = c0 == 0;
             a.actions = actions + c0;
             a.da = d_actions ? d_actions + c0 : nullptr;
-            const int64_t tiles = g.pp / 32;
-            if (int rc = launch_critic_sgrad_forward(env, kern, a, H, "fe_twin_q_backward_streamed: recurrence", st)) return rc;
-            hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
-            if (int rc = launched("fe_twin_q_backward_streamed: head")) return rc;
-            for (int t = W - 1; t >= 0; --t) {
-                g.t = t;
-                hipLaunchKernelGGL(fe_lstm_sgrad_dz_kernel, dim3(grid_for(g.pp * (H / 4))), dim3(kBlock), 0, st, g, H);
-                if (t > 0)
-                    hipLaunchKernelGGL(fe_lstm_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles),
-                                       dim3(kBlock), 0, st, g, H);
-                // a launch that fails fails the first time: stop before queueing 2 W launches behind it
-                if (t == W - 1) {
-                    if (int rc = launched("fe_twin_q_backward_streamed: backward through time")) return rc;
-                }
-            }
-            if (a.da) {
-                const int64_t blocks = (g.cnt + kBlock / 64 - 1) / (kBlock / 64);
-                hipLaunchKernelGGL(fe_critic_sgrad_da_kernel, dim3((unsigned)capped_grid(blocks)), dim3(kBlock),
-                                   (size_t)4 * H * sizeof(float), st, a, H);
-                if (int rc = launched("fe_twin_q_backward_streamed: d_actions")) return rc;
-            }
-            if (!cg[i]) continue;  // frozen: no weight contraction, no final write
-            hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
-                               dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
-                               st, g, H);
-            if (int rc = launched("fe_twin_q_backward_streamed: weight gradients")) return rc;
-            hipLaunchKernelGGL(fe_critic_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
-            if (int rc = launched("fe_twin_q_backward_streamed: final write")) return rc;
+            if (int rc = launch_sgrad_forward(env, kern, critic_sgrad_forward_lds_bytes(H), &a, g.pp / 32, kCriticSGradPrepare,
+                                              "fe_twin_q_backward_streamed: recurrence", st))
+                return rc;
+            if (int rc = sgrad_backward_chunk(who, g, H, a.da ? &a : nullptr, cg[i] ? fe_critic_sgrad_final_kernel : nullptr, st))
+                return rc;
         }
         if (d_actions) ++ran;
     }

@@ -91,157 +91,13 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_pack_kernel(const LstmSG
     }
 }
 
-// The recurrence of fe_rollout_lstm_big_kernel (forward only, A = 1) with its activations written out.  One 32-pair tile
-// per workgroup at a time; c_t and the pending h_t in per-lane scratch, as there.
+// The recurrence of fe_rollout_lstm_big_kernel (forward only, A = 1) with its activations written out: the tile loop it
+// shares with fe_critic_sgrad_forward_kernel, without the action slot.
 template <int RTW>
 __global__ __launch_bounds__(kLstmBlock, 2) void fe_lstm_sgrad_forward_kernel(const LstmSGradArgs g) {
-    constexpr int H = 64 * RTW, HP = H + 4, NG = H / 8, G4 = 4 * H, VN = H + 32;
-    constexpr int RI = kLstmBigRI, AHEAD = kLstmBigAhead;
-    static_assert(RTW % RI == 0 && (H / 8) % AHEAD == 0, "row tiles / k groups must come in whole groups");
-    extern __shared__ __align__(16) unsigned char smem[];
-    int64_t *s_src = reinterpret_cast<int64_t *>(smem);      // [32]
-    float *s_pos = reinterpret_cast<float *>(s_src + 32);    // [32]
-    float *s_h = s_pos + 32;                                 // [32][HP]
-    const int W = g.W;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, half = lane >> 5;
-    const int mt0 = wave * RTW;  // this wavefront's row tiles: mt0 .. mt0 + RTW - 1
-    const int64_t pp = g.pp, num_tiles = pp / 32;
-    float4 wq[kLstmBigAhead][kLstmBigRI];  // weight fragments in flight (see the k loop)
-    bool primed = false;
-
-    for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * 32;
-        const int pairs = g.cnt - n0 < 32 ? (int)(g.cnt - n0) : 32;
-        if (tid < 32) {  // a pair past the batch computes on the last one's descriptor (its upstream gradient is zero)
-            const int64_t n = n0 + (tid < pairs ? tid : pairs - 1);
-            s_src[tid] = g.obs_src[n];
-            s_pos[tid] = (float)g.obs_pos[n];
-        }
-        __syncthreads();
-        for (int i = tid; i < W * 32 * 32; i += kLstmBlock) {  // x_t into the stash
-            const int t = i >> 10, p = (i >> 5) & 31, j = i & 31;
-            const float v = j < 4 ? g.lr32[s_src[p] + 4 * t + j] : (j == 4 ? s_pos[p] : (j == 5 ? 1.0f : 0.0f));
-            g.vst[((int64_t)t * pp + n0 + p) * VN + H + j] = v;
-        }
-        for (int i = tid; i < 32 * H; i += kLstmBlock) g.vst[(n0 + i / H) * VN + i % H] = 0.0f;  // h_{-1}
-
-        const float *xsrc = g.lr32 + s_src[col];
-        const float4 xh = make_float4(s_pos[col], 1.0f, 0.0f, 0.0f);
-        float4 xc = half == 0 ? *reinterpret_cast<const float4 *>(xsrc) : xh;
-        float cst[RTW][4], hnew[RTW][4];
-#pragma unroll
-        for (int i = 0; i < RTW; ++i)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) cst[i][b] = 0.0f;
-        for (int t = 0; t < W; ++t) {
-            const int tn = t + 1 < W ? t + 1 : t;
-            const float4 xn = half == 0 ? *reinterpret_cast<const float4 *>(xsrc + 4 * tn) : xh;
-            const float *hrow = s_h + (size_t)col * HP + 4 * half;
-            const int64_t row = (int64_t)t * pp + n0 + col;  // this lane's (t, pair) row of the stash
-            float *grow = g.gates + row * G4 + 4 * half;
-            float *crow = g.cst + row * H + 4 * half;
-            // h_t is the h_{t-1} of step t + 1; the last one is h_W
-            float *hout = (t + 1 < W ? g.vst + (row + pp) * VN : g.hw + (n0 + col) * (int64_t)H) + 4 * half;
-#pragma unroll 1
-            for (int i0 = 0; i0 < RTW; i0 += RI) {
-                f32x16 acc[RI];
-#pragma unroll
-                for (int i = 0; i < RI; ++i)
-#pragma unroll
-                    for (int rr = 0; rr < 16; ++rr) acc[i][rr] = 0.0f;
-                // input part: four MFMAs per row tile
-                float4 wxv[RI];
-#pragma unroll
-                for (int i = 0; i < RI; ++i)
-                    wxv[i] = *reinterpret_cast<const float4 *>(g.wx + ((size_t)32 * (mt0 + i0 + i) + col) * 8 + 4 * half);
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const float xs = m == 0 ? xc.x : (m == 1 ? xc.y : (m == 2 ? xc.z : xc.w));
-                        const float ws = m == 0 ? wxv[i].x : (m == 1 ? wxv[i].y : (m == 2 ? wxv[i].z : wxv[i].w));
-                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, xs, acc[i], 0, 0, 0);
-                    }
-                if (t > 0) {
-                    // fragment-major weights: one coalesced KiB per (row tile, k group), AHEAD groups in flight across row-tile
-                    // groups, time steps and tiles (the matrix never changes)
-                    const float4 *wbase = reinterpret_cast<const float4 *>(g.whh) + lane;
-                    const float4 *wf[RI], *wfn[RI];
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        wf[i] = wbase + ((size_t)(mt0 + i0 + i) * NG) * 64;
-                        wfn[i] = wbase + ((size_t)(mt0 + (i0 + RI < RTW ? i0 + RI : 0) + i) * NG) * 64;
-                    }
-                    if (!primed) {
-#pragma unroll
-                        for (int d = 0; d < AHEAD; ++d)
-#pragma unroll
-                            for (int i = 0; i < RI; ++i) wq[d][i] = wf[i][(size_t)d * 64];
-                        primed = true;
-                    }
-#pragma unroll 1  // a real loop: unrolled, its hoisted loads spill
-                    for (int g0 = 0; g0 < NG; g0 += AHEAD) {
-#pragma unroll
-                        for (int d = 0; d < AHEAD; ++d) {
-                            const int gg = g0 + d;
-                            float4 wv[RI];
-                            const int gn = gg + AHEAD;
-#pragma unroll
-                            for (int i = 0; i < RI; ++i) {
-                                wv[i] = wq[d][i];
-                                wq[d][i] = gn < NG ? wf[i][(size_t)gn * 64] : wfn[i][(size_t)(gn - NG) * 64];
-                            }
-                            const float4 hb = *reinterpret_cast<const float4 *>(hrow + 8 * gg);
-#pragma unroll
-                            for (int m = 0; m < 4; ++m) {
-                                const float hs = m == 0 ? hb.x : (m == 1 ? hb.y : (m == 2 ? hb.z : hb.w));
-#pragma unroll
-                                for (int i = 0; i < RI; ++i) {
-                                    const float ws = m == 0 ? wv[i].x : (m == 1 ? wv[i].y : (m == 2 ? wv[i].z : wv[i].w));
-                                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, hs, acc[i], 0, 0, 0);
-                                }
-                            }
-                        }
-                    }
-                }
-                // cell update, in-lane: acc[4b + gate] is unit 8 mt + 4 half + b of pair col.  The stash gets the gates, c_t and
-                // h_t now; the LDS copy of h_t waits (in scratch) until everyone has read the old one
-#pragma unroll
-                for (int i = 0; i < RI; ++i) {
-                    const int mt = mt0 + i0 + i;
-                    float og[4];
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const v2f sif = lstm_act2<false, false>((v2f){acc[i][4 * b + 0], acc[i][4 * b + 1]});
-                        const v2f tgo = lstm_act2<true, false>((v2f){acc[i][4 * b + 2], acc[i][4 * b + 3]});
-                        const float t1 = sif.y * cst[i0 + i][b];
-                        const float t2 = sif.x * tgo.x;
-                        cst[i0 + i][b] = t1 + t2;
-                        og[b] = tgo.y;
-                        *reinterpret_cast<float4 *>(grow + 32 * mt + 8 * b) = make_float4(sif.x, sif.y, tgo.x, tgo.y);
-                    }
-#pragma unroll
-                    for (int b = 0; b < 4; b += 2) {
-                        const v2f tc = lstm_act2<true, true>((v2f){cst[i0 + i][b], cst[i0 + i][b + 1]});
-                        hnew[i0 + i][b] = og[b] * tc.x;
-                        hnew[i0 + i][b + 1] = og[b + 1] * tc.y;
-                    }
-                    *reinterpret_cast<float4 *>(crow + 8 * mt) =
-                        make_float4(cst[i0 + i][0], cst[i0 + i][1], cst[i0 + i][2], cst[i0 + i][3]);
-                    *reinterpret_cast<float4 *>(hout + 8 * mt) =
-                        make_float4(hnew[i0 + i][0], hnew[i0 + i][1], hnew[i0 + i][2], hnew[i0 + i][3]);
-                }
-            }
-            lds_barrier();  // every wavefront has read h_{t-1}
-#pragma unroll
-            for (int i = 0; i < RTW; ++i)
-                *reinterpret_cast<float4 *>(s_h + (size_t)col * HP + 8 * (mt0 + i) + 4 * half) =
-                    make_float4(hnew[i][0], hnew[i][1], hnew[i][2], hnew[i][3]);
-            xc = xn;
-            lds_barrier();  // h_t is complete
-        }
-        __syncthreads();  // the descriptors and h are free for the next tile
-    }
+#define FE_LSTM_STREAM_ACTION 0
+#include "fe_lstm_stream_sgrad_body.h"
+#undef FE_LSTM_STREAM_ACTION
 }
 
 // The head's backward (networks/lstm.py:55-56 differentiated) for one 256-pair block per workgroup: dh_W = w_out dp and
@@ -423,8 +279,11 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_wgrad_kernel(const LstmS
 
 // The split sums added in split order (the head's block sums in block order) and written in torch's row order: packed
 // gate row R = 32 mt + 8 b + 4 half + gate is row gate H + 8 mt + 4 half + b of the 4H-row tensors (lstm_row_order's
-// inverse).  The first chunk overwrites the gradients, a later one adds to them.
-__global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_final_kernel(const LstmSGradArgs g, int32_t H) {
+// inverse).  NX input columns (5: the head; 6: the critic): column n - H < 5 of a split sum is w_ih[row, n - H], column 5
+// the bias, column 6 (the action's slot, NX = 6) w_ih[row, 5]; the rest of the input tile is skipped.  The first chunk
+// overwrites the gradients, a later one adds to them.
+template <int NX>
+__device__ __forceinline__ void lstm_sgrad_final(const LstmSGradArgs &g, int32_t H) {
     const int64_t stride = (int64_t)gridDim.x * kBlock, i0 = blockIdx.x * (int64_t)kBlock + threadIdx.x;
     const int64_t VN = H + 32, PV = lstm_sgrad_part_floats(H), E = PV + H + 1;
     const int64_t blocks = lstm_sgrad_head_blocks(g.pp);
@@ -433,14 +292,14 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_final_kernel(const LstmS
         float s = 0.0f;
         if (e < PV) {
             const int64_t R = e / VN, n = e - R * VN;
-            if (n >= H + 6) continue;  // the input tile's unused columns
+            if (n >= H + NX + 1) continue;  // the input tile's unused columns
             for (int64_t k = 0; k < g.splits; ++k) s += g.part[k * PV + e];
             const int64_t rho = R & 31, row = (rho & 3) * H + 8 * (R >> 5) + 4 * ((rho >> 2) & 1) + (rho >> 3);
             if (n < H) {
                 float *o = g.g_whh + row * H + n;
                 *o = first ? s : *o + s;
-            } else if (n - H < 5) {
-                float *o = g.g_wih + row * 5 + (n - H);
+            } else if (NX == 6 ? n - H != 5 : n - H < 5) {  // (each width its own statements: the head's compile as before)
+                float *o = g.g_wih + row * NX + (NX == 6 ? (n - H < 5 ? n - H : 5) : n - H);
                 *o = first ? s : *o + s;
             } else {
                 s = first ? s : g.g_bih[row] + s;
@@ -453,6 +312,10 @@ __global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_final_kernel(const LstmS
             *o = first ? s : *o + s;
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void fe_lstm_sgrad_final_kernel(const LstmSGradArgs g, int32_t H) {
+    lstm_sgrad_final<5>(g, H);
 }
 
 }  // namespace

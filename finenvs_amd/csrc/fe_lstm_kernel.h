@@ -160,10 +160,7 @@ __host__ __device__ inline size_t lstm_big_lds_bytes(int EB, int A, int H) {
 
 template <bool SINGLE, int RTW>
 __global__ __launch_bounds__(kLstmBlock, 2) void fe_rollout_lstm_big_kernel(const Params p, const LstmArgs r) {
-    constexpr int H = 64 * RTW, HP = H + 4, NG = H / 8, SP = 32;
-    constexpr int RI = kLstmBigRI;  // row tiles run together: RI independent accumulator chains share every B fragment
-    constexpr int AHEAD = kLstmBigAhead;  // k groups a weight fragment is loaded ahead of its MFMAs
-    static_assert(RTW % RI == 0 && (H / 8) % AHEAD == 0, "row tiles / k groups must come in whole groups");
+    constexpr int H = 64 * RTW, HP = H + 4, SP = 32;
     extern __shared__ __align__(16) unsigned char smem[];
     const int A = SINGLE ? 1 : p.A;
     const int EB = p.EB;
@@ -184,8 +181,10 @@ __global__ __launch_bounds__(kLstmBlock, 2) void fe_rollout_lstm_big_kernel(cons
     const int64_t NA = p.N * A;
     const int64_t rstride = 4 * (int64_t)A;
     const int mt0 = wave * RTW;  // this wavefront's row tiles: mt0 .. mt0 + RTW - 1
-    float4 wq[kLstmBigAhead][kLstmBigRI];  // weight fragments in flight (see the k loop)
+    float4 wq[kLstmBigAhead][kLstmBigRI];  // weight fragments in flight (fe_lstm_stream_tile.h)
     bool primed = false;
+    constexpr bool STASH = false;  // nothing goes to a workspace: the rows fe_lstm_stream_tile.h would write are null
+    float *const grow = nullptr, *const crow = nullptr, *const hout = nullptr;
     for (int i = tid; i < H; i += kLstmBlock) s_wout[i] = r.wout[i];
 
     for (int64_t tile = blockIdx.x; tile < p.num_tiles; tile += gridDim.x) {
@@ -222,92 +221,14 @@ __global__ __launch_bounds__(kLstmBlock, 2) void fe_rollout_lstm_big_kernel(cons
                 const int tn = t + 1 < W ? t + 1 : t;
                 const float4 xn = half == 0 ? *reinterpret_cast<const float4 *>(xsrc + (int64_t)tn * rstride) : xh;
                 const float *hrow = s_h + (size_t)col * HP + 4 * half;
-                // a real loop over this wavefront's row-tile pairs: c_t and the pending h_t (RTW x 4 floats each per lane,
+                // a real loop over this wavefront's row-tile groups: c_t and the pending h_t (RTW x 4 floats each per lane,
                 // touched once per 1040 MFMAs) are indexed dynamically, i.e. live in per-lane scratch, not in VGPRs
+#define FE_LSTM_STREAM_ARGS r
 #pragma unroll 1
-                for (int i0 = 0; i0 < RTW; i0 += RI) {
-                    f32x16 acc[RI];
-#pragma unroll
-                    for (int i = 0; i < RI; ++i)
-#pragma unroll
-                        for (int rr = 0; rr < 16; ++rr) acc[i][rr] = 0.0f;
-                    // input part: four MFMAs per row tile
-                    float4 wxv[RI];
-#pragma unroll
-                    for (int i = 0; i < RI; ++i)
-                        wxv[i] = *reinterpret_cast<const float4 *>(r.wx + ((size_t)32 * (mt0 + i0 + i) + col) * 8 + 4 * half);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m)
-#pragma unroll
-                        for (int i = 0; i < RI; ++i) {
-                            const float xs = m == 0 ? xc.x : (m == 1 ? xc.y : (m == 2 ? xc.z : xc.w));
-                            const float ws = m == 0 ? wxv[i].x : (m == 1 ? wxv[i].y : (m == 2 ? wxv[i].z : wxv[i].w));
-                            acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, xs, acc[i], 0, 0, 0);
-                        }
-                    if (t > 0) {
-                        // fragment-major weights: one coalesced KiB per (row tile, k group), AHEAD groups in flight -- across
-                        // row-tile groups and time steps too: the tail of one k loop already fetches the head of the next
-                        // (the next group's, or after the last group the first one's again: the matrix never changes)
-                        const float4 *wbase = reinterpret_cast<const float4 *>(r.whh) + lane;
-                        const float4 *wf[RI], *wfn[RI];
-#pragma unroll
-                        for (int i = 0; i < RI; ++i) {
-                            wf[i] = wbase + ((size_t)(mt0 + i0 + i) * NG) * 64;
-                            wfn[i] = wbase + ((size_t)(mt0 + (i0 + RI < RTW ? i0 + RI : 0) + i) * NG) * 64;
-                        }
-                        if (!primed) {
-#pragma unroll
-                            for (int d = 0; d < AHEAD; ++d)
-#pragma unroll
-                                for (int i = 0; i < RI; ++i) wq[d][i] = wf[i][(size_t)d * 64];
-                            primed = true;
-                        }
-#pragma unroll 1  // a real loop: unrolled, its hoisted loads spill (NG is up to 128 groups of 4 RI MFMAs)
-                        for (int g0 = 0; g0 < NG; g0 += AHEAD) {
-#pragma unroll
-                            for (int d = 0; d < AHEAD; ++d) {
-                                const int g = g0 + d;
-                                float4 wv[RI];
-                                const int gn = g + AHEAD;
-#pragma unroll
-                                for (int i = 0; i < RI; ++i) {
-                                    wv[i] = wq[d][i];
-                                    wq[d][i] = gn < NG ? wf[i][(size_t)gn * 64] : wfn[i][(size_t)(gn - NG) * 64];
-                                }
-                                const float4 hb = *reinterpret_cast<const float4 *>(hrow + 8 * g);
-#pragma unroll
-                                for (int m = 0; m < 4; ++m) {
-                                    const float hs = m == 0 ? hb.x : (m == 1 ? hb.y : (m == 2 ? hb.z : hb.w));
-#pragma unroll
-                                    for (int i = 0; i < RI; ++i) {
-                                        const float ws = m == 0 ? wv[i].x : (m == 1 ? wv[i].y : (m == 2 ? wv[i].z : wv[i].w));
-                                        acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(ws, hs, acc[i], 0, 0, 0);
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    // cell update, in-lane; the new h waits (in scratch) until everyone has read the old one
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        float og[4];
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const v2f sif = lstm_act2<false, false>((v2f){acc[i][4 * b + 0], acc[i][4 * b + 1]});
-                            const v2f tgo = lstm_act2<true, false>((v2f){acc[i][4 * b + 2], acc[i][4 * b + 3]});
-                            const float t1 = sif.y * cst[i0 + i][b];
-                            const float t2 = sif.x * tgo.x;
-                            cst[i0 + i][b] = t1 + t2;
-                            og[b] = tgo.y;
-                        }
-#pragma unroll
-                        for (int b = 0; b < 4; b += 2) {
-                            const v2f tc = lstm_act2<true, true>((v2f){cst[i0 + i][b], cst[i0 + i][b + 1]});
-                            hnew[i0 + i][b] = og[b] * tc.x;
-                            hnew[i0 + i][b + 1] = og[b + 1] * tc.y;
-                        }
-                    }
+                for (int i0 = 0; i0 < RTW; i0 += kLstmBigRI) {
+#include "fe_lstm_stream_tile.h"
                 }
+#undef FE_LSTM_STREAM_ARGS
                 lds_barrier();  // every wavefront has read h_{t-1}
 #pragma unroll
                 for (int i = 0; i < RTW; ++i)

@@ -3,6 +3,8 @@ include/finenvs_amd_critic_streamed.h), with the helpers and the yardstick of te
 
 * anchor: with ``w_ih[:, 5] = 0`` a critic's value is ``fe_lstm_forward(out_activation 2)`` on the same weights bit for
   bit;
+* the same anchor for the backward: ``fe_twin_q_backward_streamed`` on that critic gives ``fe_lstm_backward_streamed``'s
+  ``w_hh``, ``w_ih[:, :5]``, ``b_ih``, ``b_hh``, ``w_out`` and ``b_out`` bit for bit;
 * values against an f64 torch ``CriticLSTM`` on the rendered states within ``2e-5 max|q64| + 4 max|q32 - q64|``; ``q()``
   returns ``forward``'s bits;
 * the thirteen gradients (twelve parameter tensors and ``d_actions``) against f64 within ``2e-5 max|g64| +
@@ -101,6 +103,59 @@ def test_zero_action_weight_equals_the_lstm_value_head_bit_for_bit(H, W, B):
     want = head.forward(src, pos)
     assert float(want.abs().max()) > 0.1 and float((q2 - q1).abs().max()) > 1e-3
     assert_bits(q1, want)
+
+
+def zero_action_weight_backward(env, src, pos, H, W, B):
+    """fe_twin_q_backward_streamed (critic 1 alone, ``w_ih[:, 5] = 0``) and fe_lstm_backward_streamed (no output activation)
+    on the same packed weights, descriptors and upstream gradient: ``(critic's six gradient tensors, head's six)``."""
+    import ctypes as C
+
+    from finenvs_amd import _lib
+    from finenvs_amd.critic import GRAD_KEYS, empty_packed_grads, pack_critic_weights
+
+    lib = env._lib
+    c = _critic(H, W, 10)
+    with torch.no_grad():
+        c.lstm.weight_ih_l0[:, 5].zero_()
+    w = pack_critic_weights(c)
+    assert float(w["wx"][:, 6].abs().max()) == 0.0
+    cw = _lib.FeCriticWeights(*(w[k].data_ptr() for k in ("whh", "wx", "wout", "bout")))
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    actions = torch.rand((B,), generator=gen, device="cuda") * 2 - 1  # they reach nothing: their weight is zero
+    d = (torch.randn((B,), generator=gen, device="cuda") - 1.0) / B
+    lr32 = env.log_return_environments.float().contiguous()
+    nan = float("nan")  # whatever a kernel leaves unwritten, in a workspace of its own or in an output, stays NaN
+    n_ws = int(lib.fe_twin_q_streamed_grad_workspace_floats(H, W, B))
+    assert n_ws == int(lib.fe_lstm_streamed_grad_workspace_floats(H, W, B))
+    ws_critic, ws_head = (torch.full((n_ws,), nan, device="cuda") for _ in range(2))
+    critic = {k: v.fill_(nan) for k, v in empty_packed_grads(H, "cuda").items()}
+    head = {k: torch.full((4 * H, 5) if k == "w_ih" else tuple(v.shape), nan, device="cuda") for k, v in critic.items()}
+    cg = _lib.FeCriticGrads(*(critic[k].data_ptr() for k in GRAD_KEYS))
+    lg = _lib.FeLstmGrads(*(head[k].data_ptr() for k in GRAD_KEYS))
+    src, pos = src.reshape(B).contiguous(), pos.reshape(B).contiguous()
+    _lib.check(lib.fe_twin_q_backward_streamed(
+        env._handle, lr32.data_ptr(), C.byref(cw), C.byref(cw), H, src.data_ptr(), pos.data_ptr(), actions.data_ptr(), B,
+        d.data_ptr(), None, ws_critic.data_ptr(), C.byref(cg), None, None, env._stream()), lib)
+    _lib.check(lib.fe_lstm_backward_streamed(
+        env._handle, lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wout"].data_ptr(), H, 2, src.data_ptr(),
+        pos.data_ptr(), B, None, d.data_ptr(), ws_head.data_ptr(), C.byref(lg), env._stream()), lib)
+    return critic, head
+
+
+# a partial 32-pair tile; a second, partial 256-pair head block
+@pytest.mark.parametrize("H,W,B", [(256, 4, 33), (512, 5, 257)])
+def test_zero_action_weight_backward_equals_the_lstm_value_heads_bit_for_bit(H, W, B):
+    """The backward counterpart of the anchor above: the action's column only adds ``0 x action`` to the forward's chains,
+    and the output columns of the weight contraction are independent, so the critic's gradients are the head's."""
+    env = _env(min(B, 4096), W)
+    src, pos, _ = _descriptors(env, B)
+    critic, head = zero_action_weight_backward(env, src, pos, H, W, B)
+    for k in critic:  # every element of every output was written by its own call
+        assert bool(torch.isfinite(critic[k]).all()) and bool(torch.isfinite(head[k]).all()), k
+        assert float(head[k].abs().max()) > 0, k
+    for k in ("w_hh", "b_ih", "b_hh", "w_out", "b_out"):
+        assert_bits(critic[k], head[k])
+    assert_bits(critic["w_ih"][:, :5].contiguous(), head["w_ih"])
 
 
 @pytest.mark.parametrize("H,W,B", [(256, 4, 33), (512, 5, 257), (1024, 4, 1100)])
