@@ -38,8 +38,13 @@ graph.  The first iteration that trains also runs the capture's three warm-up up
 read from the device only for iterations that are logged.  The draws differ from the other paths' (Philox on the
 device instead of ``torch.randint``), so the losses are comparable in distribution, not number for number.
 
-    python examples/sac_time_series.py [--envs 1024] [--iterations 100] [--chunk 8] [--batch 256] [--fused-targets]
-                                       [--fused-critics] [--fused-actor] [--fused-optim] [--graph-update]
+With ``--hidden`` above 128 (256, 512 or 1024; the reference trains ``hidden_dim=1024``) the actor's rollout and
+every fused front end the flags above select are built with ``streamed=True``: the kernels whose recurrent weights
+stream from L2 (include/finenvs_amd_sac_streamed.h, include/finenvs_amd_critic_streamed.h).
+
+    python examples/sac_time_series.py [--envs 1024] [--hidden 128] [--iterations 100] [--chunk 8] [--batch 256]
+                                       [--fused-targets] [--fused-critics] [--fused-actor] [--fused-optim]
+                                       [--graph-update]
 """
 import argparse
 import copy
@@ -96,9 +101,10 @@ def iterate(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=
         critic_opt = torch.optim.Adam(list(critic_1.parameters()) + list(critic_2.parameters()), lr=lr)
         resident_a = resident_c = {}
     # without weights= the front ends re-pack their modules at every call: updates are seen right away either way
-    roll = FusedSACRollout(env, actor, **resident_a)
-    twin = FusedTwinCritic(env, critic_1t, critic_2t, **resident_c) if fused_targets else None
-    twin_online = FusedTwinCritic(env, critic_1, critic_2, **resident_c) if fused_critics else None
+    streamed = {"streamed": True} if hidden > 128 else {}  # the kernels of H = 256 / 512 / 1024 are an opt-in
+    roll = FusedSACRollout(env, actor, **resident_a, **streamed)
+    twin = FusedTwinCritic(env, critic_1t, critic_2t, **resident_c, **streamed) if fused_targets else None
+    twin_online = FusedTwinCritic(env, critic_1, critic_2, **resident_c, **streamed) if fused_critics else None
     gen = torch.Generator(device=dev).manual_seed(seed)
     render = not (fused_critics and fused_actor)  # somebody still reads the rendered states
     graphed, draw = None, buffer.new_draw(batch) if graph_update else None
@@ -210,6 +216,7 @@ def main(num_envs=1024, window=4, hidden=128, iterations=100, chunk=8, batch=256
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--iterations", type=int, default=100)
     ap.add_argument("--chunk", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256)
@@ -219,6 +226,6 @@ if __name__ == "__main__":
     ap.add_argument("--fused-optim", action="store_true")
     ap.add_argument("--graph-update", action="store_true")
     a = ap.parse_args()
-    main(a.envs, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
+    main(a.envs, hidden=a.hidden, iterations=a.iterations, chunk=a.chunk, batch=a.batch, fused_targets=a.fused_targets,
          fused_critics=a.fused_critics, fused_actor=a.fused_actor, fused_optim=a.fused_optim,
          graph_update=a.graph_update)

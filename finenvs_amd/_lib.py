@@ -245,6 +245,15 @@ OPTIM_SIGNATURES = {
                                     _vp, _vp, _vp, C.POINTER(FeSacGrads), _vp]),
 }
 
+# include/finenvs_amd_sac_streamed.h: the SAC actor at H = 256 / 512 / 1024 (FeSacGrads again); each entry takes the
+# argument list of its register-resident namesake with the two output biases in device memory (the *_p form)
+SAC_STREAMED_SIGNATURES = {
+    "fe_env_rollout_sac_streamed": OPTIM_SIGNATURES["fe_env_rollout_sac_p"],
+    "fe_sac_forward_streamed": OPTIM_SIGNATURES["fe_sac_forward_p"],
+    "fe_sac_streamed_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_sac_backward_streamed": OPTIM_SIGNATURES["fe_sac_backward_p"],
+}
+
 # include/finenvs_amd_replay_cursor.h: the ring's cursor in device memory and the draw from it (finenvs_amd/replay.py)
 CURSOR_HEAD, CURSOR_SIZE, CURSOR_DRAWS, CURSOR_TICKET, CURSOR_WORDS = 0, 1, 2, 3, 4  # int64 words of fe_replay_cursor
 REPLAY_CURSOR_SIGNATURES = {
@@ -299,7 +308,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
     for name, (res, args) in {**SIGNATURES, **EXT_SIGNATURES, **EVO_SIGNATURES, **REPLAY_SIGNATURES, **SAC_SIGNATURES,
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
-                         **OPTIM_SIGNATURES,
+                         **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
                          **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res

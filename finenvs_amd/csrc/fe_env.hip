@@ -47,6 +47,7 @@
 //   fe_sac_grad_kernels.h     the SAC actor's backward pass (tanh-Gaussian head, last layer, recurrence) and its reduction
 //   fe_lstm_grad_kernels.h    the one-output LSTM head's backward pass (PPO actor / critic, TD3 actor) and its reduction
 //   fe_critic_streamed_kernels.h  the twin critics at H = 256 / 512 / 1024: streamed values, targets and backward pass
+//   fe_sac_streamed_kernels.h     the SAC actor at H = 256 / 512 / 1024: acting, forward and backward pass (streamed)
 //   fe_env.hip            (this file) host side: launch helpers (compile-time dispatch, launch epilogue, rollout
 //                         geometry, big-LDS launches), launch geometry of the step, the env object, the C ABI of the
 //                         headers in include/
@@ -78,6 +79,7 @@
 #include "finenvs_amd_lstm_grad.h"
 #include "finenvs_amd_lstm_grad_streamed.h"
 #include "finenvs_amd_critic_streamed.h"
+#include "finenvs_amd_sac_streamed.h"
 #include "finenvs_amd_optim.h"
 #include "finenvs_amd_replay_cursor.h"
 #include "finenvs_amd_ppo.h"
@@ -98,6 +100,7 @@
 #include "fe_lstm_grad_kernels.h"
 #include "fe_lstm_grad_streamed_kernels.h"
 #include "fe_critic_streamed_kernels.h"
+#include "fe_sac_streamed_kernels.h"
 #include "fe_optim_kernels.h"
 
 namespace {
@@ -1900,11 +1903,22 @@ static int launch_sgrad_forward(const fe_env *env, const void *kern, size_t lds,
 // A chunk after its recurrence: head -> (dz [, dh]) x W -> [d_actions] -> [weight contraction -> final write], every launch
 // reported as "<who>: <stage>".  `da`: the critic's argument block around g when d_actions are wanted, else null.
 // `final_kernel` null: a frozen critic.
+// `sac`: the SAC actor's argument block around g (g IS sac->g): its head stages (z, head, dh_W) replace the one-output
+// head's, its last-layer contraction follows the LSTM's and its final kernel writes all ten tensors (final_kernel unused).
 static int sgrad_backward_chunk(const char *who, LstmSGradArgs &g, int32_t H, const CriticSGradArgs *da,
-                                void (*final_kernel)(LstmSGradArgs, int32_t), hipStream_t st) {
+                                void (*final_kernel)(LstmSGradArgs, int32_t), hipStream_t st,
+                                const SacSGradArgs *sac = nullptr) {
     const int W = g.W;
     const int64_t tiles = g.pp / 32;
-    hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
+    if (sac) {
+        hipLaunchKernelGGL(fe_sac_sgrad_z_kernel, dim3((unsigned)(H / 128), (unsigned)tiles), dim3(kBlock), 0, st, *sac, H);
+        if (int rc = launched(who, "last layer")) return rc;
+        hipLaunchKernelGGL(fe_sac_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, *sac, H);
+        hipLaunchKernelGGL(fe_sac_sgrad_dh_kernel, dim3((unsigned)(H / kLstmSGradDhUnits), (unsigned)tiles), dim3(kBlock), 0,
+                           st, *sac, H);
+    } else {
+        hipLaunchKernelGGL(fe_lstm_sgrad_head_kernel, dim3((unsigned)lstm_sgrad_head_blocks(g.pp)), dim3(kBlock), 0, st, g, H);
+    }
     if (int rc = launched(who, "head")) return rc;
     for (int t = W - 1; t >= 0; --t) {
         g.t = t;
@@ -1923,11 +1937,18 @@ static int sgrad_backward_chunk(const char *who, LstmSGradArgs &g, int32_t H, co
                            (size_t)4 * H * sizeof(float), st, *da, H);
         if (int rc = launched(who, "d_actions")) return rc;
     }
-    if (!final_kernel) return FE_OK;  // frozen: no weight contraction, no final write
+    if (!final_kernel && !sac) return FE_OK;  // frozen: no weight contraction, no final write
     hipLaunchKernelGGL(fe_lstm_sgrad_wgrad_kernel,
                        dim3((unsigned)(4 * H / kLstmSGradWgRows * ((H + 32) / 32)), (unsigned)g.splits), dim3(kBlock), 0,
                        st, g, H);
     if (int rc = launched(who, "weight gradients")) return rc;
+    if (sac) {
+        hipLaunchKernelGGL(fe_sac_sgrad_wl_kernel, dim3((unsigned)(H / kLstmSGradWgRows * (H / 32)), (unsigned)sac->wl_splits),
+                           dim3(kBlock), 0, st, *sac, H);
+        if (int rc = launched(who, "last layer weight gradients")) return rc;
+        hipLaunchKernelGGL(fe_sac_sgrad_final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, *sac, H);
+        return launched(who, "final write");
+    }
     hipLaunchKernelGGL(final_kernel, dim3(grid_for(lstm_sgrad_part_floats(H))), dim3(kBlock), 0, st, g, H);
     return launched(who, "final write");
 }
@@ -2157,6 +2178,145 @@ int fe_twin_q_backward_streamed(fe_env *env, const float *logret_f32, const fe_c
                 return rc;
         }
         if (d_actions) ++ran;
+    }
+    return FE_OK;
+}
+
+// ---- include/finenvs_amd_sac_streamed.h: the SAC actor at H = 256 / 512 / 1024 ----
+static int sac_streamed_hidden(int32_t H, const char *who, const char *small) {
+    if (lstm_sgrad_hidden_ok(H)) return FE_OK;
+    return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); %s runs H = 32, 64 and 128", who, (int)H, small);
+}
+
+// Shared by fe_env_rollout_sac_streamed and fe_sac_forward_streamed: the fused form at every count (no split by time step).
+static int launch_sac_streamed(fe_env *env, SacArgs &s, int64_t count, const char *who, void *stream) {
+    const int32_t H = s.l.H;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    if (s.l.forward_only) p.eval_env = -1;
+    const int SP = lstm_geometry(env, p, count, H, true, who);
+    if (SP == 0) return FE_ERR_ARG;
+    const size_t lds = sac_big_lds_bytes(p.EB, p.A, H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        switch (H) {
+        case 256: return (const void *)fe_rollout_sac_big_kernel<single, 4>;
+        case 512: return (const void *)fe_rollout_sac_big_kernel<single, 8>;
+        default: return (const void *)fe_rollout_sac_big_kernel<single, 16>;
+        }
+    });
+    return launch_resident(env, kern, lds, p, &s, "streamed SAC kernel", stream);
+}
+
+int fe_env_rollout_sac_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                                const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd,
+                                int32_t H, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
+                                float *actions_out, float *means_out, float *stds_out, double *rewards_out,
+                                int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    static const char *who = "fe_env_rollout_sac_streamed";
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos ||
+        !rewards_out || !dones_out || K < 1)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
+        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
+    if (int rc = sac_streamed_hidden(H, who, "fe_env_rollout_sac")) return rc;
+    if (int rc = require_bound(env, who)) return rc;
+    SacArgs s;
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H);
+    s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
+    s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
+    s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
+    s.stds_out = stds_out; s.logp_out = nullptr;
+    return launch_sac_streamed(env, s, env->cfg.N, who, stream);
+}
+
+int fe_sac_forward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                            const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd,
+                            int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                            float *actions_out, float *log_probs_out, float *means_out, float *stds_out, void *stream) {
+    static const char *who = "fe_sac_forward_streamed";
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (!noise && (actions_out || log_probs_out))
+        return fail(FE_ERR_ARG, "%s: actions_out and log_probs_out need noise", who);
+    if (int rc = sac_streamed_hidden(H, who, "fe_sac_forward")) return rc;
+    if (count == 0) return FE_OK;
+    SacArgs s;
+    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H);
+    s.l.K = 1;
+    s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
+    s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
+    s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
+    s.stds_out = stds_out; s.logp_out = log_probs_out;
+    return launch_sac_streamed(env, s, count, who, stream);
+}
+
+// Workspace: [W_l^T][split sums of d W_l][head block sums][z][the head's dz], sized by the largest pass, then the workspace
+// of fe_lstm_backward_streamed.
+int64_t fe_sac_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!lstm_sgrad_hidden_ok(H) || W < 1 || count < 0) return -1;
+    return sac_sgrad_extra_floats(H, lstm_sgrad_padded_pairs(H, W, count)) + fe_lstm_streamed_grad_workspace_floats(H, W, count);
+}
+
+int fe_sac_backward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                             const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd,
+                             int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                             const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                             float *workspace, const fe_sac_grads *grads, void *stream) {
+    static const char *who = "fe_sac_backward_streamed";
+    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos ||
+        count < 0 || !noise || !actions || !stds || (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih ||
+        !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu ||
+        !grads->w_std || !grads->b_std)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = sac_streamed_hidden(H, who, "fe_sac_backward")) return rc;
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused actor gradient runs A = 1 only (its consumer, the "
+                    "fused twin critic, does)", who, (int)env->p.A);
+    if (count == 0) return FE_OK;
+    const size_t lds = lstm_sgrad_forward_lds_bytes(H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
+    hipStream_t st = (hipStream_t)stream;
+    SacSGradArgs a;
+    memset(&a, 0, sizeof(a));
+    LstmSGradArgs &g = a.g;
+    g.lr32 = logret_f32; g.whh = whh; g.wx = wx; g.W = W;
+    a.wl = wl; a.bl = bl; a.wmu = wmu; a.wstd = wstd; a.bstd = bstd;
+    a.wlt = workspace;
+    a.lpart = a.wlt + (int64_t)H * H;
+    a.hpart2 = a.lpart + sac_sgrad_wl_splits(H, pp) * (int64_t)H * H;
+    a.z = a.hpart2 + lstm_sgrad_head_blocks(pp) * sac_sgrad_hpart_floats(H);
+    a.dzh = a.z + pp * H;
+    sgrad_carve(g, a.dzh + pp * H, H, pp);
+    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_mu;
+    g.g_bout = grads->b_mu;
+    a.g_wl = grads->w_l; a.g_bl = grads->b_l; a.g_wstd = grads->w_std; a.g_bstd = grads->b_std;
+    hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
+    hipLaunchKernelGGL(fe_sac_sgrad_pack_kernel, dim3(grid_for((int64_t)H * H)), dim3(kBlock), 0, st, a, H);
+    if (int rc = launched("fe_sac_backward_streamed: weight transposes")) return rc;
+    const void *kern = H == 256 ? (const void *)fe_lstm_sgrad_forward_kernel<4>
+                                : (H == 512 ? (const void *)fe_lstm_sgrad_forward_kernel<8>
+                                            : (const void *)fe_lstm_sgrad_forward_kernel<16>);
+    // the chunks in ascending order (the head's boundaries): the first overwrites the gradients, the later ones add to them
+    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+        sgrad_chunk(g, H, c0, count, chunk);
+        a.wl_splits = sac_sgrad_wl_splits(H, g.pp);
+        g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0;
+        a.noise = noise + c0; a.actions = actions + c0; a.stds = stds + c0;
+        a.d_actions = d_actions ? d_actions + c0 : nullptr; a.d_log_probs = d_log_probs ? d_log_probs + c0 : nullptr;
+        if (int rc = launch_sgrad_forward(env, kern, lds, &g, g.pp / 32,
+                                          "streamed SAC gradient kernel: hipFuncSetAttribute / occupancy query",
+                                          "fe_sac_backward_streamed: recurrence", st))
+            return rc;
+        if (int rc = sgrad_backward_chunk(who, g, H, nullptr, nullptr, st, &a)) return rc;
     }
     return FE_OK;
 }

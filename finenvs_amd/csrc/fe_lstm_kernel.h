@@ -160,118 +160,9 @@ __host__ __device__ inline size_t lstm_big_lds_bytes(int EB, int A, int H) {
 
 template <bool SINGLE, int RTW>
 __global__ __launch_bounds__(kLstmBlock, 2) void fe_rollout_lstm_big_kernel(const Params p, const LstmArgs r) {
-    constexpr int H = 64 * RTW, HP = H + 4, SP = 32;
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int A = SINGLE ? 1 : p.A;
-    const int EB = p.EB;
-    const int S = EB * A;
-    const int W = p.W;
-    const TileLds l = carve_lds(smem, EB, S);
-    size_t off = (size_t)EB * 8 + (size_t)S * 8 + (size_t)S * 8 + (size_t)S * 4 + (size_t)S * 4 + (size_t)EB * 4;
-    off = (off + 7) & ~(size_t)7;
-    int64_t *l_idx = reinterpret_cast<int64_t *>(smem + off);
-    off = (off + (size_t)EB * 8 + 15) & ~(size_t)15;
-    float *s_h = reinterpret_cast<float *>(smem + off);  // [SP][HP]
-    float *s_wout = s_h + (size_t)SP * HP;
-    const int tid = threadIdx.x;
-    const int e = SINGLE ? tid : (int)fdiv((uint32_t)tid, p.div_A);
-    const int a = SINGLE ? 0 : tid - e * A;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int col = lane & 31, half = lane >> 5;
-    const int64_t NA = p.N * A;
-    const int64_t rstride = 4 * (int64_t)A;
-    const int mt0 = wave * RTW;  // this wavefront's row tiles: mt0 .. mt0 + RTW - 1
-    float4 wq[kLstmBigAhead][kLstmBigRI];  // weight fragments in flight (fe_lstm_stream_tile.h)
-    bool primed = false;
-    constexpr bool STASH = false;  // nothing goes to a workspace: the rows fe_lstm_stream_tile.h would write are null
-    float *const grow = nullptr, *const crow = nullptr, *const hout = nullptr;
-    for (int i = tid; i < H; i += kLstmBlock) s_wout[i] = r.wout[i];
-
-    for (int64_t tile = blockIdx.x; tile < p.num_tiles; tile += gridDim.x) {
-        const int64_t n0 = tile * EB;
-        const int ebt = (p.N - n0) < (int64_t)EB ? (int)(p.N - n0) : EB;
-        const bool active = e < ebt;
-        const int64_t n = n0 + e;
-        const int64_t sl = n * A + a;
-        SleeveReg st = rollout_load_state(p, active && !r.forward_only, n, sl);
-        if (active) {
-            const double pos0 = r.obs_pos[sl];
-            l.pos[e * A + a] = pos0;
-            if (a == 0) l.src[e] = r.obs_src[n];
-            if (r.traj_src) {
-                r.traj_pos[sl] = pos0;
-                if (a == 0) r.traj_src[n] = r.obs_src[n];
-            }
-        }
-        __syncthreads();  // also covers s_wout on the first tile
-        const int pairs = ebt * A;
-        for (int k = 0; k < r.K; ++k) {
-            const int qc = col < pairs ? col : pairs - 1;
-            const int ee = SINGLE ? qc : (int)fdiv((uint32_t)qc, p.div_A);
-            const int aa = SINGLE ? 0 : qc - ee * A;
-            const float *xsrc = r.lr32 + l.src[ee] + 4 * aa;
-            const float4 xh = make_float4((float)l.pos[qc], 1.0f, 0.0f, 0.0f);
-            float4 xc = half == 0 ? *reinterpret_cast<const float4 *>(xsrc) : xh;
-            float cst[RTW][4], hnew[RTW][4];
-#pragma unroll
-            for (int i = 0; i < RTW; ++i)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) cst[i][b] = 0.0f;
-            for (int t = 0; t < W; ++t) {
-                const int tn = t + 1 < W ? t + 1 : t;
-                const float4 xn = half == 0 ? *reinterpret_cast<const float4 *>(xsrc + (int64_t)tn * rstride) : xh;
-                const float *hrow = s_h + (size_t)col * HP + 4 * half;
-                // a real loop over this wavefront's row-tile groups: c_t and the pending h_t (RTW x 4 floats each per lane,
-                // touched once per 1040 MFMAs) are indexed dynamically, i.e. live in per-lane scratch, not in VGPRs
-#define FE_LSTM_STREAM_ARGS r
-#pragma unroll 1
-                for (int i0 = 0; i0 < RTW; i0 += kLstmBigRI) {
-#include "fe_lstm_stream_tile.h"
-                }
-#undef FE_LSTM_STREAM_ARGS
-                lds_barrier();  // every wavefront has read h_{t-1}
-#pragma unroll
-                for (int i = 0; i < RTW; ++i)
-                    *reinterpret_cast<float4 *>(s_h + (size_t)col * HP + 8 * (mt0 + i) + 4 * half) =
-                        make_float4(hnew[i][0], hnew[i][1], hnew[i][2], hnew[i][3]);
-                xc = xn;
-                lds_barrier();  // h_t is complete
-            }
-            // ---- output layer: the pair's accounting lane reduces its last hidden state ----
-            float act = 0.0f;
-            if (active) {
-                const float *hl = s_h + (size_t)(e * A + a) * HP;
-                float o = r.bout_p ? *r.bout_p : r.bout;
-#pragma unroll 8
-                for (int u = 0; u < H; ++u) o = fmaf(s_wout[u], hl[u], o);
-                act = r.out_act == 0 ? lstm_tanh(o) : (r.out_act == 2 ? o : (o < -1.0f ? -1.0f : (o > 1.0f ? 1.0f : o)));
-                if (r.means_out) r.means_out[(int64_t)k * NA + sl] = act;
-                if (r.noise && n != p.eval_env) {
-                    const float dev = r.std * r.noise[(int64_t)k * NA + sl];
-                    const float smp = act + dev;
-                    act = smp < -1.0f ? -1.0f : (smp > 1.0f ? 1.0f : smp);
-                }
-                if (r.actions_out) r.actions_out[(int64_t)k * NA + sl] = act;
-            }
-            if (!r.forward_only) {  // (uniform)
-                account_keep<SINGLE>(p, l, l_idx, A, e, a, active, n, st, act, r.rew_out + (int64_t)k * p.N,
-                                     r.done_out + (int64_t)k * p.N);
-                if (active && r.traj_src) {
-                    r.traj_pos[(int64_t)(k + 1) * NA + sl] = l.pos[e * A + a];
-                    if (a == 0) r.traj_src[(int64_t)(k + 1) * p.N + n] = l.src[e];
-                }
-            }
-            lds_barrier();  // the new observation's descriptors are complete; everyone is done with h_W
-        }
-        if (!r.forward_only) {
-            rollout_store_state(p, active, a, n, sl, st);
-            if (active) {
-                r.obs_pos[sl] = l.pos[e * A + a];
-                if (a == 0) r.obs_src[n] = l.src[e];
-            }
-        }
-        __syncthreads();
-    }
+#define FE_LSTM_SAC_HEAD 0
+#include "fe_lstm_big_rollout_body.h"
+#undef FE_LSTM_SAC_HEAD
 }
 
 // ---- large H at SMALL env counts: one launch per time step, the row tiles spread over the whole GPU ----

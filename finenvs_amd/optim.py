@@ -148,7 +148,7 @@ class _Segment:
 
 def network_kind(module: nn.Module) -> Tuple[str, int]:
     """("head" | "critic" | "actor", H) of a module ``FusedAdam.add`` takes: what ``check_head``,
-    ``check_critic`` (both with H up to 1024) or ``check_actor`` accept; ValueError otherwise."""
+    ``check_critic`` or ``check_actor`` (each with H up to 1024) accept; ValueError otherwise."""
     from .critic import check_critic
     from .lstm_head import check_head
     from .sac import check_actor
@@ -158,7 +158,7 @@ def network_kind(module: nn.Module) -> Tuple[str, int]:
         raise ValueError("FusedAdam.add needs a module with an nn.LSTM `lstm` (an LSTM head, a critic or a SAC actor); "
                          "use add_tensor for a plain tensor")
     if hasattr(module, "mu_layer") and hasattr(module, "std_layer"):
-        return "actor", check_actor(module)
+        return "actor", check_actor(module, streamed=True)
     if lstm.input_size == 6:
         return "critic", check_critic(module, streamed=True)
     return "head", check_head(module, streamed=True)[0]

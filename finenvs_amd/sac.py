@@ -14,6 +14,9 @@ with ``mu_layer`` / ``std_layer`` of one output per pair (``A = 1``).  Its ``for
 runs on descriptors too: ``sample`` is ``forward``'s (actions, log_probs) as a differentiable function of the actor's
 ten parameters (C ABI ``fe_sac_backward``, include/finenvs_amd_sac_grad.h), and ``actor_losses`` the actor's and the
 temperature's losses of ``Actor.compute_losses`` (SAC/actor.py:63-81) on replayed transitions.
+
+H in {32, 64, 128}; with ``streamed=True`` also H in {256, 512, 1024}, the reference's own ``hidden_dim``: the same
+methods on the entries of include/finenvs_amd_sac_streamed.h, whose recurrent and last-layer weights stream from L2.
 """
 from __future__ import annotations
 
@@ -27,9 +30,10 @@ import torch.nn.functional as F
 from torch.distributions import Normal
 
 from . import _lib
-from .rollout import _FusedEvaluation, lstm_pack
+from .rollout import _FusedEvaluation, lstm_fragment_major, lstm_pack
 
 SAC_HIDDEN_SIZES = (32, 64, 128)
+SAC_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
 
 
 class SACActorLSTM(nn.Module):
@@ -90,14 +94,19 @@ def pair_states(states: torch.Tensor, A: int) -> torch.Tensor:
     return states.reshape(B, W, A, 5).permute(0, 2, 1, 3).reshape(B * A, W, 5)
 
 
-def check_actor(actor: nn.Module) -> int:
-    """The hidden size of an actor the fused SAC head can run; ValueError otherwise."""
+def check_actor(actor: nn.Module, streamed: bool = False) -> int:
+    """The hidden size of an actor the fused SAC head can run; ValueError otherwise.  ``streamed``: H may also be 256,
+    512 or 1024 (the streamed kernels of include/finenvs_amd_sac_streamed.h)."""
     lstm = actor.lstm
     if lstm.num_layers != 1 or lstm.bidirectional or lstm.input_size != 5 or not lstm.batch_first or lstm.proj_size:
         raise ValueError("the fused SAC head needs nn.LSTM(5, H, num_layers=1, batch_first=True)")
     H = int(lstm.hidden_size)
-    if H not in SAC_HIDDEN_SIZES:
-        raise ValueError(f"the fused SAC head supports H in {SAC_HIDDEN_SIZES} (got {H})")
+    if streamed and H not in SAC_HIDDEN_SIZES + SAC_STREAMED_HIDDEN_SIZES:
+        raise ValueError(f"the fused SAC head supports H in {SAC_HIDDEN_SIZES + SAC_STREAMED_HIDDEN_SIZES} (got {H})")
+    if not streamed and H not in SAC_HIDDEN_SIZES:
+        raise ValueError(f"the fused SAC head supports H in {SAC_HIDDEN_SIZES} (got {H})"
+                         + ("; pass streamed=True for the streamed kernels of H in "
+                            f"{SAC_STREAMED_HIDDEN_SIZES}" if H in SAC_STREAMED_HIDDEN_SIZES else ""))
     last = actor.last_layer[0]
     if last.in_features != H or last.out_features != H:
         raise ValueError(f"last_layer must be Linear({H}, {H})")
@@ -111,10 +120,13 @@ def check_actor(actor: nn.Module) -> int:
 def pack_sac_weights(actor: nn.Module) -> Dict[str, torch.Tensor]:
     """The actor's current parameters as fe_env_rollout_sac reads them (f32, on the parameters' device, no host sync):
     whh / wx as ``lstm_pack``, ``wl`` the last layer fragment-major ([row tile][k group][lane = r + 32 h][4] =
-    W_l[32 t + r][8 g + 4 h + m]), ``bl``, ``wmu``, ``wstd`` (H), ``bmu`` / ``bstd`` (1)."""
-    H = check_actor(actor)
+    W_l[32 t + r][8 g + 4 h + m]), ``bl``, ``wmu``, ``wstd`` (H), ``bmu`` / ``bstd`` (1).  At H > 128 ``whh`` is
+    fragment-major (``lstm_fragment_major``), as the streamed kernels read it."""
+    H = check_actor(actor, streamed=True)
     lstm = actor.lstm
     whh, wx = lstm_pack(lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, H)
+    if H > 128:
+        whh = lstm_fragment_major(whh, H)
     last = actor.last_layer[0]
     wl = last.weight.detach().float().reshape(H // 32, 32, H // 8, 2, 4).permute(0, 2, 3, 1, 4).contiguous().reshape(H, H)
     return {
@@ -147,7 +159,8 @@ def actor_parameters(actor: nn.Module) -> Tuple[torch.Tensor, ...]:
 
 class _SacSample(torch.autograd.Function):
     """(actions, log_probs) of ``FusedSACRollout.forward`` as a differentiable function of the actor's ten parameters:
-    the forward is ``fe_sac_forward``, the backward ``fe_sac_backward`` (the same activations, recomputed)."""
+    the forward is ``fe_sac_forward``, the backward ``fe_sac_backward`` (the same activations, recomputed); at H > 128
+    their ``_streamed`` namesakes (include/finenvs_amd_sac_streamed.h)."""
 
     @staticmethod
     def forward(ctx, roll, src, pos, noise, *params):
@@ -175,14 +188,17 @@ class _SacSample(torch.autograd.Function):
         grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in SAC_GRAD_KEYS]
         if B:
             g_a, g_lp = (None if g is None else g.reshape(B).float().contiguous() for g in (g_a, g_lp))
-            ws = torch.empty((int(env._lib.fe_sac_grad_workspace_floats(H, int(env.num_intervals), B)),),
-                             dtype=torch.float32, device=dev)
+            floats = env._lib.fe_sac_streamed_grad_workspace_floats if roll.streamed else env._lib.fe_sac_grad_workspace_floats
+            ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
             w, (bmu, bstd) = ctx.packed, ctx.biases  # the biases: two floats, or two device addresses (weights=)
             if roll.weights is not None:
                 roll.weights.check_version(ctx.version)
             sg = _lib.FeSacGrads(*(g.data_ptr() for g in grads))
             ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            backward = env._lib.fe_sac_backward_p if roll.weights is not None else env._lib.fe_sac_backward
+            if roll.streamed:
+                backward = env._lib.fe_sac_backward_streamed
+            else:
+                backward = env._lib.fe_sac_backward_p if roll.weights is not None else env._lib.fe_sac_backward
             _lib.check(backward(
                 env._handle, roll._lr32.data_ptr(), w["whh"].data_ptr(), w["wx"].data_ptr(), w["wl"].data_ptr(),
                 w["bl"].data_ptr(), w["wmu"].data_ptr(), bmu, w["wstd"].data_ptr(), bstd, H, src.data_ptr(),
@@ -207,10 +223,20 @@ class FusedSACRollout(_FusedEvaluation):
     ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that ``actor`` is registered with.  ``run``, ``forward`` and
     ``sample`` then read that optimizer's packed buffers and the two output biases on the device: nothing is packed
     per call and nothing is copied to the host.  Those buffers are rewritten in place: a ``weights.step()`` or
-    ``weights.repack()`` between ``sample`` and its ``backward()`` is a RuntimeError."""
+    ``weights.repack()`` between ``sample`` and its ``backward()`` is a RuntimeError.
 
-    def __init__(self, env, actor: nn.Module, weights=None):
-        self.H = check_actor(actor)
+    ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent and last-layer weights stream from L2
+    (C ABI ``fe_env_rollout_sac_streamed`` / ``fe_sac_forward_streamed`` / ``fe_sac_backward_streamed``,
+    include/finenvs_amd_sac_streamed.h), with the same methods and semantics.  There the two output biases are always
+    read on the device (nothing is copied to the host, with or without ``weights=``), the backward is several launches
+    per LSTM time step and its workspace grows with the batch up to ``fe_lstm_streamed_grad_chunk_pairs`` pairs, and
+    ``run`` is the fused kernel at every env count: the split-by-time-step form of ``fe_env_rollout_lstm_split`` is not
+    extended to SAC, so below a few thousand pairs one CU walks the whole matrix.  The small sizes go the
+    register-resident way whether or not ``streamed`` is passed."""
+
+    def __init__(self, env, actor: nn.Module, weights=None, streamed: bool = False):
+        self.H = check_actor(actor, streamed)
+        self.streamed = self.H > 128  # which entries run: a function of H alone
         self.weights = weights
         if weights is not None:
             weights.packed(actor)  # ValueError if the actor is not registered with it
@@ -235,7 +261,7 @@ class FusedSACRollout(_FusedEvaluation):
         w = self.weights.packed(self.actor) if self.weights is not None else pack_sac_weights(self.actor)
         if w["whh"].device != torch.device(self.env._dev):
             raise ValueError(f"the actor's parameters must live on the env's device {self.env._dev}")
-        if self.weights is not None:
+        if self.weights is not None or self.streamed:  # the biases are read on the device
             bmu, bstd = w["bmu"].data_ptr(), w["bstd"].data_ptr()
         else:
             # the two output biases are kernel arguments: one small copy to the host, ordered after any pending update
@@ -289,7 +315,10 @@ class FusedSACRollout(_FusedEvaluation):
         self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
         self.stds = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_stds else None
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        rollout = env._lib.fe_env_rollout_sac_p if self.weights is not None else env._lib.fe_env_rollout_sac
+        if self.streamed:
+            rollout = env._lib.fe_env_rollout_sac_streamed
+        else:
+            rollout = env._lib.fe_env_rollout_sac_p if self.weights is not None else env._lib.fe_env_rollout_sac
         _lib.check(rollout(
             env._handle, *w, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(), ptr(noise), actions.data_ptr(),
             ptr(self.means), ptr(self.stds), rewards.data_ptr(), dones.data_ptr(), ptr(src_out), ptr(pos_out),
@@ -317,7 +346,10 @@ class FusedSACRollout(_FusedEvaluation):
         if B:
             self._check_epoch()
             ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-            forward = env._lib.fe_sac_forward_p if self.weights is not None else env._lib.fe_sac_forward
+            if self.streamed:
+                forward = env._lib.fe_sac_forward_streamed
+            else:
+                forward = env._lib.fe_sac_forward_p if self.weights is not None else env._lib.fe_sac_forward
             _lib.check(forward(
                 env._handle, *self._weights(), src.data_ptr(), pos.data_ptr(), B, ptr(noise), ptr(actions),
                 ptr(log_probs), means.data_ptr(), stds.data_ptr(), env._stream()))
