@@ -281,6 +281,33 @@ PPO_SIGNATURES = {
     "fe_ppo_value_loss": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
+
+# include/finenvs_amd_mlp_head.h: the MLP head trained on descriptors (finenvs_amd/mlp_head.py, FusedMLPRollout)
+MLP_GRAD_CHUNK_PAIRS = 512  # FE_MLP_GRAD_CHUNK_PAIRS
+
+
+class FeMlpWeights(C.Structure):
+    """struct fe_mlp_weights of include/finenvs_amd_mlp_head.h."""
+
+    _fields_ = [("w1t", _vp), ("wpos", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
+
+
+class FeMlpGrads(C.Structure):
+    """struct fe_mlp_grads of include/finenvs_amd_mlp_head.h."""
+
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp)]
+
+
+_mw = C.POINTER(FeMlpWeights)
+MLP_HEAD_SIGNATURES = {
+    "fe_mlp_pack": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "fe_env_rollout_mlp_sampled": (C.c_int, [_vp, _vp, _mw, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp,
+                                             _vp, _vp, _vp, _vp]),
+    "fe_mlp_forward": (C.c_int, [_vp, _vp, _mw, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "fe_mlp_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_mlp_backward": (C.c_int, [_vp, _vp, _mw, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(FeMlpGrads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -309,7 +336,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
-                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES}.items():
+                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

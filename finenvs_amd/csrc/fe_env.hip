@@ -31,6 +31,7 @@
 //   fe_step_kernel.h      fe_env_kernel (the fused step and reset() rendering)
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
+//   fe_mlp_head_kernels.h  the MLP head's training entries: device packing, sampled rollout, value on descriptors, backward
 //   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA), and with the SAC actor's head
 //   fe_lstm_rollout_body.h  the register-resident rollout's body, included by both of those kernels
 //   fe_lstm_stream_tile.h   one row-tile group of the streamed recurrence at H = 256 / 512 / 1024, included by the large-H
@@ -83,11 +84,13 @@
 #include "finenvs_amd_optim.h"
 #include "finenvs_amd_replay_cursor.h"
 #include "finenvs_amd_ppo.h"
+#include "finenvs_amd_mlp_head.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
 #include "fe_step_kernel.h"
 #include "fe_rollout_kernels.h"
+#include "fe_mlp_head_kernels.h"
 #include "fe_lstm_kernel.h"
 #include "fe_aux_kernels.h"
 #include "fe_evo_kernels.h"
@@ -858,6 +861,161 @@ int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, c
     if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "fe_env_rollout_mlp: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", (int)H, 4 * p.W, lds);
     return launch_big_lds(env->device, kern, grid, lds, p, r, stream, "fe_env_rollout_mlp");
+}
+
+// ---- include/finenvs_amd_mlp_head.h: the MLP head trained on descriptors ----
+// The checks every entry shares; `who` names it.  W1^T must fit the LDS next to the rollout's default tile, whichever
+// kernel runs: one rule for acting, values and gradients.
+static int mlp_head_checked(const fe_env *env, const float *logret_f32, const fe_mlp_weights *w, int32_t H, int32_t activation,
+                            int32_t out_activation, const char *who) {
+    if (!env || !logret_f32 || !w || !w->w1t || !w->wpos || !w->b1 || !w->w2 || !w->b2)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
+    if (out_activation < 0 || out_activation > 2)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh), 1 (clamp) or 2 (none)", who);
+    return FE_OK;
+}
+
+static int mlp_head_fits(const fe_env *env, int32_t H, const char *who) {
+    const Params &p = env->p;
+    const size_t lds = mlp_lds_bytes(128 / p.A > 1 ? 128 / p.A : 1, p.A, p.W, H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", who, (int)H, 4 * p.W, lds);
+    return FE_OK;
+}
+
+int fe_mlp_pack(const float *weight1, int32_t H, int32_t W, float *w1t, float *wpos, void *stream) {
+    if (!weight1 || !w1t || !wpos) return fail(FE_ERR_ARG, "fe_mlp_pack: bad argument");
+    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "fe_mlp_pack: H must be 32, 64 or 128 (got %d)", (int)H);
+    if (W < 1) return fail(FE_ERR_ARG, "fe_mlp_pack: W must be >= 1 (got %d)", (int)W);
+    DeviceGuard guard(device_of(weight1));
+    if (int rc = guard.status()) return rc;
+    hipLaunchKernelGGL(fe_mlp_pack_kernel, dim3(grid_for((int64_t)H * 4 * W + H)), dim3(kBlock), 0, (hipStream_t)stream, weight1,
+                       (int)H, (int)W, w1t, wpos);
+    return launched("fe_mlp_pack");
+}
+
+int fe_env_rollout_mlp_sampled(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H,
+                               int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                               const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                               int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    static const char *who = "fe_env_rollout_mlp_sampled";
+    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
+        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
+    if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "%s: std must be >= 0 when noise is given", who);
+    if (!obs_src || !obs_pos || !rewards_out || !dones_out || K < 1) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (int rc = require_bound(env, who)) return rc;
+    if (int rc = mlp_head_fits(env, H, who)) return rc;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    MlpHeadArgs r;
+    memset(&r, 0, sizeof(r));
+    r.lr32 = logret_f32; r.w1t = weights->w1t; r.wpos = weights->wpos; r.b1 = weights->b1; r.w2 = weights->w2; r.b2 = weights->b2;
+    r.H = H; r.act = activation; r.out_act = out_activation; r.K = K; r.obs_src = obs_src; r.obs_pos = obs_pos;
+    r.noise = noise; r.std = std; r.actions_out = actions_out; r.means_out = means_out; r.rew_out = rewards_out;
+    r.done_out = dones_out; r.traj_src = states_src_out; r.traj_pos = states_pos_out;
+    // the geometry of fe_env_rollout_mlp: 128 pairs per workgroup, one 32-pair column block per wavefront
+    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
+    const size_t lds = mlp_lds_bytes(p.EB, p.A, p.W, H);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_rollout_mlp_sampled_kernel<single, 1>
+                       : (H == 64 ? (const void *)fe_rollout_mlp_sampled_kernel<single, 2>
+                                  : (const void *)fe_rollout_mlp_sampled_kernel<single, 4>);
+    });
+    if (lds > kMaxLds)  // (a tile override larger than the default)
+        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", who, (int)H, 4 * p.W, lds);
+    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+}
+
+int fe_mlp_forward(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H, int32_t activation,
+                   int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
+                   void *stream) {
+    static const char *who = "fe_mlp_forward";
+    if (!obs_src || !obs_pos || !out || count < 0) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (int rc = mlp_head_fits(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    MlpHeadArgs r;
+    memset(&r, 0, sizeof(r));
+    r.lr32 = logret_f32; r.w1t = weights->w1t; r.wpos = weights->wpos; r.b1 = weights->b1; r.w2 = weights->w2; r.b2 = weights->b2;
+    r.H = H; r.act = activation; r.out_act = out_activation; r.K = 1;
+    r.obs_src = const_cast<int64_t *>(obs_src); r.obs_pos = const_cast<double *>(obs_pos);  // read only in this kernel
+    r.actions_out = out; r.count = count;
+    const int64_t blocks = (count * p.A + 31) / 32;
+    const int64_t grid = capped_grid((blocks + kBlock / 64 - 1) / (kBlock / 64));
+    const size_t lds = mlp_head_weight_lds_bytes(p.W, H);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_mlp_forward_kernel<single, 1>
+                       : (H == 64 ? (const void *)fe_mlp_forward_kernel<single, 2> : (const void *)fe_mlp_forward_kernel<single, 4>);
+    });
+    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+}
+
+// Workspace: [dpre (32 blocks, H)][partial products (splits, H, F)][d w2 / d b2 partials (waves, H + 4)].
+int64_t fe_mlp_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
+    if (count == 0) return 0;
+    const int64_t blocks = (count + 31) / 32, splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
+    return 32 * blocks * H + splits * H * mlp_grad_fp(W) + 4 * mlp_grad_groups(blocks) * (H + 4);
+}
+
+int fe_mlp_backward(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H, int32_t activation,
+                    int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                    const float *outputs, const float *d_outputs, float *workspace, const fe_mlp_grads *grads,
+                    void *stream) {
+    static const char *who = "fe_mlp_backward";
+    if (!obs_src || !obs_pos || count < 0 || !d_outputs || !workspace || !grads || !grads->w1 || !grads->b1 || !grads->w2 ||
+        !grads->b2)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (out_activation == 1)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on", who);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_mlp_forward returned", who);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused LSTM "
+                    "head does)", who, (int)env->p.A);
+    if (int rc = mlp_head_fits(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    MlpGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.w1t = weights->w1t; g.wpos = weights->wpos; g.b1 = weights->b1; g.w2 = weights->w2;
+    g.obs_src = obs_src; g.obs_pos = obs_pos; g.outputs = outputs; g.d_outputs = d_outputs;
+    g.count = count; g.blocks = (count + 31) / 32; g.splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
+    const int64_t groups = mlp_grad_groups(g.blocks);
+    g.waves = 4 * groups;
+    g.W = W; g.H = H; g.act = activation; g.out_act = out_activation; g.FP = mlp_grad_fp(W);
+    g.dpre = workspace;
+    g.part = g.dpre + 32 * g.blocks * H;
+    g.wpart = g.part + g.splits * H * g.FP;
+    g.g_w1 = grads->w1; g.g_b1 = grads->b1; g.g_w2 = grads->w2; g.g_b2 = grads->b2;
+    void *args[] = {&g};
+    const hipStream_t st = (hipStream_t)stream;
+    const void *k1 = H == 32 ? (const void *)fe_mlp_grad_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp_grad_kernel<2> : (const void *)fe_mlp_grad_kernel<4>);
+    const size_t lds = mlp_head_weight_lds_bytes(W, H);
+    if (int rc = prepare_big_lds(env->device, k1, lds, who)) return rc;
+    if (int rc = launched("fe_mlp_backward: first layer", hipLaunchKernel(k1, dim3((unsigned)groups), dim3(kBlock), args, lds, st)))
+        return rc;
+    const void *k2 = H == 32 ? (const void *)fe_mlp_wgrad_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp_wgrad_kernel<2> : (const void *)fe_mlp_wgrad_kernel<4>);
+    const int64_t items = g.splits * (g.FP / 32);
+    const int64_t grid2 = capped_grid((items + kBlock / 64 - 1) / (kBlock / 64));
+    if (int rc = launched("fe_mlp_backward: weight gradient", hipLaunchKernel(k2, dim3((unsigned)grid2), dim3(kBlock), args, 0, st)))
+        return rc;
+    hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)H * (4 * W + 2) + H + 1)), dim3(kBlock), 0, st, g);
+    return launched("fe_mlp_backward: reduction");
 }
 
 // Tile geometry of the fused LSTM kernels (LSTM and SAC heads) for `count` envs (rollout) or descriptors (forward): sets

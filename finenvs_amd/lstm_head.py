@@ -18,7 +18,7 @@ include/finenvs_amd_lstm_grad_streamed.h).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import TYPE_CHECKING, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -26,6 +26,9 @@ from torch.distributions import Normal
 
 from . import _lib
 from .rollout import FusedLSTMRollout, lstm_fragment_major, lstm_pack
+
+if TYPE_CHECKING:
+    from .mlp_head import FusedMLPHead
 
 LSTM_HEAD_HIDDEN_SIZES = (32, 64, 128)
 LSTM_HEAD_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
@@ -351,12 +354,14 @@ def fused_ppo_critic_loss(values: torch.Tensor, returns: torch.Tensor, workspace
     return _FusedValueLoss.apply(values, returns, workspace)
 
 
-def ppo_actor_loss(head: FusedLSTMHead, log_std: torch.Tensor, src: torch.Tensor, pos: torch.Tensor, actions: torch.Tensor,
+def ppo_actor_loss(head: "Union[FusedLSTMHead, FusedMLPHead]", log_std: torch.Tensor, src: torch.Tensor, pos: torch.Tensor, actions: torch.Tensor,
                    old_log_probs: torch.Tensor, advantages: torch.Tensor, clip_epsilon: float = 0.2,
                    entropy_coefficient: float = 0.01, fused: bool = False, workspace: torch.Tensor = None) -> torch.Tensor:
     """``compute_actor_loss`` (PPO/continuous_actor.py:59-78) on B state descriptors, nothing rendered: the clipped
     surrogate of ``Normal(head(src, pos), exp(log_std))`` plus the entropy bonus, negated.  ``actions``,
-    ``old_log_probs``, ``advantages``: B elements each.  ``log_std`` gets its gradient from autograd.
+    ``old_log_probs``, ``advantages``: B elements each.  ``log_std`` gets its gradient from autograd.  ``head``: a
+    ``FusedLSTMHead`` or a ``FusedMLPHead`` (finenvs_amd/mlp_head.py) -- anything that maps ``(src, pos)`` to a
+    differentiable (B, 1) float32 output.
 
     ``fused=True``: the loss and its gradients from one launch (``fused_ppo_actor_loss``) instead of some thirty
     element-wise ones; ``backward()`` accumulates into ``log_std.grad`` and the head's ``.grad`` as before.
@@ -368,11 +373,11 @@ def ppo_actor_loss(head: FusedLSTMHead, log_std: torch.Tensor, src: torch.Tensor
     return torch_ppo_actor_loss(head(src, pos), log_std, *cols, clip_epsilon, entropy_coefficient)
 
 
-def ppo_critic_loss(head: FusedLSTMHead, src: torch.Tensor, pos: torch.Tensor, returns: torch.Tensor, fused: bool = False,
+def ppo_critic_loss(head: "Union[FusedLSTMHead, FusedMLPHead]", src: torch.Tensor, pos: torch.Tensor, returns: torch.Tensor, fused: bool = False,
                     workspace: torch.Tensor = None) -> torch.Tensor:
     """``compute_critic_loss`` (PPO/critic.py:26-32) on B state descriptors: the mean squared error of
-    ``head(src, pos)`` against ``returns`` (B elements).  ``fused=True``: loss and gradient from one launch
-    (``fused_ppo_critic_loss``)."""
+    ``head(src, pos)`` against ``returns`` (B elements); ``head``: a ``FusedLSTMHead`` or a ``FusedMLPHead``
+    (finenvs_amd/mlp_head.py).  ``fused=True``: loss and gradient from one launch (``fused_ppo_critic_loss``)."""
     ret = _column(returns, int(src.numel()), "returns")
     if fused:
         return fused_ppo_critic_loss(head(src, pos), ret, workspace)

@@ -12,6 +12,7 @@ observation a replay ends on is the buffer the next replay starts from.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Callable, List, Optional
 
 import torch
@@ -387,8 +388,12 @@ class FusedMLPRollout(_FusedEvaluation):
     ``H`` in {32, 64, 128}."""
 
     ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2}
+    OUTPUT_ACTIVATIONS = {"tanh": 0, "clamp": 1, "none": 2}  # "none": a critic (forward() only; an action needs bounds)
 
-    def __init__(self, env, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: float = 0.0, activation: str = "elu"):
+    def __init__(self, env, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: float = 0.0, activation: str = "elu",
+                 output_activation: str = "clamp"):
+        """``output_activation``: ``"clamp"`` (the default: clamp(p, -1, 1)), ``"tanh"`` (the reference's MLP actor,
+        PPO/continuous_actor.py:81-101) or ``"none"`` (its critic, PPO/critic.py:35-50)."""
         W = env.num_intervals
         if W1.dim() != 2 or W1.shape[0] != 5 * W:
             raise ValueError(f"W1 must be ({5 * W}, H): one row per flattened observation element")
@@ -397,9 +402,13 @@ class FusedMLPRollout(_FusedEvaluation):
             raise ValueError("H must be 32, 64 or 128")
         if activation not in self.ACTIVATIONS:
             raise ValueError(f"activation must be one of {sorted(self.ACTIVATIONS)}")
+        if output_activation not in self.OUTPUT_ACTIVATIONS:
+            raise ValueError(f"output_activation must be one of {sorted(self.OUTPUT_ACTIVATIONS)}")
         if env.redraw != "device" and not env.evaluate:
             raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
         self.env, self.H, self.act = env, H, self.ACTIVATIONS[activation]
+        self.out_act = self.OUTPUT_ACTIVATIONS[output_activation]
+        self.means = None
         dev = env._dev
         self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
@@ -421,22 +430,99 @@ class FusedMLPRollout(_FusedEvaluation):
         self.b1 = b1.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
         self.w2 = W2.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
         self.b2 = float(b2)
+        # the output bias where the training entries read it (include/finenvs_amd_mlp_head.h); made on first use
+        self.b2_dev = None
 
-    def run(self, num_steps: int, record_actions: bool = True):
-        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32)."""
+    def _weights(self):
+        """``fe_mlp_weights`` of the packed buffers.  ``b2_dev`` is the host's ``b2`` copied once, or a ``FusedMLPHead``'s
+        own (then ``b2`` is None: nothing of that head's weights lives on the host)."""
+        from . import _lib
+
+        if self.b2_dev is None:
+            self.b2_dev = torch.tensor([self.b2], dtype=torch.float32).to(self.env._dev)
+        return _lib.FeMlpWeights(self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
+                                 self.b2_dev.data_ptr())
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The head evaluated on ANY B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` float64 --
+        rows of a ``TrajectoryBuffer(states=True)``, gathered ones included) without stepping the env and without
+        materialising the observations: ``(B, A)`` float32 (C ABI ``fe_mlp_forward``).  With
+        ``output_activation="none"`` this is the critic of the reference's ``PPOAgentMLP``: the values of all K + 1
+        states of a chunk in one launch."""
+        from . import _lib
+
+        env, A = self.env, self.env.num_assets
+        B = int(obs_src.numel())
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
+        if out is None:
+            out = torch.empty((B, A), dtype=torch.float32, device=env._dev)
+        elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
+            raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
+        if B:
+            w = self._weights()
+            _lib.check(env._lib.fe_mlp_forward(env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act,
+                                               src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), env._stream()))
+        return out
+
+    def run(self, num_steps: int, record_actions: bool = True, noise: Optional[torch.Tensor] = None,
+            std: Optional[float] = None, record_means: bool = False, trajectory=None):
+        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32).
+
+        Training rollouts (``agent.step`` of finenvs/agents/PPO/PPO_agent.py:98-108), as ``FusedLSTMRollout.run``:
+        pass ``noise`` -- (K, N, A) f32 standard-normal draws from the caller's generator -- and ``std =
+        exp(log_standard_deviation)``; the action is ``clamp(mean + std * noise, -1, 1)``, the eval env of a
+        training-mode env acts on the mean (an evaluate-mode env has none: every env samples).  ``record_means`` keeps
+        the means in ``self.means`` ((K, N, A), what ``log_prob`` needs).  ``trajectory``: an empty
+        ``TrajectoryBuffer(K, N, A, states=True)`` without capacity padding -- the kernel writes actions, rewards, dones
+        and the K + 1 state descriptors straight into its chunk; the returned tensors are then views of it.
+
+        A plain ``run(K)`` of a rollout with the default clamp output is ``fe_env_rollout_mlp``; everything else is
+        ``fe_env_rollout_mlp_sampled`` (include/finenvs_amd_mlp_head.h)."""
         from . import _lib
 
         env, K = self.env, int(num_steps)
         N, A = env.num_envs, env.num_assets
-        actions = torch.empty((K, N, A), dtype=torch.float32, device=env._dev) if record_actions else None
-        rewards = torch.empty((K, N), dtype=torch.float64, device=env._dev)
-        dones = torch.empty((K, N), dtype=torch.int32, device=env._dev)
+        dev = env._dev
+        src_out = pos_out = None
+        if trajectory is not None:
+            tr = trajectory
+            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
+                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
+                                 "without capacity padding")
+            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
+            src_out, pos_out = tr.obs_src, tr.obs_pos
+        else:
+            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
+            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
+            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
+        if noise is not None:
+            if std is None or not float(std) >= 0.0:
+                raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
+            if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
+                raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
+            noise = noise.contiguous()
         self._begin_run()
-        _lib.check(env._lib.fe_env_rollout_mlp(
-            env._handle, self._lr32.data_ptr(), self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(),
-            self.w2.data_ptr(), self.b2, self.H, self.act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
-            actions.data_ptr() if record_actions else None, rewards.data_ptr(), dones.data_ptr(), env._stream()))
+        plain = (self.out_act == 1 and noise is None and not record_means and trajectory is None and self.b2 is not None)
+        if plain:
+            self.means = None
+            _lib.check(env._lib.fe_env_rollout_mlp(
+                env._handle, self._lr32.data_ptr(), self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(),
+                self.w2.data_ptr(), self.b2, self.H, self.act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
+                actions.data_ptr() if record_actions else None, rewards.data_ptr(), dones.data_ptr(), env._stream()))
+        else:
+            self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
+            w = self._weights()
+            _lib.check(env._lib.fe_env_rollout_mlp_sampled(
+                env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, K, self.obs_src.data_ptr(),
+                self.obs_pos.data_ptr(), noise.data_ptr() if noise is not None else None,
+                float(std) if noise is not None else 0.0, actions.data_ptr() if actions is not None else None,
+                self.means.data_ptr() if record_means else None, rewards.data_ptr(), dones.data_ptr(),
+                src_out.data_ptr() if src_out is not None else None, pos_out.data_ptr() if pos_out is not None else None,
+                env._stream()))
         self._end_run()
+        if trajectory is not None:
+            trajectory.mark_filled(K)
         return actions, rewards, dones
 
 

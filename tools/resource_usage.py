@@ -11,6 +11,7 @@ table (no scratch in the step / render kernels).
 """
 from __future__ import annotations
 
+import functools
 import os
 import re
 import subprocess
@@ -33,7 +34,13 @@ def demangle(names):
 
 
 def kernel_table(defines=()):
-    """[{name, sgpr, vgpr, agpr, scratch, occupancy, sgpr_spill, vgpr_spill, lds}] for every kernel of the build."""
+    """[{name, sgpr, vgpr, agpr, scratch, occupancy, sgpr_spill, vgpr_spill, lds}] for every kernel of the build.  One
+    compile per process and set of defines: the test modules that assert on the table share it."""
+    return [dict(row) for row in _kernel_table(tuple(defines))]
+
+
+@functools.lru_cache(maxsize=None)
+def _kernel_table(defines):
     from finenvs_amd.csrc import build as B
 
     with tempfile.TemporaryDirectory(prefix="fe_ru_") as tmp:
