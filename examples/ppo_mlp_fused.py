@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """PPO with the reference's MLP actor on the fused rollout: examples/ppo_lstm_fused.py for ``PPOAgentMLP``
 (finenvs/agents/PPO/PPO_agent.py:209-243) with one hidden layer -- ``ContinuousActorMLP((5W, H, 1))`` (ELU, Tanh) and
-``CriticMLP((5W, H, 1))`` (ELU, Identity).  The K env steps between two ``agent.train`` calls are ONE kernel launch
+``CriticMLP((5W, H, 1))`` (ELU, Identity) -- or, with ``--hidden-layers 2``, with the reference's default of two:
+``(5W, H, H, 1)`` (finenvs_amd/mlp2_head.py, include/finenvs_amd_mlp2_head.h).  The K env steps between two ``agent.train`` calls are ONE kernel launch
 (actor evaluated in the kernel on the matrix cores, actions sampled from the caller's noise, agent.store's fields written
 into a trajectory chunk whose ``states`` are 16-byte descriptors).
 
     python examples/ppo_mlp_fused.py [--envs 4096] [--steps 16] [--iters 5] [--hidden 64] [--window 4] [--fused-update]
-                                     [--fused-optim]
+                                     [--fused-optim] [--hidden-layers {1,2}]
 
 What runs where:
     rollout   : FusedMLPRollout.run(K, noise, std, trajectory)        one launch per K steps (fe_env_rollout_mlp_sampled),
@@ -21,6 +22,8 @@ What runs where:
                 --fused-optim (implies --fused-update): FusedAdam of finenvs_amd/optim.py with the four parameters of each
                 head and log_std registered as plain tensors (add_tensor): one launch per optimizer step.  (Packed MLP
                 weights resident in the optimizer are out of scope: the heads re-pack on the device, fe_mlp_pack.)
+                --hidden-layers 2: the same with MLP2Head / FusedMLP2Head / FusedMLP2Rollout (fe_env_rollout_mlp2_sampled,
+                fe_mlp2_forward / fe_mlp2_backward) and six parameters per head
 """
 import argparse
 import math
@@ -35,9 +38,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from finenvs_amd import TimeSeriesEnv  # noqa: E402
 from finenvs_amd.data import synthetic  # noqa: E402
 from finenvs_amd.lstm_head import ppo_actor_loss, ppo_critic_loss  # noqa: E402
+from finenvs_amd.mlp2_head import FusedMLP2Head, MLP2Head, mlp2_head_parameters  # noqa: E402
 from finenvs_amd.mlp_head import FusedMLPHead, MLPHead, mlp_head_parameters  # noqa: E402
 from finenvs_amd.optim import FusedAdam  # noqa: E402
-from finenvs_amd.rollout import FusedMLPRollout  # noqa: E402
+from finenvs_amd.rollout import FusedMLP2Rollout, FusedMLPRollout  # noqa: E402
 from finenvs_amd.stats import EpisodeStats  # noqa: E402
 from finenvs_amd.trajectory import TrajectoryBuffer  # noqa: E402
 
@@ -48,25 +52,37 @@ def _rollout_weights(net):
     return w1.detach().t(), b1.detach(), w2.detach(), float(b2.detach())
 
 
+def _rollout2_weights(net):
+    """``FusedMLP2Rollout``'s constructor arguments of an ``MLP2Head``: W1 (5W, H), b1, W2 (H, H), b2, W3, b3."""
+    w1, b1, w2, b2, w3, b3 = mlp2_head_parameters(net)
+    return w1.detach().t(), b1.detach(), w2.detach(), b2.detach(), w3.detach(), float(b3.detach())
+
+
 def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatches=4, seed=0, quiet=False,
-         fused_update=False, fused_optim=False):
+         fused_update=False, fused_optim=False, hidden_layers=1):
     fused_update = fused_update or fused_optim
+    if hidden_layers not in (1, 2):
+        raise ValueError(f"hidden_layers must be 1 or 2 (got {hidden_layers})")
+    # the module, its parameters in gradient order, the fused head, the rollout object and its constructor arguments
+    Head, parameters, FusedHead, Rollout, rollout_weights = (
+        (MLPHead, mlp_head_parameters, FusedMLPHead, FusedMLPRollout, _rollout_weights) if hidden_layers == 1 else
+        (MLP2Head, mlp2_head_parameters, FusedMLP2Head, FusedMLP2Rollout, _rollout2_weights))
     torch.manual_seed(seed)
     dev = "cuda:0"
     prices, day_id, _ = synthetic.synthetic_series(12, 1, 390, 1234)
     env = TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=window, num_envs=envs, redraw="device", seed=seed,
                         obs_dtype=torch.float32)  # the learner consumes states.float() (PPO_agent.py:101)
-    actor = MLPHead(hidden, window, "elu", "tanh", device=dev)
-    critic = MLPHead(hidden, window, "elu", "none", device=dev)
+    actor = Head(hidden, window, "elu", "tanh", device=dev)
+    critic = Head(hidden, window, "elu", "none", device=dev)
     with torch.no_grad():  # log-returns are ~1e-3: scale their columns so that the hidden units see them
         for net in (actor, critic):
             net.network[0].weight.reshape(hidden, window, 5)[:, :, :4].mul_(100.0)
     log_std = torch.nn.Parameter(torch.full((1,), math.log(0.5), device=dev))
     if fused_optim:
         opt_a, opt_c = FusedAdam(lr=3e-4), FusedAdam(lr=3e-4)
-        for p in list(mlp_head_parameters(actor)) + [log_std]:
+        for p in list(parameters(actor)) + [log_std]:
             opt_a.add_tensor(p)
-        for p in mlp_head_parameters(critic):
+        for p in parameters(critic):
             opt_c.add_tensor(p)
     else:
         opt_a = torch.optim.Adam(list(actor.parameters()) + [log_std], 3e-4)
@@ -74,11 +90,11 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
     traj = TrajectoryBuffer(steps, envs, 1, states=True)
     stats = EpisodeStats(env)
     if fused_update:  # the heads train on descriptors; each owns the rollout object that runs its parameters
-        actor_head, critic_head = FusedMLPHead(env, actor), FusedMLPHead(env, critic)
+        actor_head, critic_head = FusedHead(env, actor), FusedHead(env, critic)
         roll, value_head = actor_head.rollout, critic_head.rollout
     else:
-        roll = FusedMLPRollout(env, *_rollout_weights(actor), activation="elu", output_activation="tanh")
-        value_head = FusedMLPRollout(env, *_rollout_weights(critic), activation="elu", output_activation="none")
+        roll = Rollout(env, *rollout_weights(actor), activation="elu", output_activation="tanh")
+        value_head = Rollout(env, *rollout_weights(critic), activation="elu", output_activation="none")
     gen = torch.Generator(device=dev).manual_seed(seed)
     clip, ent_coef, gamma = 0.2, 0.01, 0.99
     history = []
@@ -130,8 +146,8 @@ def main(envs=4096, steps=16, iters=5, hidden=64, window=4, epochs=2, minibatche
             actor_head.refresh()
             critic_head.refresh()
         else:
-            roll.set_weights(*_rollout_weights(actor))  # the updated networks go back into the kernels
-            value_head.set_weights(*_rollout_weights(critic))
+            roll.set_weights(*rollout_weights(actor))  # the updated networks go back into the kernels
+            value_head.set_weights(*rollout_weights(critic))
         traj.clear()
         log = stats.read(reset=True)
         history.append((float(loss_c.detach()), float(rewards.mean()), log))
@@ -156,5 +172,8 @@ if __name__ == "__main__":
     ap.add_argument("--fused-optim", action="store_true",
                     help="with --fused-update: one launch per optimizer step (FusedAdam on the heads' tensors)")
     ap.add_argument("--fused-update", action="store_true", help="train both heads on descriptors with the fused backward")
+    ap.add_argument("--hidden-layers", type=int, default=1, choices=[1, 2],
+                    help="2: the reference's default MLP of two hidden layers (H, H)")
     a = ap.parse_args()
-    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update, fused_optim=a.fused_optim)
+    main(a.envs, a.steps, a.iters, a.hidden, a.window, fused_update=a.fused_update, fused_optim=a.fused_optim,
+         hidden_layers=a.hidden_layers)

@@ -308,6 +308,32 @@ MLP_HEAD_SIGNATURES = {
     "fe_mlp_backward": (C.c_int, [_vp, _vp, _mw, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(FeMlpGrads), _vp]),
 }
 
+# include/finenvs_amd_mlp2_head.h: the two-hidden-layer MLP head (finenvs_amd/mlp2_head.py, FusedMLP2Rollout)
+MLP2_GRAD_CHUNK_PAIRS = 512  # FE_MLP2_GRAD_CHUNK_PAIRS
+MLP2_MAX_WINDOW = {32: 296, 64: 128, 128: 40}  # FE_MLP2_MAX_WINDOW_H*: the largest window admitted with one asset
+
+
+class FeMlp2Weights(C.Structure):
+    """struct fe_mlp2_weights of include/finenvs_amd_mlp2_head.h."""
+
+    _fields_ = [("w1t", _vp), ("wpos", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp)]
+
+
+class FeMlp2Grads(C.Structure):
+    """struct fe_mlp2_grads of include/finenvs_amd_mlp2_head.h."""
+
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp)]
+
+
+_mw2 = C.POINTER(FeMlp2Weights)
+MLP2_HEAD_SIGNATURES = {
+    "fe_env_rollout_mlp2_sampled": (C.c_int, [_vp, _vp, _mw2, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.c_float, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp]),
+    "fe_mlp2_forward": (C.c_int, [_vp, _vp, _mw2, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "fe_mlp2_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_mlp2_backward": (C.c_int, [_vp, _vp, _mw2, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(FeMlp2Grads), _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -336,7 +362,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
-                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES}.items():
+                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

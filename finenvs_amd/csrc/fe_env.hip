@@ -32,6 +32,7 @@
 //   fe_rollout_kernels.h  K-step fused rollouts with an in-kernel policy: linear window / table form, MLP head (MFMA)
 //   fe_activations.h      exact-operation sigmoid / tanh shared by the LSTM and MLP heads
 //   fe_mlp_head_kernels.h  the MLP head's training entries: device packing, sampled rollout, value on descriptors, backward
+//   fe_mlp2_head_kernels.h the two-hidden-layer MLP head: sampled rollout, value on descriptors, backward
 //   fe_lstm_kernel.h      K-step fused rollout with the reference's LSTM actor (MFMA), and with the SAC actor's head
 //   fe_lstm_rollout_body.h  the register-resident rollout's body, included by both of those kernels
 //   fe_lstm_stream_tile.h   one row-tile group of the streamed recurrence at H = 256 / 512 / 1024, included by the large-H
@@ -85,12 +86,14 @@
 #include "finenvs_amd_replay_cursor.h"
 #include "finenvs_amd_ppo.h"
 #include "finenvs_amd_mlp_head.h"
+#include "finenvs_amd_mlp2_head.h"
 
 #include "fe_device_common.h"
 #include "fe_store_policy.h"
 #include "fe_step_kernel.h"
 #include "fe_rollout_kernels.h"
 #include "fe_mlp_head_kernels.h"
+#include "fe_mlp2_head_kernels.h"
 #include "fe_lstm_kernel.h"
 #include "fe_aux_kernels.h"
 #include "fe_evo_kernels.h"
@@ -1016,6 +1019,183 @@ int fe_mlp_backward(fe_env *env, const float *logret_f32, const fe_mlp_weights *
         return rc;
     hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)H * (4 * W + 2) + H + 1)), dim3(kBlock), 0, st, g);
     return launched("fe_mlp_backward: reduction");
+}
+
+// ---- include/finenvs_amd_mlp2_head.h: the two-hidden-layer MLP head ----
+static int mlp2_head_checked(const fe_env *env, const float *logret_f32, const fe_mlp2_weights *w, int32_t H, int32_t activation,
+                             int32_t out_activation, const char *who) {
+    if (!env || !logret_f32 || !w || !w->w1t || !w->wpos || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
+    if (out_activation < 0 || out_activation > 2)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh), 1 (clamp) or 2 (none)", who);
+    return FE_OK;
+}
+
+// One rule for acting, values and gradients: W1^T and the padded W2 fit the LDS next to the rollout's default tile.
+static int mlp2_head_fits(const fe_env *env, int32_t H, const char *who) {
+    const Params &p = env->p;
+    const size_t lds = mlp2_lds_bytes(128 / p.A > 1 ? 128 / p.A : 1, p.A, p.W, H);
+    if (lds > kMaxLds)
+        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) and W2 (%d x %d) do not fit the 160 KiB LDS: the window does not fit (%zu bytes "
+                    "needed)", who, (int)H, 4 * p.W, (int)H, (int)H, lds);
+    return FE_OK;
+}
+
+static Mlp2HeadArgs mlp2_head_args(const float *logret_f32, const fe_mlp2_weights *w, int32_t H, int32_t activation,
+                                   int32_t out_activation) {
+    Mlp2HeadArgs r;
+    memset(&r, 0, sizeof(r));
+    r.h.lr32 = logret_f32; r.h.w1t = w->w1t; r.h.wpos = w->wpos; r.h.b1 = w->b1; r.h.w2 = w->w3; r.h.b2 = w->b3;
+    r.h.H = H; r.h.act = activation; r.h.out_act = out_activation; r.h.K = 1;
+    r.w2h = w->w2; r.b2h = w->b2;
+    return r;
+}
+
+int fe_env_rollout_mlp2_sampled(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H,
+                                int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                                const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                                int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    static const char *who = "fe_env_rollout_mlp2_sampled";
+    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
+        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
+    if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "%s: std must be >= 0 when noise is given", who);
+    if (!obs_src || !obs_pos || !rewards_out || !dones_out || K < 1) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (int rc = require_bound(env, who)) return rc;
+    if (int rc = mlp2_head_fits(env, H, who)) return rc;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    Mlp2HeadArgs r = mlp2_head_args(logret_f32, weights, H, activation, out_activation);
+    r.h.K = K; r.h.obs_src = obs_src; r.h.obs_pos = obs_pos;
+    r.h.noise = noise; r.h.std = std; r.h.actions_out = actions_out; r.h.means_out = means_out; r.h.rew_out = rewards_out;
+    r.h.done_out = dones_out; r.h.traj_src = states_src_out; r.h.traj_pos = states_pos_out;
+    // the geometry of fe_env_rollout_mlp: 128 pairs per workgroup, one 32-pair column block per wavefront
+    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
+    const size_t lds = mlp2_lds_bytes(p.EB, p.A, p.W, H);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_rollout_mlp2_sampled_kernel<single, 1>
+                       : (H == 64 ? (const void *)fe_rollout_mlp2_sampled_kernel<single, 2>
+                                  : (const void *)fe_rollout_mlp2_sampled_kernel<single, 4>);
+    });
+    if (lds > kMaxLds)  // (a tile override larger than the default)
+        return fail(FE_ERR_ARG, "%s: the weight image does not fit the 160 KiB LDS at this tile (%zu bytes needed)", who, lds);
+    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+}
+
+int fe_mlp2_forward(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H, int32_t activation,
+                    int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
+                    void *stream) {
+    static const char *who = "fe_mlp2_forward";
+    if (!obs_src || !obs_pos || !out || count < 0) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (int rc = mlp2_head_fits(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    Mlp2HeadArgs r = mlp2_head_args(logret_f32, weights, H, activation, out_activation);
+    r.h.obs_src = const_cast<int64_t *>(obs_src); r.h.obs_pos = const_cast<double *>(obs_pos);  // read only in this kernel
+    r.h.actions_out = out; r.h.count = count;
+    const int64_t blocks = (count * p.A + 31) / 32;
+    const int64_t grid = capped_grid((blocks + kBlock / 64 - 1) / (kBlock / 64));
+    const size_t lds = mlp2_weight_lds_bytes(p.W, H);
+    const void *kern = with_bool(p.A == 1, [H](auto S) {
+        constexpr bool single = decltype(S)::value;
+        return H == 32 ? (const void *)fe_mlp2_forward_kernel<single, 1>
+                       : (H == 64 ? (const void *)fe_mlp2_forward_kernel<single, 2> : (const void *)fe_mlp2_forward_kernel<single, 4>);
+    });
+    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+}
+
+// Workspace: [dz1 (32 blocks, H)][a1][dz2][layer-1 partials (splits, H, F)][[dW2 | d b2] partials (splits, H, H + 32)]
+// [d w3 / d b3 partials (waves, H + 4)].
+int64_t fe_mlp2_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
+    if (count == 0) return 0;
+    const int64_t blocks = (count + 31) / 32, splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
+    return 3 * 32 * blocks * H + splits * H * (mlp_grad_fp(W) + H + 32) + 4 * mlp_grad_groups(blocks) * (H + 4);
+}
+
+int fe_mlp2_backward(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H, int32_t activation,
+                     int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                     const float *outputs, const float *d_outputs, float *workspace, const fe_mlp2_grads *grads,
+                     void *stream) {
+    static const char *who = "fe_mlp2_backward";
+    if (!obs_src || !obs_pos || count < 0 || !d_outputs || !workspace || !grads || !grads->w1 || !grads->b1 || !grads->w2 ||
+        !grads->b2 || !grads->w3 || !grads->b3)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (out_activation == 1)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on", who);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_mlp2_forward returned", who);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused LSTM "
+                    "head does)", who, (int)env->p.A);
+    if (int rc = mlp2_head_fits(env, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    Mlp2GradArgs g2;
+    memset(&g2, 0, sizeof(g2));
+    MlpGradArgs &g = g2.g;
+    g.lr32 = logret_f32; g.w1t = weights->w1t; g.wpos = weights->wpos; g.b1 = weights->b1; g.w2 = weights->w3;
+    g.obs_src = obs_src; g.obs_pos = obs_pos; g.outputs = outputs; g.d_outputs = d_outputs;
+    g.count = count; g.blocks = (count + 31) / 32; g.splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
+    const int64_t groups = mlp_grad_groups(g.blocks);
+    g.waves = 4 * groups;
+    g.W = W; g.H = H; g.act = activation; g.out_act = out_activation; g.FP = mlp_grad_fp(W);
+    const int64_t rows = 32 * g.blocks * H;
+    g.dpre = workspace;
+    g2.a1 = g.dpre + rows;
+    g2.dz2 = g2.a1 + rows;
+    g.part = g2.dz2 + rows;
+    g2.part2 = g.part + g.splits * H * g.FP;
+    g.wpart = g2.part2 + g.splits * H * (H + 32);
+    g.g_w1 = grads->w1; g.g_b1 = grads->b1; g.g_w2 = grads->w3; g.g_b2 = grads->b3;
+    g2.w2h = weights->w2; g2.b2h = weights->b2; g2.g_w2h = grads->w2; g2.g_b2h = grads->b2;
+    void *args2[] = {&g2};
+    void *args[] = {&g};
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t wave_groups = capped_grid((g.blocks + kBlock / 64 - 1) / (kBlock / 64));
+    // (1) both hidden layers recomputed: a1, dz2, the partials of d w3 / d b3
+    const void *k1 = H == 32 ? (const void *)fe_mlp2_grad_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp2_grad_kernel<2> : (const void *)fe_mlp2_grad_kernel<4>);
+    const size_t lds1 = mlp2_weight_lds_bytes(W, H);
+    if (int rc = prepare_big_lds(env->device, k1, lds1, who)) return rc;
+    if (int rc = launched("fe_mlp2_backward: hidden layers", hipLaunchKernel(k1, dim3((unsigned)groups), dim3(kBlock), args2, lds1, st)))
+        return rc;
+    // (2) dz1 = (W2^T dz2) * act'(z1)
+    const void *k2 = H == 32 ? (const void *)fe_mlp2_dgrad_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp2_dgrad_kernel<2> : (const void *)fe_mlp2_dgrad_kernel<4>);
+    const size_t lds2 = (size_t)H * mlp2_hp(H) * 4;
+    if (int rc = prepare_big_lds(env->device, k2, lds2, who)) return rc;
+    if (int rc = launched("fe_mlp2_backward: W2^T dz2", hipLaunchKernel(k2, dim3((unsigned)wave_groups), dim3(kBlock), args2, lds2, st)))
+        return rc;
+    // (3) [dW2 | d b2] partials
+    const void *k3 = H == 32 ? (const void *)fe_mlp2_wgrad2_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp2_wgrad2_kernel<2> : (const void *)fe_mlp2_wgrad2_kernel<4>);
+    const int64_t items3 = g.splits * (H / 32 + 1);
+    if (int rc = launched("fe_mlp2_backward: dz2^T a1",
+                          hipLaunchKernel(k3, dim3((unsigned)capped_grid((items3 + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock),
+                                          args2, 0, st)))
+        return rc;
+    // (4), (5) the first layer's weight gradient and the output layer's partials: fe_mlp_backward's kernels on dz1
+    const void *k4 = H == 32 ? (const void *)fe_mlp_wgrad_kernel<1>
+                             : (H == 64 ? (const void *)fe_mlp_wgrad_kernel<2> : (const void *)fe_mlp_wgrad_kernel<4>);
+    const int64_t items = g.splits * (g.FP / 32);
+    const int64_t grid4 = capped_grid((items + kBlock / 64 - 1) / (kBlock / 64));
+    if (int rc = launched("fe_mlp2_backward: first-layer weight gradient", hipLaunchKernel(k4, dim3((unsigned)grid4), dim3(kBlock), args, 0, st)))
+        return rc;
+    hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)H * (4 * W + 2) + H + 1)), dim3(kBlock), 0, st, g);
+    if (int rc = launched("fe_mlp2_backward: reduction")) return rc;
+    hipLaunchKernelGGL(fe_mlp2_grad_reduce_kernel, dim3(grid_for((int64_t)H * (H + 1))), dim3(kBlock), 0, st, g2);
+    return launched("fe_mlp2_backward: W2 reduction");
 }
 
 // Tile geometry of the fused LSTM kernels (LSTM and SAC heads) for `count` envs (rollout) or descriptors (forward): sets

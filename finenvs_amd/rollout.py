@@ -526,6 +526,134 @@ class FusedMLPRollout(_FusedEvaluation):
         return actions, rewards, dones
 
 
+class FusedMLP2Rollout(_FusedEvaluation):
+    """``FusedMLPRollout`` for the reference's default MLP of two hidden layers (``hidden_dims=(H, H)``,
+    finenvs/agents/networks/multilayer_perceptron.py; C ABI include/finenvs_amd_mlp2_head.h):
+
+        mean = out(b3 + W3 . act(W2 act(W1^T . flatten(states.float()) + b1) + b2))
+
+    per (env, asset) pair, ``H`` in {32, 64, 128}.  ``W1`` is (5W, H) with rows in observation order, ``W2`` (H, H) as
+    ``network[2].weight`` holds it, ``b1`` / ``b2`` / ``W3`` (H,).  Both layers run on the MFMA units; the second takes
+    the first one's activations from registers.  Every ``run`` is ``fe_env_rollout_mlp2_sampled``, ``forward`` is
+    ``fe_mlp2_forward``; no observation is written to HBM."""
+
+    ACTIVATIONS = FusedMLPRollout.ACTIVATIONS
+    OUTPUT_ACTIVATIONS = FusedMLPRollout.OUTPUT_ACTIVATIONS
+
+    def __init__(self, env, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor,
+                 b3: float = 0.0, activation: str = "elu", output_activation: str = "clamp"):
+        W = env.num_intervals
+        if W1.dim() != 2 or W1.shape[0] != 5 * W:
+            raise ValueError(f"W1 must be ({5 * W}, H): one row per flattened observation element")
+        H = int(W1.shape[1])
+        if H not in (32, 64, 128):
+            raise ValueError("H must be 32, 64 or 128")
+        if tuple(W2.shape) != (H, H):
+            raise ValueError(f"W2 must be ({H}, {H}): both hidden layers have the same width")
+        if activation not in self.ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(self.ACTIVATIONS)}")
+        if output_activation not in self.OUTPUT_ACTIVATIONS:
+            raise ValueError(f"output_activation must be one of {sorted(self.OUTPUT_ACTIVATIONS)}")
+        if env.redraw != "device" and not env.evaluate:
+            raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
+        self.env, self.H, self.act = env, H, self.ACTIVATIONS[activation]
+        self.out_act = self.OUTPUT_ACTIVATIONS[output_activation]
+        self.means = None
+        dev = env._dev
+        self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
+        self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
+        self._lr32 = getattr(env, "_log_return_f32", None)
+        if self._lr32 is None:
+            self._lr32 = env.log_return_environments.float().contiguous()
+        self.set_weights(W1, b1, W2, b2, W3, b3)
+        self.sync_from_env()
+
+    def set_weights(self, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor,
+                    b3: float) -> None:
+        """The first layer is packed as ``FusedMLPRollout.set_weights`` packs it; the rest is kept as given."""
+        W, H, dev = self.env.num_intervals, self.H, self.env._dev
+        w = W1.detach().to(dtype=torch.float32, device="cpu").reshape(W, 5, H)
+        self.w1t = w[:, :4, :].reshape(4 * W, H).t().contiguous().to(dev)
+        wpos = torch.zeros((H,), dtype=torch.float32)
+        for j in range(W):  # sequential f32 sum, j ascending, as fe_mlp_pack
+            wpos = wpos + w[j, 4, :]
+        self.wpos = wpos.to(dev)
+        self.b1 = b1.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
+        self.w2 = W2.detach().to(dtype=torch.float32, device=dev).reshape(H, H).contiguous()
+        self.b2 = b2.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
+        self.w3 = W3.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
+        self.b3_dev = torch.tensor([float(b3)], dtype=torch.float32).to(dev)
+
+    def _weights(self):
+        from . import _lib
+
+        return _lib.FeMlp2Weights(self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
+                                  self.b2.data_ptr(), self.w3.data_ptr(), self.b3_dev.data_ptr())
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The head on ANY B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` float64): ``(B, A)``
+        float32 (C ABI ``fe_mlp2_forward``), without stepping the env and without materialising the observations."""
+        from . import _lib
+
+        env, A = self.env, self.env.num_assets
+        B = int(obs_src.numel())
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
+        if out is None:
+            out = torch.empty((B, A), dtype=torch.float32, device=env._dev)
+        elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
+            raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
+        if B:
+            w = self._weights()
+            _lib.check(env._lib.fe_mlp2_forward(env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act,
+                                                src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), env._stream()))
+        return out
+
+    def run(self, num_steps: int, record_actions: bool = True, noise: Optional[torch.Tensor] = None,
+            std: Optional[float] = None, record_means: bool = False, trajectory=None):
+        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32); arguments and semantics as
+        ``FusedMLPRollout.run``: ``noise`` (K, N, A) f32 with ``std`` samples ``clamp(mean + std * noise, -1, 1)`` (the
+        eval env of a training-mode env acts on the mean), ``record_means`` keeps ``self.means``, ``trajectory`` is an
+        empty ``TrajectoryBuffer(K, N, A, states=True)`` the kernel fills with the K + 1 descriptor rows."""
+        from . import _lib
+
+        env, K = self.env, int(num_steps)
+        N, A = env.num_envs, env.num_assets
+        dev = env._dev
+        src_out = pos_out = None
+        if trajectory is not None:
+            tr = trajectory
+            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
+                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
+                                 "without capacity padding")
+            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
+            src_out, pos_out = tr.obs_src, tr.obs_pos
+        else:
+            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
+            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
+            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
+        if noise is not None:
+            if std is None or not float(std) >= 0.0:
+                raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
+            if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
+                raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
+            noise = noise.contiguous()
+        self._begin_run()
+        self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
+        w = self._weights()
+        _lib.check(env._lib.fe_env_rollout_mlp2_sampled(
+            env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, K, self.obs_src.data_ptr(),
+            self.obs_pos.data_ptr(), noise.data_ptr() if noise is not None else None,
+            float(std) if noise is not None else 0.0, actions.data_ptr() if actions is not None else None,
+            self.means.data_ptr() if record_means else None, rewards.data_ptr(), dones.data_ptr(),
+            src_out.data_ptr() if src_out is not None else None, pos_out.data_ptr() if pos_out is not None else None,
+            env._stream()))
+        self._end_run()
+        if trajectory is not None:
+            trajectory.mark_filled(K)
+        return actions, rewards, dones
+
+
 def lstm_row_order(H: int) -> torch.Tensor:
     """Row of ``weight_hh_l0`` / ``weight_ih_l0`` (torch order: gate * H + unit, gates i, f, g, o) that packed row
     R = 32*mt + 8*b + 4*half + gate holds: the hidden unit of R is 8*mt + 4*half + b, so that one accumulator lane of

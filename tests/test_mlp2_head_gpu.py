@@ -1,0 +1,743 @@
+"""GPU: the two-hidden-layer MLP head trained on descriptors (include/finenvs_amd_mlp2_head.h, finenvs_amd/mlp2_head.py,
+FusedMLP2Rollout).
+
+* anchor: with ``W2 = I``, ``b2 = 0`` and ReLU the deeper head IS the one-layer head (``relu(relu(z)) = relu(z)``, the
+  identity contraction is exact): ``fe_mlp2_forward`` equals ``fe_mlp_forward`` and ``FusedMLP2Rollout.run`` equals
+  ``FusedMLPRollout.run`` on a twin env bit for bit -- actions, means, rewards, dones, descriptor rows, end state;
+* rollout self-consistency with general weights: ``fe_mlp2_forward`` on row k of the recorded descriptors equals
+  ``means[k]``, ``actions == clamp(means + std * noise, -1, 1)`` in torch f32, the eval env acts on its mean, an
+  evaluate-mode env samples everywhere, ``run(3); run(3)`` equals ``run(6)``, and a twin env stepped with
+  ``env.step(actions[k])`` returns the same rewards, dones and final state, all bit for bit;
+* values: ``head(src, pos)`` equals ``rollout.forward(src, pos)`` bit for bit, and the f64 copy of the module within the
+  project's yardstick ``2e-5 max|y64| + 4 max|y32 - y64|``;
+* gradients of the six parameters (and PPO's ``log_std``) against an f64 torch copy of the module on the rendered states,
+  within ``2e-5 max|g64| + 4 max|g_torch32 - g64|`` per tensor, for ``y.sum()``, the PPO critic loss and the PPO actor
+  loss.  On every batch, from the f64 copy: ``max|p| < 4``, no f64 gradient identically zero, the share of negative
+  pre-activations of BOTH hidden layers in [0.2, 0.8], and the samples with any ``|z1|`` or ``|z2| < 1e-5`` get upstream
+  gradient 0 in all three arms and are at most 2 % of B.  One more condition on the batch, decided by the f64 copy alone
+  (``_output_bias_gradient_is_resolvable``): ``d b3`` must not cancel below one ulp of forward noise;
+* two backward calls give the same bits; ``.grad`` accumulates as torch's does; a frozen head gets nothing; B = 0 works;
+  a pending ``backward()`` after a ``refresh()`` differentiates the weights its forward ran with;
+* memory contract: nothing is written outside the workspace (exactly as long as the size function says), the six
+  gradient buffers, ``out``, ``means_out`` and the descriptor rows, and NaN-filled buffers give the bits of
+  sentinel-filled ones;
+* the window limit at H = 128, refusals, and examples/ppo_mlp_fused.py with ``hidden_layers=2``.
+"""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from tests import test_lstm_grad_gpu as tl
+from tests import test_mlp_head_gpu as th
+from tests import test_mlp_rollout_gpu as tm
+
+pytestmark = pytest.mark.gpu
+NAMES = ("w1", "b1", "w2", "b2", "w3", "b3")
+CLIP, ENT = tl.CLIP, tl.ENT
+CHUNK = 512  # FE_MLP2_GRAD_CHUNK_PAIRS
+F32, F64, I64, I32 = torch.float32, torch.float64, torch.int64, torch.int32
+assert_bits, _env, _descriptors, _zero = th.assert_bits, th._env, th._descriptors, th._zero
+STATE = ("cash", "margin", "long_shares", "short_shares", "env_indices", "env_spots")
+
+
+def _module(H, W, seed, activation="elu", output="tanh", identity=False):
+    """MLP2Head with the first-layer scaling of tests/test_mlp_rollout_gpu.py::_weights, the second layer drawn as
+    randn(H, H) 1.5 / sqrt(H) with bias 0.3 randn; ``identity``: W2 = I, b2 = 0 (the anchor to the one-layer head)."""
+    from finenvs_amd.mlp2_head import MLP2Head
+
+    W1, b1, W3, b3 = tm._weights(W, H, seed)
+    gen = torch.Generator().manual_seed(1000 + seed)
+    m = MLP2Head(H, W, activation, output)
+    with torch.no_grad():
+        m.network[0].weight.copy_(torch.from_numpy(W1).t())
+        m.network[0].bias.copy_(torch.from_numpy(b1))
+        if identity:
+            m.network[2].weight.copy_(torch.eye(H))
+            m.network[2].bias.zero_()
+        else:
+            m.network[2].weight.copy_(torch.randn((H, H), generator=gen) * (1.5 / np.sqrt(H)))
+            m.network[2].bias.copy_(0.3 * torch.randn((H,), generator=gen))
+        m.network[4].weight.copy_(torch.from_numpy(W3).reshape(1, H))
+        m.network[4].bias.fill_(float(b3))
+    return m.cuda()
+
+
+def _rollout(env, module, output="tanh"):
+    """A FusedMLP2Rollout of the module's parameters through the host packing (set_weights)."""
+    from finenvs_amd.mlp2_head import mlp2_head_parameters
+    from finenvs_amd.rollout import FusedMLP2Rollout
+
+    w1, b1, w2, b2, w3, b3 = (p.detach() for p in mlp2_head_parameters(module))
+    return FusedMLP2Rollout(env, w1.t(), b1, w2, b2, w3, float(b3), activation=module.activation, output_activation=output)
+
+
+def _params(module):
+    from finenvs_amd.mlp2_head import mlp2_head_parameters
+
+    return list(mlp2_head_parameters(module))
+
+
+def _max_window(H):
+    """The largest W whose weight image fits the LDS next to the rollout's tile of 128 pairs: mlp_lds_bytes of
+    finenvs_amd/csrc/fe_rollout_kernels.h at EB = 128, A = 1, plus b2 and the W2 image with rows of H + 4 floats
+    (mlp2_extra_lds_bytes of finenvs_amd/csrc/fe_mlp2_head_kernels.h), against 160 KiB."""
+    def lds(W):
+        kp = -(-4 * W // 32) * 32 + 4
+        tile = 128 * 8 + 128 * 8 + 128 * 8 + 128 * 4 + 128 * 4 + 128 * 4
+        b = ((tile + 7) & ~7) + 128 * 8 + 128 * 4
+        b = (b + 15) & ~15
+        b = (b + H * kp * 4 + 3 * H * 4 + 15) & ~15
+        return b + (H + H * (H + 4)) * 4
+
+    W = 1
+    while lds(W + 1) <= 160 * 1024:
+        W += 1
+    return W
+
+
+WMAX = _max_window(128)
+
+
+# ------------------------------------------------------------------------------------ anchor to the one-layer head
+@pytest.mark.parametrize("N,A,W,H", [(300, 1, 8, 32), (77, 3, 7, 64), (200, 1, 16, 128)])
+def test_identity_second_layer_equals_the_one_layer_head_bit_for_bit(N, A, W, H):
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    K = 3
+    m2 = _module(H, W, 3 * N + W, "relu", identity=True)
+    m1 = th._module(H, W, 3 * N + W, "relu")  # the same W1, b1 and output layer
+    assert torch.equal(m1.network[0].weight, m2.network[0].weight) and torch.equal(m1.network[2].weight, m2.network[4].weight)
+    envs = [_env(N, W, A=A), _env(N, W, A=A)]
+    one, two = th._rollout(envs[0], m1, "tanh"), _rollout(envs[1], m2, "tanh")
+    dev = envs[0]._dev
+    gen = torch.Generator(device=dev).manual_seed(N)
+    assert_bits(two.forward(two.obs_src, two.obs_pos), one.forward(one.obs_src, one.obs_pos), "forward on the first state")
+    for rep, noise in enumerate((None, torch.randn((K, N, A), generator=gen, device=dev), None)):
+        trajs = [TrajectoryBuffer(K, N, A, device=dev, states=True) for _ in range(2)]
+        kw = dict(noise=noise, std=0.6 if noise is not None else None, record_means=True)
+        a0, r0, d0 = one.run(K, trajectory=trajs[0], **kw)
+        a1, r1, d1 = two.run(K, trajectory=trajs[1], **kw)
+        what = f"run {rep}"
+        assert_bits(a1, a0, what + " actions")
+        assert_bits(two.means, one.means, what + " means")
+        assert_bits(r1, r0, what + " rewards")
+        assert_bits(d1, d0, what + " dones")
+        assert_bits(trajs[1].obs_src, trajs[0].obs_src, what + " descriptor rows")
+        assert_bits(trajs[1].obs_pos, trajs[0].obs_pos, what + " descriptor rows")
+        for name in STATE:
+            assert_bits(getattr(envs[1], name), getattr(envs[0], name), f"{what} {name}")
+        assert_bits(two.obs_src, one.obs_src, what + " obs_src")
+        assert_bits(two.obs_pos, one.obs_pos, what + " obs_pos")
+        src, pos = trajs[0].obs_src.reshape(-1), trajs[0].obs_pos.reshape(-1, A)
+        assert_bits(two.forward(src, pos), one.forward(src, pos), what + " forward on all K + 1 rows")
+    assert float(one.means.abs().max()) > 0.3 and float(one.means.min()) < 0 < float(one.means.max())
+
+
+# -------------------------------------------------------------------------------------------- rollout self-consistency
+@pytest.mark.parametrize("N,A,W,H,activation,evaluate", [(131, 1, 4, 32, "elu", False), (77, 3, 7, 64, "tanh", False),
+                                                         (131, 5, 4, 128, "elu", False), (131, 1, 4, 32, "tanh", True)])
+def test_rollout_is_consistent_with_forward_sampling_and_env_step(N, A, W, H, activation, evaluate):
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    m = _module(H, W, N + H, activation)
+    envs = [_env(N, W, A=A, evaluate=evaluate) for _ in range(3)]
+    r6, r33 = _rollout(envs[0], m), _rollout(envs[1], m)
+    dev = envs[0]._dev
+    gen = torch.Generator(device=dev).manual_seed(N)
+    noise = torch.randn((6, N, A), generator=gen, device=dev)
+    std = 0.7
+    traj = TrajectoryBuffer(6, N, A, device=dev, states=True)
+    a, r, d = r6.run(6, noise=noise, std=std, record_means=True, trajectory=traj)
+    means = r6.means
+    assert a.data_ptr() == traj.actions.data_ptr() and len(traj) == 6
+    for k in range(6):  # the means are the head on the recorded states
+        assert_bits(r6.forward(traj.obs_src[k], traj.obs_pos[k]), means[k], f"means of step {k}")
+    assert_bits(traj.obs_src[6], r6.obs_src, "last descriptor row")
+    assert_bits(traj.obs_pos[6], r6.obs_pos)
+    want = (means + torch.tensor(std, dtype=F32, device=dev) * noise).clamp(-1.0, 1.0)
+    if not evaluate:
+        ev = int(envs[0]._eval_env)
+        assert ev == N - 1
+        assert_bits(a[:, ev], means[:, ev], "the eval env acts on its mean")
+        assert not torch.equal(want[:, ev], means[:, ev])
+        want[:, ev] = means[:, ev]
+    else:
+        assert int(envs[0]._eval_env) == -1
+    assert_bits(a, want, "actions = clamp(means + std * noise)")
+    assert int((a != means).sum()) > 0.9 * (a.numel() - 6 * A)
+    assert bool((means.abs() < 1.0).all()) and float(means.std()) > 0.05
+    # two launches of three steps are one of six
+    parts = [r33.run(3, noise=noise[:3].contiguous(), std=std, record_means=True)]
+    m0 = r33.means
+    parts.append(r33.run(3, noise=noise[3:].contiguous(), std=std, record_means=True))
+    assert_bits(torch.cat([m0, r33.means]), means, "means")
+    for i, name in enumerate(("actions", "rewards", "dones")):
+        assert_bits(torch.cat([parts[0][i], parts[1][i]]), (a, r, d)[i], name)
+    assert_bits(r33.obs_src, r6.obs_src)
+    assert_bits(r33.obs_pos, r6.obs_pos)
+    # a twin env stepped with the recorded actions
+    twin = envs[2]
+    for k in range(6):
+        _, rk, dk, _ = twin.step(a[k].contiguous())
+        assert_bits(rk, r[k], f"env.step rewards of step {k}")
+        assert_bits(dk, d[k], f"env.step dones of step {k}")
+    envs[0]._sync_public_views()
+    for name in STATE:
+        assert_bits(getattr(twin, name), getattr(envs[0], name), f"env.step {name}")
+    with pytest.raises(ValueError, match="std"):
+        r6.run(1, noise=noise[:1].contiguous())
+    with pytest.raises(ValueError, match="noise must be"):
+        r6.run(2, noise=noise[:1].contiguous(), std=std)
+    with pytest.raises(ValueError, match="trajectory must be"):
+        r6.run(3, trajectory=TrajectoryBuffer(4, N, A, device=dev, states=True))
+
+
+# -------------------------------------------------------------------------------------------------------------- values
+@pytest.mark.parametrize("H,W,activation,output", [(32, 4, "elu", "tanh"), (64, 7, "relu", "none"), (128, 16, "tanh", "tanh"),
+                                                   (128, WMAX, "elu", "none")])
+def test_values_equal_forward_bit_for_bit_and_the_f64_module_within_the_yardstick(H, W, activation, output):
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    env = _env(300, W)
+    src, pos, _ = _descriptors(env, 557)
+    m = _module(H, W, 11, activation, output)
+    head = FusedMLP2Head(env, m)
+    y = head(src, pos)
+    assert y.shape == (557, 1) and y.dtype is F32 and y.requires_grad
+    assert_bits(y, head.rollout.forward(src, pos))
+    assert_bits(y, _rollout(env, m, output).forward(src, pos), "device packing against host packing")
+    states = env.render(src, pos)
+    with torch.no_grad():
+        y32 = m(states.float()).double()
+        y64 = copy.deepcopy(m).double()(states.double())
+    err = float((y.detach().double() - y64).abs().max())
+    tol = 2e-5 * float(y64.abs().max()) + 4 * float((y32 - y64).abs().max())
+    print(f"values ({H}, {W}, {activation}, {output}): err {err:.3e} tol {tol:.3e} ratio {err / tol:.3f}")
+    assert err <= tol, (err, tol)
+    assert float(y64.std()) > 0.05
+
+
+# ----------------------------------------------------------------------------------------------------------- gradients
+class _Shaped(nn.Module):
+    """An MLP2Head under the attribute names tests/test_lstm_grad_gpu.py::_ppo_inputs perturbs (``last_layer[0].bias``)."""
+
+    def __init__(self, m):
+        super().__init__()
+        self.m = m
+        self.last_layer = nn.Sequential(m.network[4], m.network[5])
+
+    def forward(self, states):
+        return self.m(states)
+
+
+def _conditions(module, states):
+    """The batch conditions, from the f64 copy; returns the kink mask (B, 1)."""
+    B = states.shape[0]
+    m64 = copy.deepcopy(module).double()
+    with torch.no_grad():
+        x = states.double().reshape(B, -1)
+        z1 = m64.network[0](x)
+        z2 = m64.network[2](m64.network[1](z1))
+        p = m64.network[4](m64.network[3](z2))
+    assert float(p.abs().max()) < 4.0, float(p.abs().max())  # not saturated
+    for z in (z1, z2):
+        neg = float((z < 0).double().mean())
+        assert 0.2 <= neg <= 0.8, neg
+    kink = (z1.abs() < 1e-5).any(dim=1, keepdim=True) | (z2.abs() < 1e-5).any(dim=1, keepdim=True)
+    assert int(kink.sum()) <= 0.02 * B, (int(kink.sum()), B)
+    return kink
+
+
+def _torch_grads(kind, module, states, kink, extra, dtype):
+    m = copy.deepcopy(module).to(dtype)
+    _zero(m)
+    if kind == "ppo_actor":
+        log_std = extra[0].detach().clone().to(dtype).requires_grad_(True)
+        extra = (log_std,) + tuple(extra[1:])
+    loss = th._loss(kind, m(states.to(dtype)), kink, extra, dtype)
+    loss.backward()
+    return loss.detach(), [p.grad for p in _params(m)] + ([log_std.grad] if kind == "ppo_actor" else [])
+
+
+def _fused_grads(kind, head, src, pos, kink, extra):
+    _zero(head.module)
+    if kind == "ppo_actor":
+        log_std = extra[0].detach().clone().requires_grad_(True)
+        extra = (log_std,) + tuple(extra[1:])
+    loss = th._loss(kind, head(src, pos), kink, extra, F32)
+    loss.backward()
+    return loss.detach(), [p.grad.clone() for p in _params(head.module)] + ([log_std.grad] if kind == "ppo_actor" else [])
+
+
+def _compare(kind, g, g32, g64):
+    worst = 0.0
+    for name, gf, gt, gd in zip(NAMES + ("log_std",), g, g32, g64):
+        assert gf.shape == gd.shape and gf.dtype is F32, (kind, name)
+        assert float(gd.abs().max()) > 0, (kind, name)  # not degenerate
+        err = float((gf.double() - gd).abs().max())
+        tol = 2e-5 * float(gd.abs().max()) + 4 * float((gt.double() - gd).abs().max())
+        print(f"{kind:10s} {name:7s} err {err:.3e} tol {tol:.3e} ratio {err / tol:.3f}")
+        worst = max(worst, err / tol)
+        assert err <= tol, (kind, name, err, tol)
+    return worst
+
+
+ULP = 2.0 ** -23  # of a float32 in [1, 2): the grid p lives on (max|p| < 4 is asserted)
+
+
+def _output_bias_gradient_is_resolvable(kind, module, states, kink, extra):
+    """From the f64 copy alone: is ``d b3 = sum_n dp_n`` (dp_n = d loss / d p_n) a sum the yardstick can be asked of?
+
+    Every f32 forward, torch's included, carries at least one rounding of p: p_n + e_n with |e_n| of the order of ULP.
+    The loss is evaluated on that output, so each term moves by ``s_n e_n`` with ``s_n = d dp_n / d p_n`` and the sum by
+    about ``ULP ||s||_2`` -- whatever the backward does.  The yardstick's floor for a one-element tensor is
+    ``2e-5 |sum_n dp_n|``; its other part, four times torch f32's REALISED error, is one draw of that same noise and can
+    be arbitrarily small.  Under a PPO loss the terms have both signs and the sum can cancel by orders of magnitude (a
+    draw with |sum dp| = 5e-5, where d w3 of the same batch reaches 0.19, was met at (64, 2, 33, elu); the fused forward's
+    noise on y was measured there at 2.3e-7 rms and torch f32's at 1.7e-7); such a batch measures the lottery, not the code.  So a batch is
+    used only if ``2e-5 |sum dp| >= ULP ||s||_2``: the floor alone covers one ulp of forward noise."""
+    m64 = copy.deepcopy(module).double()
+    x = states.double().reshape(states.shape[0], -1)
+    p = m64.network[:5](x).detach().requires_grad_(True)
+    if kind == "ppo_actor":
+        extra = (extra[0].detach().double(),) + tuple(extra[1:])
+    loss = th._loss(kind, m64.network[5](p), kink, extra, F64)
+    (dp,) = torch.autograd.grad(loss, p, create_graph=True)
+    # the loss is a mean over samples: d dp_m / d p_n = 0 for m != n.  (dp constant in p, y.sum() of a critic: no noise term)
+    s = torch.autograd.grad(dp.sum(), p, allow_unused=True)[0] if dp.requires_grad else None
+    noise = ULP * (float(s.norm()) if s is not None else 0.0)
+    return 2e-5 * abs(float(dp.detach().sum())) >= noise
+
+
+def _inputs(kind, module, states, kink, seed):
+    """The loss's other inputs, drawn from the first seed from ``seed`` up whose batch
+    ``_output_bias_gradient_is_resolvable`` (decided by f64 torch alone, never by the code under test)."""
+    B = states.shape[0]
+    for s in range(seed, seed + 32):
+        if kind == "ppo_actor":
+            extra = tl._ppo_inputs(_Shaped(module), states, s)
+        elif kind == "ppo_critic":
+            gen = torch.Generator(device="cuda").manual_seed(s)
+            with torch.no_grad():
+                extra = module(states.float()) + 0.3 * torch.randn((B, 1), generator=gen, device="cuda")  # the returns
+        else:
+            extra = None
+        if _output_bias_gradient_is_resolvable(kind, module, states, kink, extra):
+            if s != seed:
+                print(f"{kind}: seeds {seed}..{s - 1} give a cancelling d b3, using {s}")
+            return extra
+        assert kind != "sum"  # dp = 1 or 1 - y^2 > 0: nothing cancels
+    raise AssertionError("no seed gives a resolvable d b3")
+
+
+def _check_against_f64(kind, head, env, src, pos, seed=7):
+    states = env.render(src, pos)
+    kink = _conditions(head.module, states)
+    extra = _inputs(kind, head.module, states, kink, seed)
+    loss, g = _fused_grads(kind, head, src, pos, kink, extra)
+    l32, g32 = _torch_grads(kind, head.module, states.float(), kink, extra, F32)
+    l64, g64 = _torch_grads(kind, head.module, states.double(), kink, extra, F64)
+    assert len(g) == len(g32) == len(g64) == (7 if kind == "ppo_actor" else 6)
+    worst = _compare(kind, g, g32, g64)
+    err, tol = abs(float(loss) - float(l64)), 2e-5 * abs(float(l64)) + 4 * abs(float(l32) - float(l64)) + 1e-7
+    assert err <= tol, (kind, "loss", err, tol)
+    return worst
+
+
+def _conditioned_module(states, H, W, seed, activation, output):
+    """The module of the first seed among ``seed``, ``seed + 1000``, ... whose f64 copy meets ``_conditions`` on these
+    states.  (Envs that share a day start from the same observation: at B = 33 one unit within 1e-5 of zero on such a
+    state is three kink samples, and 2 % of 33 allows none.)  ``_check_against_f64`` asserts the conditions again."""
+    for s in range(seed, seed + 8000, 1000):
+        m = _module(H, W, s, activation, output)
+        try:
+            _conditions(m, states)
+        except AssertionError as exc:
+            print(f"module seed {s} misses the batch conditions on these descriptors ({exc}); trying {s + 1000}")
+            continue
+        return m
+    raise AssertionError("no module seed meets the batch conditions")
+
+
+ACTIVATION_CASES = [(H, 4, 33, act, F64 if (H // 32 + i) % 2 else F32) for H in (32, 64, 128)
+                    for i, act in enumerate(("elu", "relu", "tanh"))]
+SIZE_CASES = [
+    (64, 4, 1, "elu", F64), (32, 4, 31, "elu", F32), (128, 4, 32, "elu", F64), (64, 4, 257, "relu", F32),
+    (128, 4, 4097, "tanh", F32),
+    (64, 4, CHUNK - 1, "elu", F32), (128, 4, CHUNK, "elu", F64), (32, 4, CHUNK + 1, "relu", F64),
+    (64, 4, 2 * CHUNK + 33, "tanh", F32),
+    (32, 4, 70001, "elu", F64),        # more blocks than the first kernel has wavefronts: its grid-stride
+    (32, 1, 33, "elu", F64),           # W = 1: the second lane half reads only zero padding
+    (128, 1, 31, "relu", F32),
+    (64, 2, 33, "elu", F32),
+    (64, 7, 33, "elu", F64),           # odd W: the last row group half empty
+    (128, WMAX, 33, "elu", F32),       # the largest window the LDS admits at H = 128
+]
+
+
+@pytest.mark.parametrize("H,W,B,activation,obs_dtype", ACTIVATION_CASES + SIZE_CASES)
+def test_gradients_against_f64_torch(H, W, B, activation, obs_dtype):
+    """Worst err / tol over kinds (PPO actor, PPO critic, y.sum() of both heads) and tensors per case (H, W, B,
+    activation), measured on an MI355X:
+      activations at W = 4, B = 33   H = 32: elu 0.085, relu 0.047, tanh 0.262;  H = 64: 0.086, 0.324, 0.035;
+                                     H = 128: 0.132, 0.114, 0.166
+      batch sizes at W = 4           (64, 1, elu) 0.033, (32, 31, elu) 0.092, (128, 32, elu) 0.104, (64, 257, relu) 0.085,
+                                     (128, 4 097, tanh) 0.357
+      around the split of 512 pairs  (64, 511, elu) 0.187, (128, 512, elu) 0.227, (32, 513, relu) 0.267,
+                                     (64, 1 057, tanh) 0.144
+      the first kernel's grid-stride (32, 4, 70 001, elu) 0.349
+      windows                        W = 1: (32, 33, elu) 0.158, (128, 31, relu) 0.095;  W = 2: (64, 33, elu) 0.076;
+                                     W = 7: (64, 33, elu) 0.100;  W = 40, the largest at H = 128: (128, 33, elu) 0.080
+    Two batches were re-drawn by the f64-only rules above: at (64, 2, 33, elu) the PPO inputs of seed 7 give a d b3 that
+    cancels to 5e-5 (with them: err 1.08e-7 against tol 1.06e-7 on that one element, every other tensor <= 0.10), seed 8
+    is used; at (128, 40, 33, elu) module seed 188 puts a unit within 1e-5 of zero on a start state three envs share."""
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    env = _env(min(B, 4096), W, obs_dtype=obs_dtype)
+    src, pos, _ = _descriptors(env, B)
+    states = env.render(src, pos)
+    actor = FusedMLP2Head(env, _conditioned_module(states, H, W, 20 + H + W, activation, "tanh"))
+    value = FusedMLP2Head(env, _conditioned_module(states, H, W, 21 + H + W, activation, "none"))
+    worst = max(_check_against_f64("ppo_actor", actor, env, src, pos),
+                _check_against_f64("ppo_critic", value, env, src, pos),
+                _check_against_f64("sum", actor, env, src, pos),
+                _check_against_f64("sum", value, env, src, pos))
+    print(f"WORST ({H}, {W}, {B}, {activation}) {worst:.3f}")
+
+
+# ------------------------------------------------------------------------------------------------------- window limit
+def _descriptors_of(env):
+    roll = th._rollout(env, th._module(32, env.num_intervals, 2))
+    return roll.obs_src, roll.obs_pos
+
+
+def test_the_largest_window_is_the_largest():
+    from finenvs_amd import _lib
+    from finenvs_amd.mlp2_head import MLP2_MAX_WINDOW, FusedMLP2Head
+
+    assert WMAX == MLP2_MAX_WINDOW[128] == 40
+    assert (_max_window(32), _max_window(64)) == (MLP2_MAX_WINDOW[32], MLP2_MAX_WINDOW[64])
+    env = _env(8, WMAX + 1)
+    m = _module(128, WMAX + 1, 1)
+    with pytest.raises(_lib.FinEnvsNativeError, match="fe_mlp2_forward: .* does not fit"):
+        FusedMLP2Head(env, m)(*_descriptors_of(env))
+    roll = _rollout(env, m)
+    with pytest.raises(_lib.FinEnvsNativeError, match="fe_env_rollout_mlp2_sampled: .* does not fit"):
+        roll.run(1, record_means=True)
+    # the C ABI refuses the backward itself too, before it touches a pointer
+    lib, w, g = env._lib, _lib.FeMlp2Weights(*([16] * 7)), _lib.FeMlp2Grads(*([16] * 6))
+    rc = lib.fe_mlp2_backward(env._handle, 16, C.byref(w), 128, 0, 0, 16, 16, 4, 16, 16, 16, C.byref(g), None)
+    assert rc == _lib.FE_ERR_ARG
+    msg = lib.fe_last_error()
+    assert b"fe_mlp2_backward: W1 (128 x 164)" in msg and b"does not fit" in msg, msg
+    y = FusedMLP2Head(env, _module(64, WMAX + 1, 1))(*_descriptors_of(env))  # H = 64 fits
+    y.sum().backward()
+    assert bool(torch.isfinite(y).all())
+
+
+# ------------------------------------------------------------------------------- determinism and autograd behaviour
+def test_backward_is_deterministic_and_grad_accumulates_as_torchs_does():
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    for H, W, B, act, output in ((32, 4, 1057, "elu", "tanh"), (128, 16, 4097, "relu", "none")):
+        env = _env(1024, W)
+        src, pos, _ = _descriptors(env, B)
+        head = FusedMLP2Head(env, _module(H, W, 4, act, output))
+        gen = torch.Generator(device="cuda").manual_seed(H)
+        up = torch.randn((B, 1), generator=gen, device="cuda")
+
+        def grads(zero=True):
+            if zero:
+                _zero(head.module)
+            (head(src, pos) * up).sum().backward()
+            return [p.grad.clone() for p in _params(head.module)]
+
+        g1, g2 = grads(), grads()
+        for a, b, name in zip(g1, g2, NAMES):
+            assert_bits(a, b, f"two backward calls, {name}")
+            assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0
+        g3 = grads(zero=False)  # .grad accumulates
+        for a, b, name in zip(g3, g1, NAMES):
+            assert_bits(a, b + b, f"accumulated {name}")
+        head.module.zero_grad(set_to_none=False)  # ... into the zeroed buffers, not over them
+        g4 = grads(zero=False)
+        for a, b in zip(g4, g1):
+            assert_bits(a, b)
+        _zero(head.module)
+        (head(src, pos).double() * up.double()).sum().backward()  # an f64 upstream gradient: the bits of its f32 copy
+        for p, b in zip(_params(head.module), g1):
+            assert_bits(p.grad, b)
+
+
+def test_a_pending_backward_after_a_refresh_differentiates_the_weights_its_forward_ran_with():
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    env = _env(64, 4)
+    src, pos, _ = _descriptors(env, 200)
+    head = FusedMLP2Head(env, _module(64, 4, 6))
+    _zero(head.module)
+    head(src, pos).sum().backward()
+    want = [p.grad.clone() for p in _params(head.module)]
+    _zero(head.module)
+    y = head(src, pos)
+    with torch.no_grad():  # an optimizer step and a refresh between the forward and its backward
+        for p in _params(head.module):
+            p.mul_(1.5)
+    head.refresh()
+    y.sum().backward()
+    for p, b, name in zip(_params(head.module), want, NAMES):
+        assert_bits(p.grad, b, name)
+    _zero(head.module)
+    head(src, pos).sum().backward()  # and the new weights give other gradients
+    assert not torch.equal(head.module.network[2].weight.grad, want[2])
+
+
+def test_a_frozen_head_launches_nothing_and_an_empty_batch_works(monkeypatch):
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    env = _env(64, 4)
+    src, pos, _ = _descriptors(env, 64)
+    head = FusedMLP2Head(env, _module(32, 4, 9))
+    calls = []
+    real = env._lib.fe_mlp2_backward
+    monkeypatch.setattr(env._lib, "fe_mlp2_backward", lambda *a: calls.append(1) or real(*a))
+    scale = torch.ones((), device="cuda", requires_grad=True)
+    head.module.requires_grad_(False)
+    y = head(src, pos)
+    assert not y.requires_grad
+    (y * scale).sum().backward()
+    assert calls == [] and all(p.grad is None for p in _params(head.module))
+    head.module.requires_grad_(True)
+    head.module.network[2].weight.requires_grad_(False)  # partly frozen: one launch, the frozen tensor gets nothing
+    head(src, pos).sum().backward()
+    assert calls == [1] and head.module.network[2].weight.grad is None
+    assert all(p.grad is not None for i, p in enumerate(_params(head.module)) if i != 2)
+    # B = 0
+    head.module.requires_grad_(True)
+    _zero(head.module)
+    packs = []
+    real_pack = env._lib.fe_mlp_pack
+    monkeypatch.setattr(env._lib, "fe_mlp_pack", lambda *a: packs.append(1) or real_pack(*a))
+    y = head(src[:0], pos[:0])
+    assert y.shape == (0, 1)
+    y.sum().backward()
+    assert calls == [1] and packs == []
+    for p in _params(head.module):
+        assert p.grad is not None and float(p.grad.abs().max()) == 0.0
+    assert head.rollout.forward(src[:0], pos[:0]).shape == (0, 1)
+
+
+def test_refusals():
+    from finenvs_amd import _lib
+    from finenvs_amd.mlp2_head import FusedMLP2Head, MLP2Head
+    from finenvs_amd.rollout import FusedMLP2Rollout
+
+    env2 = _env(8, 4, A=2)
+    with pytest.raises(ValueError, match="one asset"):
+        FusedMLP2Head(env2, _module(32, 4, 1))
+    lib, w, g = env2._lib, _lib.FeMlp2Weights(*([16] * 7)), _lib.FeMlp2Grads(*([16] * 6))
+    rc = lib.fe_mlp2_backward(env2._handle, 16, C.byref(w), 32, 0, 0, 16, 16, 4, 16, 16, 16, C.byref(g), None)
+    assert rc == _lib.FE_ERR_ARG and b"fe_mlp2_backward: the env has 2 assets" in lib.fe_last_error()
+    rc = lib.fe_mlp2_backward(env2._handle, 16, C.byref(w), 32, 0, 1, 16, 16, 4, 16, 16, 16, C.byref(g), None)
+    assert rc == _lib.FE_ERR_ARG and b"fe_mlp2_backward: out_activation must be 0 (tanh) or 2 (none)" in lib.fe_last_error()
+    rc = lib.fe_mlp2_forward(env2._handle, 16, C.byref(w), 48, 0, 0, 16, 16, 4, 16, None)
+    assert rc == _lib.FE_ERR_ARG and b"fe_mlp2_forward: H must be 32, 64 or 128" in lib.fe_last_error()
+    rc = lib.fe_env_rollout_mlp2_sampled(env2._handle, 16, C.byref(w), 32, 0, 0, 0, 16, 16, None, 0.0, None, None, 16, 16, None,
+                                         None, None)
+    assert rc == _lib.FE_ERR_ARG and b"fe_env_rollout_mlp2_sampled: bad argument" in lib.fe_last_error()
+    env = _env(8, 4)
+    with pytest.raises(ValueError, match="float32 parameters"):
+        FusedMLP2Head(env, _module(32, 4, 1).double())
+    with pytest.raises(ValueError, match="must live on the env's device"):
+        FusedMLP2Head(env, MLP2Head(32, 4))
+    with pytest.raises(ValueError, match="window of 7 rows"):
+        FusedMLP2Head(env, _module(32, 7, 1))
+    with pytest.raises(ValueError, match="two hidden layers"):
+        FusedMLP2Head(env, th._module(32, 4, 1))
+    head = FusedMLP2Head(env, _module(32, 4, 1))
+    with pytest.raises(ValueError, match="one position per descriptor"):
+        head(head.rollout.obs_src, head.rollout.obs_pos[:3])
+    p = [q.detach() for q in _params(_module(32, 4, 1))]
+    with pytest.raises(ValueError, match="output_activation must be one of"):
+        FusedMLP2Rollout(env, p[0].t(), p[1], p[2], p[3], p[4], 0.0, output_activation="sigmoid")
+    with pytest.raises(ValueError, match="W2 must be"):
+        FusedMLP2Rollout(env, p[0].t(), p[1], p[2][:, :16], p[3], p[4], 0.0)
+
+
+# ----------------------------------------------------------------------------------------------------- memory contract
+_window, _bands_intact, SENTINEL = th._window, th._bands_intact, th.SENTINEL
+
+
+@pytest.mark.parametrize("H,W,B,output", [(32, 4, 1, "tanh"), (64, 7, 33, "none"), (128, 16, 1057, "tanh")])
+def test_memory_contract_of_forward_and_backward(H, W, B, output):
+    from finenvs_amd import _lib
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    env = _env(min(B, 512), W)
+    src, pos, _ = _descriptors(env, B)
+    head = FusedMLP2Head(env, _module(H, W, 13, "elu", output))
+    roll, lib = head.rollout, env._lib
+    weights = roll._weights()
+    out_act = roll.out_act
+    big_out, out = _window(B, F32, float("nan"))  # out: exactly B floats
+    _lib.check(lib.fe_mlp2_forward(env._handle, roll._lr32.data_ptr(), C.byref(weights), H, roll.act, out_act, src.data_ptr(),
+                                   pos.data_ptr(), B, out.data_ptr(), env._stream()))
+    _bands_intact(big_out, B, "out")
+    assert_bits(out.reshape(B, 1), roll.forward(src, pos))
+    gen = torch.Generator(device="cuda").manual_seed(B)
+    up = torch.randn((B,), generator=gen, device="cuda")
+    n_ws = int(lib.fe_mlp2_grad_workspace_floats(H, W, B))
+    sizes = {"w1": H * 5 * W, "b1": H, "w2": H * H, "b2": H, "w3": H, "b3": 1}
+    results = []
+    for poison in (float("nan"), SENTINEL):
+        big_ws, ws = _window(n_ws, F32, poison)
+        wins = {k: _window(n, F32, poison) for k, n in sizes.items()}
+        mg = _lib.FeMlp2Grads(*(wins[k][1].data_ptr() for k in NAMES))
+        _lib.check(lib.fe_mlp2_backward(env._handle, roll._lr32.data_ptr(), C.byref(weights), H, roll.act, out_act,
+                                        src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), up.data_ptr(), ws.data_ptr(),
+                                        C.byref(mg), env._stream()))
+        _bands_intact(big_ws, n_ws, "workspace")
+        for k, n in sizes.items():
+            _bands_intact(wins[k][0], n, k)
+            assert bool(torch.isfinite(wins[k][1]).all()), k
+        results.append([wins[k][1].clone() for k in NAMES])
+    for a, b, k in zip(results[0], results[1], NAMES):
+        assert_bits(a, b, f"{k}: NaN-filled against sentinel-filled buffers")
+    _zero(head.module)
+    (head(src, pos).reshape(B) * up).sum().backward()
+    for a, p, k in zip(results[0], _params(head.module), NAMES):
+        assert_bits(a, p.grad.reshape(-1), f"{k} against the front end")
+
+
+def test_memory_contract_of_the_sampled_rollout():
+    from finenvs_amd import _lib
+
+    N, A, W, H, K = 77, 3, 7, 64, 3
+    envs = [_env(N, W, A=A), _env(N, W, A=A)]
+    m = _module(H, W, 17)
+    roll, twin = _rollout(envs[0], m), _rollout(envs[1], m)
+    dev = envs[0]._dev
+    gen = torch.Generator(device=dev).manual_seed(N)
+    noise = torch.randn((K, N, A), generator=gen, device=dev)
+    a_ref, r_ref, d_ref = twin.run(K, noise=noise, std=0.4, record_means=True)
+    nan = float("nan")
+    wins = {"actions": _window(K * N * A, F32, nan), "means": _window(K * N * A, F32, nan),
+            "rewards": _window(K * N, F64, nan), "dones": _window(K * N, I32, -7),
+            "ssrc": _window((K + 1) * N, I64, -7), "spos": _window((K + 1) * N * A, F64, nan)}
+    big_noise, nwin = _window(K * N * A, F32, 0.0)
+    big_noise.fill_(nan)  # a read past the noise reaches an action
+    nwin.copy_(noise.reshape(-1))
+    lib, w = envs[0]._lib, roll._weights()
+    roll._begin_run()
+    _lib.check(lib.fe_env_rollout_mlp2_sampled(
+        envs[0]._handle, roll._lr32.data_ptr(), C.byref(w), H, roll.act, roll.out_act, K, roll.obs_src.data_ptr(),
+        roll.obs_pos.data_ptr(), nwin.data_ptr(), 0.4, wins["actions"][1].data_ptr(), wins["means"][1].data_ptr(),
+        wins["rewards"][1].data_ptr(), wins["dones"][1].data_ptr(), wins["ssrc"][1].data_ptr(), wins["spos"][1].data_ptr(),
+        envs[0]._stream()))
+    roll._end_run()
+    for name, (big, win) in wins.items():
+        _bands_intact(big, win.numel(), name)
+    assert_bits(wins["actions"][1], a_ref.reshape(-1), "actions")
+    assert_bits(wins["means"][1], twin.means.reshape(-1), "means")
+    assert_bits(wins["rewards"][1], r_ref.reshape(-1), "rewards")
+    assert_bits(wins["dones"][1], d_ref.reshape(-1), "dones")
+    assert_bits(wins["ssrc"][1][K * N:], twin.obs_src.reshape(-1), "last descriptor row")
+    assert_bits(wins["spos"][1][K * N * A:], twin.obs_pos.reshape(-1))
+    assert bool((wins["ssrc"][1] >= 0).all()) and bool(torch.isfinite(wins["spos"][1]).all())
+
+
+# ------------------------------------------------------------------------------------------------------------- example
+@pytest.mark.parametrize("fused_optim", [False, True])
+def test_ppo_example_with_two_hidden_layers_trains_without_rendering(monkeypatch, fused_optim):
+    from finenvs_amd import TimeSeriesEnv, mlp2_head
+    from finenvs_amd.trajectory import TrajectoryBuffer
+
+    mod = th._example()
+    heads = []
+
+    class Recording(mlp2_head.FusedMLP2Head):
+        def __init__(self, env, module):
+            super().__init__(env, module)
+            heads.append(self)
+
+    def refuse(self, *a, **k):
+        raise AssertionError("an observation was rendered")
+
+    monkeypatch.setattr(mod, "FusedMLP2Head", Recording)
+    monkeypatch.setattr(TrajectoryBuffer, "minibatch_states", refuse)
+    monkeypatch.setattr(TimeSeriesEnv, "render", refuse)
+    history = mod.main(envs=256, steps=4, iters=2, hidden=32, window=4, fused_update=True, fused_optim=fused_optim, quiet=True,
+                       hidden_layers=2)
+    assert len(history) == 2 and len(heads) == 2
+    for critic_loss, mean_reward, log in history:
+        assert np.isfinite(critic_loss) and np.isfinite(mean_reward)
+    for head, output in zip(heads, ("tanh", "none")):
+        assert head.output_activation == output and mlp2_head.check_mlp2_head(head.module)[0] == 32
+        src, pos = head.rollout.obs_src.clone(), head.rollout.obs_pos.clone()
+        acted = head.rollout.forward(src, pos).clone()  # what the kernel runs after the example's last update
+        y = head(src, pos)  # takes the module's parameters over as they stand
+        assert_bits(acted, y)
+        assert bool(torch.isfinite(y).all())
+        assert_bits(_rollout(head.env, head.module, output).forward(src, pos), acted)
+    torch.manual_seed(0)  # the example's own construction: what the heads started from
+    for head, output in zip(heads, ("tanh", "none")):
+        untrained = mlp2_head.MLP2Head(32, 4, "elu", output, device="cuda:0")
+        for p, q in zip(_params(head.module), _params(untrained)):
+            assert p.shape == q.shape and not torch.equal(p, q)  # all six tensors were trained
+
+
+@pytest.mark.parametrize("kind,output", [("ppo_actor", "tanh"), ("ppo_critic", "none")])
+def test_one_adam_step_agrees_with_an_eager_twin_on_the_rendered_minibatch(kind, output):
+    """The update of examples/ppo_mlp_fused.py at ``hidden_layers=2`` against an eager torch twin doing the same update on
+    the rendered mini-batch: the parameters agree within ``_adam_bound`` of tests/test_mlp_head_gpu.py."""
+    from finenvs_amd.lstm_head import ppo_actor_loss, ppo_critic_loss, torch_ppo_actor_loss, torch_ppo_critic_loss
+    from finenvs_amd.mlp2_head import FusedMLP2Head
+
+    H, W, B = 32, 4, 1024
+    env = _env(256, W, obs_dtype=F32)
+    src, pos, _ = _descriptors(env, B)
+    module = _module(H, W, 31, "elu", output)
+    twin, m64 = copy.deepcopy(module), copy.deepcopy(module).double()
+    head = FusedMLP2Head(env, module)
+    states = env.render(src, pos)
+    kink = _conditions(module, states)
+    assert not bool(kink.any())  # (ELU has no kink anyway; the public loss functions take no mask)
+    if kind == "ppo_actor":
+        log_std, actions, old_logp, adv = tl._ppo_inputs(_Shaped(module), states, 3)
+        ls = [log_std.detach().clone().requires_grad_(True) for _ in range(3)]
+        fused_loss = ppo_actor_loss(head, ls[0], src, pos, actions, old_logp, adv, CLIP, ENT, fused=True)
+        twin_loss = torch_ppo_actor_loss(twin(states.float()), ls[1], actions, old_logp, adv, CLIP, ENT)
+        loss64 = torch_ppo_actor_loss(m64(states.double()), ls[2].double(), actions.double(), old_logp.double(), adv.double(),
+                                      CLIP, ENT)
+    else:
+        gen = torch.Generator(device="cuda").manual_seed(3)
+        with torch.no_grad():
+            returns = module(states.float()) + 0.3 * torch.randn((B, 1), generator=gen, device="cuda")
+        fused_loss = ppo_critic_loss(head, src, pos, returns, fused=True)
+        twin_loss = torch_ppo_critic_loss(twin(states.float()), returns)
+        loss64 = torch_ppo_critic_loss(m64(states.double()), returns.double())
+    before = [p.detach().clone() for p in _params(module)]
+    opts = [torch.optim.Adam(m.parameters(), th.ADAM_LR, eps=th.ADAM_EPS) for m in (module, twin)]
+    for loss, opt in zip((fused_loss, twin_loss), opts):
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+    loss64.backward()
+    for name, pf, pt, pd, p0 in zip(NAMES, _params(module), _params(twin), _params(m64), before):
+        g64 = pd.grad
+        tol = 2e-5 * float(g64.abs().max()) + 4 * float((pt.grad.double() - g64).abs().max())
+        assert float((pf.grad.double() - g64).abs().max()) <= tol, (kind, name)  # the yardstick itself
+        delta = tol + float((pt.grad.double() - g64).abs().max())
+        bound = th._adam_bound(p0, pt.grad, delta)
+        diff = (pf.detach().double() - pt.detach().double()).abs()
+        moved = (pt.detach() - p0).abs()
+        print(f"{kind} {name}: max diff {float(diff.max()):.3e}, max bound {float(bound.max()):.3e}, "
+              f"elements free to flip {int((pt.grad.abs().double() <= delta).sum())} of {pt.numel()}")
+        assert bool((diff <= bound).all()), (kind, name, float((diff - bound).max()))
+        assert float(moved.max()) > 0.5 * th.ADAM_LR  # the step happened
+    head.refresh()
+    assert_bits(head.rollout.forward(src, pos), head(src, pos))
