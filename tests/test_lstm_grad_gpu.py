@@ -73,7 +73,10 @@ def _critic(H, W, seed):
 
 
 def _descriptors(env, B, seed=1):
-    """B observation descriptors of the env's own days (rollout rows, as a trajectory chunk or the ring holds them)."""
+    """B observation descriptors of the env's own days: the first B of the (K + 1) N rows a K-step rollout records.  While
+    ``B <= num_envs`` those are all row 0, the RESET states of a fresh env: ``obs_pos`` is exactly 0.0 and ``obs_src`` one
+    of the table's day starts (at most one distinct sample per day); stepped rows begin at index ``num_envs``.  Positions
+    that are not zero and windows all over the table: tests/test_grad_descriptors_gpu.py."""
     from finenvs_amd.rollout import FusedLSTMRollout
     from finenvs_amd.trajectory import TrajectoryBuffer
 

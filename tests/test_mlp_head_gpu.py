@@ -83,7 +83,10 @@ def _rollout(env, module, output="clamp", activation=None):
 
 
 def _descriptors(env, B, seed=1):
-    """B observation descriptors of the env's own days: the K + 1 rows of a sampled MLP rollout's trajectory chunk."""
+    """B observation descriptors of the env's own days: the first B of the (K + 1) N rows of a sampled MLP rollout's
+    trajectory chunk.  While ``B <= num_envs`` those are all row 0, the RESET states of a fresh env: ``obs_pos`` is exactly
+    0.0 and ``obs_src`` one of the table's day starts (at most one distinct sample per day); stepped rows begin at index
+    ``num_envs``.  Positions that are not zero and windows all over the table: tests/test_grad_descriptors_gpu.py."""
     from finenvs_amd.trajectory import TrajectoryBuffer
 
     N = env.num_envs

@@ -72,7 +72,10 @@ def _critic(H, W, seed):
 
 
 def _descriptors(env, B, seed=1):
-    """B observation descriptors of the env's own days (SAC rollout rows, as the replay ring would hold them)."""
+    """B observation descriptors of the env's own days: the first B of the (K + 1) N rows a K-step SAC rollout records.
+    While ``B <= num_envs`` those are all row 0, the RESET states of a fresh env: ``obs_pos`` is exactly 0.0 and ``obs_src``
+    one of the table's day starts (at most one distinct sample per day); stepped rows begin at index ``num_envs``.
+    Positions that are not zero and windows all over the table: tests/test_grad_descriptors_gpu.py."""
     from finenvs_amd.sac import FusedSACRollout, SACActorLSTM
     from finenvs_amd.trajectory import TrajectoryBuffer
 
