@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .replay import as_draw
-from .rollout import lstm_fragment_major, lstm_pack, lstm_row_order_on
+from .rollout import log_return_f32, lstm_fragment_major, lstm_pack, lstm_row_order_on
 
 CRITIC_HIDDEN_SIZES = (32, 64, 128)
 CRITIC_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
@@ -232,9 +232,7 @@ class FusedTwinCritic:
         self.weights = weights
         if weights is not None:
             weights.packed(critic_1), weights.packed(critic_2)  # ValueError if a critic is not registered with it
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
+        self._lr32 = log_return_f32(env)
         self.last: Dict[str, torch.Tensor] = {}
 
     def _check_devices(self) -> None:

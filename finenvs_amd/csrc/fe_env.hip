@@ -139,6 +139,20 @@ auto with_bool(bool b, F &&f) {
     return b ? f(std::true_type{}) : f(std::false_type{});
 }
 
+// with_nt calls f(std::integral_constant<int, NT>) for the kernels' NT template argument, NT = H / 32 row tiles at
+// H = 32 / 64 / 128 (the caller has refused every other H); with_nt<64, 4> serves the streamed kernels, NT = H / 64 at
+// H = 256 / 512 / 1024.  The three-argument form composes it with with_bool for kernel<SINGLE, NT>: f(S, NT).
+template <int UNIT = 32, int NT0 = 1, class F>
+auto with_nt(int32_t H, F &&f) {
+    return H == NT0 * UNIT ? f(std::integral_constant<int, NT0>{})
+                           : (H == 2 * NT0 * UNIT ? f(std::integral_constant<int, 2 * NT0>{}) : f(std::integral_constant<int, 4 * NT0>{}));
+}
+
+template <int UNIT = 32, int NT0 = 1, class F>
+auto with_nt(bool single, int32_t H, F &&f) {
+    return with_bool(single, [&](auto S) { return with_nt<UNIT, NT0>(H, [&](auto NT) { return f(S, NT); }); });
+}
+
 template <class F>
 auto with_layout(bool f32, int vec, F &&f) {
     using V1 = std::integral_constant<int, 1>;
@@ -156,10 +170,10 @@ int launched(const char *who, hipError_t he) {
 int launched(const char *who) { return launched(who, hipGetLastError()); }
 
 // ... of stage `what` of entry `who`: reported as "<who>: <what> launch: <HIP error>"
-int launched(const char *who, const char *what) {
+int launched(const char *who, const char *what, hipError_t he = hipGetLastError()) {
     char step[96];
     snprintf(step, sizeof(step), "%s: %s", who, what);
-    return launched(step);
+    return launched(step, he);
 }
 
 }  // namespace
@@ -836,13 +850,25 @@ int fe_env_rollout_table(fe_env *env, const double *table, const double *wsum, d
     return launched("fe_env_rollout_table");
 }
 
+// The hidden sizes the MLP kernels are instantiated for (with_nt).
+static bool mlp_h_ok(int32_t H) { return H == 32 || H == 64 || H == 128; }
+
+// What every MLP entry refuses about the network's shape, in `who`'s name.
+static int mlp_shape_checked(int32_t H, int32_t activation, const char *who) {
+    if (!mlp_h_ok(H)) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
+    return FE_OK;
+}
+
+// The MLP rollouts' default tile: 128 (env, asset) pairs per workgroup, an env's sleeves kept together.
+static int64_t mlp_tile_envs(const Params &p) { return 128 / p.A > 1 ? 128 / p.A : 1; }
+
 int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, const float *wpos, const float *b1,
                        const float *w2, float b2, int32_t H, int32_t activation, int32_t K, int64_t *obs_src,
                        double *obs_pos, float *actions_out, double *rewards_out, int32_t *dones_out, void *stream) {
     if (!env || !logret_f32 || !w1t || !wpos || !b1 || !w2 || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_mlp: bad argument");
-    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "fe_env_rollout_mlp: H must be 32, 64 or 128 (got %d)", (int)H);
-    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "fe_env_rollout_mlp: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)");
+    if (int rc = mlp_shape_checked(H, activation, "fe_env_rollout_mlp")) return rc;
     if (int rc = require_bound(env, "fe_env_rollout_mlp")) return rc;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
@@ -854,43 +880,101 @@ int fe_env_rollout_mlp(fe_env *env, const float *logret_f32, const float *w1t, c
     // (A 512-thread form running policy and accounting of two sub-tiles in antiphase was tried and dropped: on
     // gfx950 the f32-input MFMA executes on the vector ALUs -- SQ_VALU_MFMA_COEXEC_CYCLES = 0 -- so there is
     // nothing for the accounting to hide behind; profiles/r02_microbench/mlp_prof.txt.)
-    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
+    const int64_t grid = rollout_geometry(env, p, mlp_tile_envs(p), /*replace=*/true);
     const size_t lds = mlp_lds_bytes(p.EB, p.A, p.W, H);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_rollout_mlp_kernel<single, 1>
-                       : (H == 64 ? (const void *)fe_rollout_mlp_kernel<single, 2> : (const void *)fe_rollout_mlp_kernel<single, 4>);
-    });
+    const void *kern = with_nt(p.A == 1, H, [](auto S, auto NT) { return (const void *)fe_rollout_mlp_kernel<decltype(S)::value, decltype(NT)::value>; });
     if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "fe_env_rollout_mlp: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", (int)H, 4 * p.W, lds);
     return launch_big_lds(env->device, kern, grid, lds, p, r, stream, "fe_env_rollout_mlp");
 }
 
-// ---- include/finenvs_amd_mlp_head.h: the MLP head trained on descriptors ----
-// The checks every entry shares; `who` names it.  W1^T must fit the LDS next to the rollout's default tile, whichever
-// kernel runs: one rule for acting, values and gradients.
-static int mlp_head_checked(const fe_env *env, const float *logret_f32, const fe_mlp_weights *w, int32_t H, int32_t activation,
+// ---- include/finenvs_amd_mlp_head.h and include/finenvs_amd_mlp2_head.h: the MLP heads trained on descriptors ----
+// Either head's weights as the shared code sees them: the first layer, the second hidden layer if there is one, the output
+// layer (fe_mlp_weights' w2 / b2, fe_mlp2_weights' w3 / b3).  `given`: the caller's struct and every pointer in it.
+struct MlpHeadView {
+    const float *w1t, *wpos, *b1;
+    const float *w2h, *b2h;  // (H, H), (H): the second hidden layer; null in the one-layer head
+    const float *wout, *bout;
+    bool deep, given;
+};
+
+static MlpHeadView mlp_view(const fe_mlp_weights *w) {
+    if (!w) return {};
+    return {w->w1t, w->wpos, w->b1, nullptr, nullptr, w->w2, w->b2, false, w->w1t && w->wpos && w->b1 && w->w2 && w->b2};
+}
+
+static MlpHeadView mlp_view(const fe_mlp2_weights *w) {
+    if (!w) return {};
+    return {w->w1t, w->wpos, w->b1, w->w2, w->b2, w->w3, w->b3, true,
+            w->w1t && w->wpos && w->b1 && w->w2 && w->b2 && w->w3 && w->b3};
+}
+
+// The checks every entry shares; `who` names it.
+static int mlp_head_checked(const fe_env *env, const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t activation,
                             int32_t out_activation, const char *who) {
-    if (!env || !logret_f32 || !w || !w->w1t || !w->wpos || !w->b1 || !w->w2 || !w->b2)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
-    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
+    if (!env || !logret_f32 || !w.given) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_shape_checked(H, activation, who)) return rc;
     if (out_activation < 0 || out_activation > 2)
         return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh), 1 (clamp) or 2 (none)", who);
     return FE_OK;
 }
 
-static int mlp_head_fits(const fe_env *env, int32_t H, const char *who) {
+// One rule for acting, values and gradients, whichever kernel runs: the weight image (W1^T, and the padded W2 of the
+// deeper head) fits the LDS next to the rollout's tile of `eb` envs.
+static size_t mlp_head_lds_bytes(const MlpHeadView &w, int64_t eb, const Params &p, int32_t H) {
+    return w.deep ? mlp2_lds_bytes((int)eb, p.A, p.W, H) : mlp_lds_bytes((int)eb, p.A, p.W, H);
+}
+
+static int mlp_head_fits(const fe_env *env, const MlpHeadView &w, int32_t H, const char *who) {
     const Params &p = env->p;
-    const size_t lds = mlp_lds_bytes(128 / p.A > 1 ? 128 / p.A : 1, p.A, p.W, H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", who, (int)H, 4 * p.W, lds);
-    return FE_OK;
+    const size_t lds = mlp_head_lds_bytes(w, mlp_tile_envs(p), p, H);
+    if (lds <= kMaxLds) return FE_OK;
+    if (w.deep)
+        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) and W2 (%d x %d) do not fit the 160 KiB LDS: the window does not fit (%zu bytes "
+                    "needed)", who, (int)H, 4 * p.W, (int)H, (int)H, lds);
+    return fail(FE_ERR_ARG, "%s: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", who, (int)H, 4 * p.W, lds);
+}
+
+// LDS of the kernels that hold only the weight image (forward, backward)
+static size_t mlp_head_image_bytes(const MlpHeadView &w, int W, int32_t H) {
+    return w.deep ? mlp2_weight_lds_bytes(W, H) : mlp_head_weight_lds_bytes(W, H);
+}
+
+// The argument block of either head's rollout and forward kernels: a one-layer kernel takes the leading MlpHeadArgs.
+static Mlp2HeadArgs mlp_head_args(const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t activation,
+                                  int32_t out_activation) {
+    Mlp2HeadArgs r;
+    memset(&r, 0, sizeof(r));
+    r.h.lr32 = logret_f32; r.h.w1t = w.w1t; r.h.wpos = w.wpos; r.h.b1 = w.b1; r.h.w2 = w.wout; r.h.b2 = w.bout;
+    r.h.H = H; r.h.act = activation; r.h.out_act = out_activation; r.h.K = 1;
+    r.w2h = w.w2h; r.b2h = w.b2h;
+    return r;
+}
+
+// Either head's kernels at (A == 1, H): the sampled rollout, the forward, the backward's first launch and the layer-1
+// weight gradient both backward passes end with.  Named here and in this order on purpose: the device code object lists
+// its template instantiations as the host code first names them, and that object stays byte for byte what it was.
+struct MlpHeadKernels { const void *sampled, *forward, *grad, *wgrad; };
+
+static MlpHeadKernels mlp_head_kernels(bool deep, bool single, int32_t H) {
+    MlpHeadKernels k;
+    if (!deep) {
+        k.sampled = with_nt(single, H, [](auto S, auto NT) { return (const void *)fe_rollout_mlp_sampled_kernel<decltype(S)::value, decltype(NT)::value>; });
+        k.forward = with_nt(single, H, [](auto S, auto NT) { return (const void *)fe_mlp_forward_kernel<decltype(S)::value, decltype(NT)::value>; });
+        k.grad = with_nt(H, [](auto NT) { return (const void *)fe_mlp_grad_kernel<decltype(NT)::value>; });
+    }
+    k.wgrad = with_nt(H, [](auto NT) { return (const void *)fe_mlp_wgrad_kernel<decltype(NT)::value>; });
+    if (deep) {
+        k.sampled = with_nt(single, H, [](auto S, auto NT) { return (const void *)fe_rollout_mlp2_sampled_kernel<decltype(S)::value, decltype(NT)::value>; });
+        k.forward = with_nt(single, H, [](auto S, auto NT) { return (const void *)fe_mlp2_forward_kernel<decltype(S)::value, decltype(NT)::value>; });
+        k.grad = with_nt(H, [](auto NT) { return (const void *)fe_mlp2_grad_kernel<decltype(NT)::value>; });
+    }
+    return k;
 }
 
 int fe_mlp_pack(const float *weight1, int32_t H, int32_t W, float *w1t, float *wpos, void *stream) {
     if (!weight1 || !w1t || !wpos) return fail(FE_ERR_ARG, "fe_mlp_pack: bad argument");
-    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "fe_mlp_pack: H must be 32, 64 or 128 (got %d)", (int)H);
+    if (!mlp_h_ok(H)) return fail(FE_ERR_ARG, "fe_mlp_pack: H must be 32, 64 or 128 (got %d)", (int)H);
     if (W < 1) return fail(FE_ERR_ARG, "fe_mlp_pack: W must be >= 1 (got %d)", (int)W);
     DeviceGuard guard(device_of(weight1));
     if (int rc = guard.status()) return rc;
@@ -899,75 +983,162 @@ int fe_mlp_pack(const float *weight1, int32_t H, int32_t W, float *w1t, float *w
     return launched("fe_mlp_pack");
 }
 
-int fe_env_rollout_mlp_sampled(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H,
-                               int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
-                               const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
-                               int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
-    static const char *who = "fe_env_rollout_mlp_sampled";
+// fe_env_rollout_mlp_sampled and fe_env_rollout_mlp2_sampled
+static int rollout_mlp_sampled_impl(fe_env *env, const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t activation,
+                                    int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
+                                    float std, float *actions_out, float *means_out, double *rewards_out, int32_t *dones_out,
+                                    int64_t *states_src_out, double *states_pos_out, void *stream, const char *who) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
     if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "%s: std must be >= 0 when noise is given", who);
     if (!obs_src || !obs_pos || !rewards_out || !dones_out || K < 1) return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
+    if (int rc = mlp_head_checked(env, logret_f32, w, H, activation, out_activation, who)) return rc;
     if (int rc = require_bound(env, who)) return rc;
-    if (int rc = mlp_head_fits(env, H, who)) return rc;
+    if (int rc = mlp_head_fits(env, w, H, who)) return rc;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     Params p = env->p;
-    MlpHeadArgs r;
-    memset(&r, 0, sizeof(r));
-    r.lr32 = logret_f32; r.w1t = weights->w1t; r.wpos = weights->wpos; r.b1 = weights->b1; r.w2 = weights->w2; r.b2 = weights->b2;
-    r.H = H; r.act = activation; r.out_act = out_activation; r.K = K; r.obs_src = obs_src; r.obs_pos = obs_pos;
-    r.noise = noise; r.std = std; r.actions_out = actions_out; r.means_out = means_out; r.rew_out = rewards_out;
-    r.done_out = dones_out; r.traj_src = states_src_out; r.traj_pos = states_pos_out;
+    Mlp2HeadArgs r = mlp_head_args(logret_f32, w, H, activation, out_activation);
+    r.h.K = K; r.h.obs_src = obs_src; r.h.obs_pos = obs_pos;
+    r.h.noise = noise; r.h.std = std; r.h.actions_out = actions_out; r.h.means_out = means_out; r.h.rew_out = rewards_out;
+    r.h.done_out = dones_out; r.h.traj_src = states_src_out; r.h.traj_pos = states_pos_out;
     // the geometry of fe_env_rollout_mlp: 128 pairs per workgroup, one 32-pair column block per wavefront
-    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
-    const size_t lds = mlp_lds_bytes(p.EB, p.A, p.W, H);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_rollout_mlp_sampled_kernel<single, 1>
-                       : (H == 64 ? (const void *)fe_rollout_mlp_sampled_kernel<single, 2>
-                                  : (const void *)fe_rollout_mlp_sampled_kernel<single, 4>);
-    });
-    if (lds > kMaxLds)  // (a tile override larger than the default)
+    const int64_t grid = rollout_geometry(env, p, mlp_tile_envs(p), /*replace=*/true);
+    const size_t lds = mlp_head_lds_bytes(w, p.EB, p, H);
+    const void *kern = mlp_head_kernels(w.deep, p.A == 1, H).sampled;
+    if (lds > kMaxLds) {  // (a tile override larger than the default)
+        if (w.deep) return fail(FE_ERR_ARG, "%s: the weight image does not fit the 160 KiB LDS at this tile (%zu bytes needed)", who, lds);
         return fail(FE_ERR_ARG, "%s: W1 (%d x %d) does not fit the 160 KiB LDS (%zu bytes needed)", who, (int)H, 4 * p.W, lds);
+    }
     return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+}
+
+int fe_env_rollout_mlp_sampled(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H,
+                               int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                               const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                               int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    return rollout_mlp_sampled_impl(env, logret_f32, mlp_view(weights), H, activation, out_activation, K, obs_src, obs_pos, noise,
+                                    std, actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream,
+                                    "fe_env_rollout_mlp_sampled");
+}
+
+int fe_env_rollout_mlp2_sampled(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H,
+                                int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
+                                const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
+                                int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
+    return rollout_mlp_sampled_impl(env, logret_f32, mlp_view(weights), H, activation, out_activation, K, obs_src, obs_pos, noise,
+                                    std, actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream,
+                                    "fe_env_rollout_mlp2_sampled");
+}
+
+// fe_mlp_forward and fe_mlp2_forward
+static int mlp_forward_impl(fe_env *env, const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t activation,
+                            int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
+                            void *stream, const char *who) {
+    if (!obs_src || !obs_pos || !out || count < 0) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_head_checked(env, logret_f32, w, H, activation, out_activation, who)) return rc;
+    if (int rc = mlp_head_fits(env, w, H, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    Params p = env->p;
+    Mlp2HeadArgs r = mlp_head_args(logret_f32, w, H, activation, out_activation);
+    r.h.obs_src = const_cast<int64_t *>(obs_src); r.h.obs_pos = const_cast<double *>(obs_pos);  // read only in this kernel
+    r.h.actions_out = out; r.h.count = count;
+    const int64_t blocks = (count * p.A + 31) / 32;
+    const int64_t grid = capped_grid((blocks + kBlock / 64 - 1) / (kBlock / 64));
+    const void *kern = mlp_head_kernels(w.deep, p.A == 1, H).forward;
+    return launch_big_lds(env->device, kern, grid, mlp_head_image_bytes(w, p.W, H), p, r, stream, who);
 }
 
 int fe_mlp_forward(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H, int32_t activation,
                    int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
                    void *stream) {
-    static const char *who = "fe_mlp_forward";
-    if (!obs_src || !obs_pos || !out || count < 0) return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
-    if (int rc = mlp_head_fits(env, H, who)) return rc;
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    Params p = env->p;
-    MlpHeadArgs r;
-    memset(&r, 0, sizeof(r));
-    r.lr32 = logret_f32; r.w1t = weights->w1t; r.wpos = weights->wpos; r.b1 = weights->b1; r.w2 = weights->w2; r.b2 = weights->b2;
-    r.H = H; r.act = activation; r.out_act = out_activation; r.K = 1;
-    r.obs_src = const_cast<int64_t *>(obs_src); r.obs_pos = const_cast<double *>(obs_pos);  // read only in this kernel
-    r.actions_out = out; r.count = count;
-    const int64_t blocks = (count * p.A + 31) / 32;
-    const int64_t grid = capped_grid((blocks + kBlock / 64 - 1) / (kBlock / 64));
-    const size_t lds = mlp_head_weight_lds_bytes(p.W, H);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_mlp_forward_kernel<single, 1>
-                       : (H == 64 ? (const void *)fe_mlp_forward_kernel<single, 2> : (const void *)fe_mlp_forward_kernel<single, 4>);
-    });
-    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
+    return mlp_forward_impl(env, logret_f32, mlp_view(weights), H, activation, out_activation, obs_src, obs_pos, count, out, stream,
+                            "fe_mlp_forward");
 }
 
-// Workspace: [dpre (32 blocks, H)][partial products (splits, H, F)][d w2 / d b2 partials (waves, H + 4)].
-int64_t fe_mlp_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    if (count == 0) return 0;
-    const int64_t blocks = (count + 31) / 32, splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
-    return 32 * blocks * H + splits * H * mlp_grad_fp(W) + 4 * mlp_grad_groups(blocks) * (H + 4);
+int fe_mlp2_forward(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H, int32_t activation,
+                    int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
+                    void *stream) {
+    return mlp_forward_impl(env, logret_f32, mlp_view(weights), H, activation, out_activation, obs_src, obs_pos, count, out, stream,
+                            "fe_mlp2_forward");
+}
+
+// The backward passes' workspace, in floats from its start, for either depth (a1, dz2 and part2 are the deeper head's):
+// [dpre = dz1 (32 blocks, H)][a1][dz2][layer-1 partials (splits, H, FP)][[dW2 | d b2] partials (splits, H, H + 32)]
+// [output-layer partials (waves, H + 4)].  The exported sizes and the carve-up both read it.
+struct MlpGradLayout {
+    int64_t blocks, splits, groups;
+    int32_t FP;
+    int64_t a1, dz2, part, part2, wpart, total;
+};
+
+static MlpGradLayout mlp_grad_layout(bool deep, int32_t H, int32_t W, int64_t count) {
+    MlpGradLayout l;
+    l.blocks = (count + 31) / 32;
+    l.splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
+    l.groups = mlp_grad_groups(l.blocks);
+    l.FP = mlp_grad_fp(W);
+    const int64_t rows = 32 * l.blocks * H;
+    l.a1 = rows;
+    l.dz2 = 2 * rows;
+    l.part = deep ? 3 * rows : rows;
+    l.part2 = l.part + l.splits * H * l.FP;
+    l.wpart = l.part2 + (deep ? l.splits * H * (H + 32) : 0);
+    l.total = l.wpart + 4 * l.groups * (H + 4);
+    return l;
+}
+
+static int64_t mlp_grad_workspace_floats(bool deep, int32_t H, int32_t W, int64_t count) {
+    if (!mlp_h_ok(H) || W < 1 || count < 0) return -1;
+    return count == 0 ? 0 : mlp_grad_layout(deep, H, W, count).total;
+}
+
+int64_t fe_mlp_grad_workspace_floats(int32_t H, int32_t W, int64_t count) { return mlp_grad_workspace_floats(false, H, W, count); }
+
+int64_t fe_mlp2_grad_workspace_floats(int32_t H, int32_t W, int64_t count) { return mlp_grad_workspace_floats(true, H, W, count); }
+
+// What both backward entries refuse, in this order.  `given`: the entry's own pointers and its gradient struct are there.
+static int mlp_backward_checked(const fe_env *env, const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t activation,
+                                int32_t out_activation, bool given, const float *outputs, const char *who) {
+    if (!given) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = mlp_head_checked(env, logret_f32, w, H, activation, out_activation, who)) return rc;
+    if (out_activation == 1)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on", who);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values %s returned", who,
+                    w.deep ? "fe_mlp2_forward" : "fe_mlp_forward");
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused LSTM "
+                    "head does)", who, (int)env->p.A);
+    return mlp_head_fits(env, w, H, who);
+}
+
+// The arguments of the layer-1 and output-layer kernels; g_wout / g_bout: the output layer's gradients.
+static MlpGradArgs mlp_grad_args(const float *logret_f32, const MlpHeadView &w, int32_t H, int32_t W, int32_t activation,
+                                 int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                                 const float *outputs, const float *d_outputs, float *workspace, const MlpGradLayout &l,
+                                 float *g_w1, float *g_b1, float *g_wout, float *g_bout) {
+    MlpGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.w1t = w.w1t; g.wpos = w.wpos; g.b1 = w.b1; g.w2 = w.wout;
+    g.obs_src = obs_src; g.obs_pos = obs_pos; g.outputs = outputs; g.d_outputs = d_outputs;
+    g.count = count; g.blocks = l.blocks; g.splits = l.splits; g.waves = 4 * l.groups;
+    g.W = W; g.H = H; g.act = activation; g.out_act = out_activation; g.FP = l.FP;
+    g.dpre = workspace; g.part = workspace + l.part; g.wpart = workspace + l.wpart;
+    g.g_w1 = g_w1; g.g_b1 = g_b1; g.g_w2 = g_wout; g.g_b2 = g_bout;
+    return g;
+}
+
+// The first layer's weight gradient (`kern`, its step named `wgrad_step`) and the reduction of layer 1 and the output layer.
+static int mlp_backward_layer1(MlpGradArgs &g, const void *kern, const char *who, const char *wgrad_step, hipStream_t st) {
+    void *args[] = {&g};
+    const int64_t items = g.splits * (g.FP / 32);
+    const int64_t grid = capped_grid((items + kBlock / 64 - 1) / (kBlock / 64));
+    if (int rc = launched(who, wgrad_step, hipLaunchKernel(kern, dim3((unsigned)grid), dim3(kBlock), args, 0, st))) return rc;
+    hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)g.H * (4 * g.W + 2) + g.H + 1)), dim3(kBlock), 0, st, g);
+    return launched(who, "reduction");
 }
 
 int fe_mlp_backward(fe_env *env, const float *logret_f32, const fe_mlp_weights *weights, int32_t H, int32_t activation,
@@ -975,149 +1146,24 @@ int fe_mlp_backward(fe_env *env, const float *logret_f32, const fe_mlp_weights *
                     const float *outputs, const float *d_outputs, float *workspace, const fe_mlp_grads *grads,
                     void *stream) {
     static const char *who = "fe_mlp_backward";
-    if (!obs_src || !obs_pos || count < 0 || !d_outputs || !workspace || !grads || !grads->w1 || !grads->b1 || !grads->w2 ||
-        !grads->b2)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
-    if (out_activation == 1)
-        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on", who);
-    if (out_activation == 0 && !outputs)
-        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_mlp_forward returned", who);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused LSTM "
-                    "head does)", who, (int)env->p.A);
-    if (int rc = mlp_head_fits(env, H, who)) return rc;
+    const MlpHeadView w = mlp_view(weights);
+    const bool given = obs_src && obs_pos && count >= 0 && d_outputs && workspace && grads && grads->w1 && grads->b1 &&
+                       grads->w2 && grads->b2;
+    if (int rc = mlp_backward_checked(env, logret_f32, w, H, activation, out_activation, given, outputs, who)) return rc;
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
-    MlpGradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.lr32 = logret_f32; g.w1t = weights->w1t; g.wpos = weights->wpos; g.b1 = weights->b1; g.w2 = weights->w2;
-    g.obs_src = obs_src; g.obs_pos = obs_pos; g.outputs = outputs; g.d_outputs = d_outputs;
-    g.count = count; g.blocks = (count + 31) / 32; g.splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
-    const int64_t groups = mlp_grad_groups(g.blocks);
-    g.waves = 4 * groups;
-    g.W = W; g.H = H; g.act = activation; g.out_act = out_activation; g.FP = mlp_grad_fp(W);
-    g.dpre = workspace;
-    g.part = g.dpre + 32 * g.blocks * H;
-    g.wpart = g.part + g.splits * H * g.FP;
-    g.g_w1 = grads->w1; g.g_b1 = grads->b1; g.g_w2 = grads->w2; g.g_b2 = grads->b2;
+    const MlpGradLayout l = mlp_grad_layout(false, H, W, count);
+    MlpGradArgs g = mlp_grad_args(logret_f32, w, H, W, activation, out_activation, obs_src, obs_pos, count, outputs, d_outputs,
+                                  workspace, l, grads->w1, grads->b1, grads->w2, grads->b2);
     void *args[] = {&g};
     const hipStream_t st = (hipStream_t)stream;
-    const void *k1 = H == 32 ? (const void *)fe_mlp_grad_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp_grad_kernel<2> : (const void *)fe_mlp_grad_kernel<4>);
-    const size_t lds = mlp_head_weight_lds_bytes(W, H);
-    if (int rc = prepare_big_lds(env->device, k1, lds, who)) return rc;
-    if (int rc = launched("fe_mlp_backward: first layer", hipLaunchKernel(k1, dim3((unsigned)groups), dim3(kBlock), args, lds, st)))
-        return rc;
-    const void *k2 = H == 32 ? (const void *)fe_mlp_wgrad_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp_wgrad_kernel<2> : (const void *)fe_mlp_wgrad_kernel<4>);
-    const int64_t items = g.splits * (g.FP / 32);
-    const int64_t grid2 = capped_grid((items + kBlock / 64 - 1) / (kBlock / 64));
-    if (int rc = launched("fe_mlp_backward: weight gradient", hipLaunchKernel(k2, dim3((unsigned)grid2), dim3(kBlock), args, 0, st)))
-        return rc;
-    hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)H * (4 * W + 2) + H + 1)), dim3(kBlock), 0, st, g);
-    return launched("fe_mlp_backward: reduction");
-}
-
-// ---- include/finenvs_amd_mlp2_head.h: the two-hidden-layer MLP head ----
-static int mlp2_head_checked(const fe_env *env, const float *logret_f32, const fe_mlp2_weights *w, int32_t H, int32_t activation,
-                             int32_t out_activation, const char *who) {
-    if (!env || !logret_f32 || !w || !w->w1t || !w->wpos || !w->b1 || !w->w2 || !w->b2 || !w->w3 || !w->b3)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (H != 32 && H != 64 && H != 128) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
-    if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
-    if (out_activation < 0 || out_activation > 2)
-        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh), 1 (clamp) or 2 (none)", who);
-    return FE_OK;
-}
-
-// One rule for acting, values and gradients: W1^T and the padded W2 fit the LDS next to the rollout's default tile.
-static int mlp2_head_fits(const fe_env *env, int32_t H, const char *who) {
-    const Params &p = env->p;
-    const size_t lds = mlp2_lds_bytes(128 / p.A > 1 ? 128 / p.A : 1, p.A, p.W, H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: W1 (%d x %d) and W2 (%d x %d) do not fit the 160 KiB LDS: the window does not fit (%zu bytes "
-                    "needed)", who, (int)H, 4 * p.W, (int)H, (int)H, lds);
-    return FE_OK;
-}
-
-static Mlp2HeadArgs mlp2_head_args(const float *logret_f32, const fe_mlp2_weights *w, int32_t H, int32_t activation,
-                                   int32_t out_activation) {
-    Mlp2HeadArgs r;
-    memset(&r, 0, sizeof(r));
-    r.h.lr32 = logret_f32; r.h.w1t = w->w1t; r.h.wpos = w->wpos; r.h.b1 = w->b1; r.h.w2 = w->w3; r.h.b2 = w->b3;
-    r.h.H = H; r.h.act = activation; r.h.out_act = out_activation; r.h.K = 1;
-    r.w2h = w->w2; r.b2h = w->b2;
-    return r;
-}
-
-int fe_env_rollout_mlp2_sampled(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H,
-                                int32_t activation, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
-                                const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
-                                int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
-    static const char *who = "fe_env_rollout_mlp2_sampled";
-    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
-    if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "%s: std must be >= 0 when noise is given", who);
-    if (!obs_src || !obs_pos || !rewards_out || !dones_out || K < 1) return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
-    if (int rc = require_bound(env, who)) return rc;
-    if (int rc = mlp2_head_fits(env, H, who)) return rc;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    Params p = env->p;
-    Mlp2HeadArgs r = mlp2_head_args(logret_f32, weights, H, activation, out_activation);
-    r.h.K = K; r.h.obs_src = obs_src; r.h.obs_pos = obs_pos;
-    r.h.noise = noise; r.h.std = std; r.h.actions_out = actions_out; r.h.means_out = means_out; r.h.rew_out = rewards_out;
-    r.h.done_out = dones_out; r.h.traj_src = states_src_out; r.h.traj_pos = states_pos_out;
-    // the geometry of fe_env_rollout_mlp: 128 pairs per workgroup, one 32-pair column block per wavefront
-    const int64_t grid = rollout_geometry(env, p, 128 / p.A > 1 ? 128 / p.A : 1, /*replace=*/true);
-    const size_t lds = mlp2_lds_bytes(p.EB, p.A, p.W, H);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_rollout_mlp2_sampled_kernel<single, 1>
-                       : (H == 64 ? (const void *)fe_rollout_mlp2_sampled_kernel<single, 2>
-                                  : (const void *)fe_rollout_mlp2_sampled_kernel<single, 4>);
-    });
-    if (lds > kMaxLds)  // (a tile override larger than the default)
-        return fail(FE_ERR_ARG, "%s: the weight image does not fit the 160 KiB LDS at this tile (%zu bytes needed)", who, lds);
-    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
-}
-
-int fe_mlp2_forward(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H, int32_t activation,
-                    int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count, float *out,
-                    void *stream) {
-    static const char *who = "fe_mlp2_forward";
-    if (!obs_src || !obs_pos || !out || count < 0) return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
-    if (int rc = mlp2_head_fits(env, H, who)) return rc;
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    Params p = env->p;
-    Mlp2HeadArgs r = mlp2_head_args(logret_f32, weights, H, activation, out_activation);
-    r.h.obs_src = const_cast<int64_t *>(obs_src); r.h.obs_pos = const_cast<double *>(obs_pos);  // read only in this kernel
-    r.h.actions_out = out; r.h.count = count;
-    const int64_t blocks = (count * p.A + 31) / 32;
-    const int64_t grid = capped_grid((blocks + kBlock / 64 - 1) / (kBlock / 64));
-    const size_t lds = mlp2_weight_lds_bytes(p.W, H);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_mlp2_forward_kernel<single, 1>
-                       : (H == 64 ? (const void *)fe_mlp2_forward_kernel<single, 2> : (const void *)fe_mlp2_forward_kernel<single, 4>);
-    });
-    return launch_big_lds(env->device, kern, grid, lds, p, r, stream, who);
-}
-
-// Workspace: [dz1 (32 blocks, H)][a1][dz2][layer-1 partials (splits, H, F)][[dW2 | d b2] partials (splits, H, H + 32)]
-// [d w3 / d b3 partials (waves, H + 4)].
-int64_t fe_mlp2_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    if (count == 0) return 0;
-    const int64_t blocks = (count + 31) / 32, splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
-    return 3 * 32 * blocks * H + splits * H * (mlp_grad_fp(W) + H + 32) + 4 * mlp_grad_groups(blocks) * (H + 4);
+    const MlpHeadKernels k = mlp_head_kernels(false, true, H);
+    const size_t lds = mlp_head_image_bytes(w, W, H);
+    if (int rc = prepare_big_lds(env->device, k.grad, lds, who)) return rc;
+    if (int rc = launched(who, "first layer", hipLaunchKernel(k.grad, dim3((unsigned)l.groups), dim3(kBlock), args, lds, st))) return rc;
+    return mlp_backward_layer1(g, k.wgrad, who, "weight gradient", st);
 }
 
 int fe_mlp2_backward(fe_env *env, const float *logret_f32, const fe_mlp2_weights *weights, int32_t H, int32_t activation,
@@ -1125,77 +1171,44 @@ int fe_mlp2_backward(fe_env *env, const float *logret_f32, const fe_mlp2_weights
                      const float *outputs, const float *d_outputs, float *workspace, const fe_mlp2_grads *grads,
                      void *stream) {
     static const char *who = "fe_mlp2_backward";
-    if (!obs_src || !obs_pos || count < 0 || !d_outputs || !workspace || !grads || !grads->w1 || !grads->b1 || !grads->w2 ||
-        !grads->b2 || !grads->w3 || !grads->b3)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = mlp2_head_checked(env, logret_f32, weights, H, activation, out_activation, who)) return rc;
-    if (out_activation == 1)
-        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on", who);
-    if (out_activation == 0 && !outputs)
-        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_mlp2_forward returned", who);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused LSTM "
-                    "head does)", who, (int)env->p.A);
-    if (int rc = mlp2_head_fits(env, H, who)) return rc;
+    const MlpHeadView w = mlp_view(weights);
+    const bool given = obs_src && obs_pos && count >= 0 && d_outputs && workspace && grads && grads->w1 && grads->b1 &&
+                       grads->w2 && grads->b2 && grads->w3 && grads->b3;
+    if (int rc = mlp_backward_checked(env, logret_f32, w, H, activation, out_activation, given, outputs, who)) return rc;
     if (count == 0) return FE_OK;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
+    const MlpGradLayout l = mlp_grad_layout(true, H, W, count);
     Mlp2GradArgs g2;
     memset(&g2, 0, sizeof(g2));
-    MlpGradArgs &g = g2.g;
-    g.lr32 = logret_f32; g.w1t = weights->w1t; g.wpos = weights->wpos; g.b1 = weights->b1; g.w2 = weights->w3;
-    g.obs_src = obs_src; g.obs_pos = obs_pos; g.outputs = outputs; g.d_outputs = d_outputs;
-    g.count = count; g.blocks = (count + 31) / 32; g.splits = (count + kMlpGradChunk - 1) / kMlpGradChunk;
-    const int64_t groups = mlp_grad_groups(g.blocks);
-    g.waves = 4 * groups;
-    g.W = W; g.H = H; g.act = activation; g.out_act = out_activation; g.FP = mlp_grad_fp(W);
-    const int64_t rows = 32 * g.blocks * H;
-    g.dpre = workspace;
-    g2.a1 = g.dpre + rows;
-    g2.dz2 = g2.a1 + rows;
-    g.part = g2.dz2 + rows;
-    g2.part2 = g.part + g.splits * H * g.FP;
-    g.wpart = g2.part2 + g.splits * H * (H + 32);
-    g.g_w1 = grads->w1; g.g_b1 = grads->b1; g.g_w2 = grads->w3; g.g_b2 = grads->b3;
-    g2.w2h = weights->w2; g2.b2h = weights->b2; g2.g_w2h = grads->w2; g2.g_b2h = grads->b2;
+    g2.g = mlp_grad_args(logret_f32, w, H, W, activation, out_activation, obs_src, obs_pos, count, outputs, d_outputs, workspace,
+                         l, grads->w1, grads->b1, grads->w3, grads->b3);
+    g2.a1 = workspace + l.a1; g2.dz2 = workspace + l.dz2; g2.part2 = workspace + l.part2;
+    g2.w2h = w.w2h; g2.b2h = w.b2h; g2.g_w2h = grads->w2; g2.g_b2h = grads->b2;
     void *args2[] = {&g2};
-    void *args[] = {&g};
     const hipStream_t st = (hipStream_t)stream;
-    const int64_t wave_groups = capped_grid((g.blocks + kBlock / 64 - 1) / (kBlock / 64));
+    const int64_t wave_groups = capped_grid((l.blocks + kBlock / 64 - 1) / (kBlock / 64));
     // (1) both hidden layers recomputed: a1, dz2, the partials of d w3 / d b3
-    const void *k1 = H == 32 ? (const void *)fe_mlp2_grad_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp2_grad_kernel<2> : (const void *)fe_mlp2_grad_kernel<4>);
-    const size_t lds1 = mlp2_weight_lds_bytes(W, H);
-    if (int rc = prepare_big_lds(env->device, k1, lds1, who)) return rc;
-    if (int rc = launched("fe_mlp2_backward: hidden layers", hipLaunchKernel(k1, dim3((unsigned)groups), dim3(kBlock), args2, lds1, st)))
-        return rc;
+    const MlpHeadKernels k = mlp_head_kernels(true, true, H);
+    const size_t lds1 = mlp_head_image_bytes(w, W, H);
+    if (int rc = prepare_big_lds(env->device, k.grad, lds1, who)) return rc;
+    if (int rc = launched(who, "hidden layers", hipLaunchKernel(k.grad, dim3((unsigned)l.groups), dim3(kBlock), args2, lds1, st))) return rc;
     // (2) dz1 = (W2^T dz2) * act'(z1)
-    const void *k2 = H == 32 ? (const void *)fe_mlp2_dgrad_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp2_dgrad_kernel<2> : (const void *)fe_mlp2_dgrad_kernel<4>);
+    const void *k2 = with_nt(H, [](auto NT) { return (const void *)fe_mlp2_dgrad_kernel<decltype(NT)::value>; });
     const size_t lds2 = (size_t)H * mlp2_hp(H) * 4;
     if (int rc = prepare_big_lds(env->device, k2, lds2, who)) return rc;
-    if (int rc = launched("fe_mlp2_backward: W2^T dz2", hipLaunchKernel(k2, dim3((unsigned)wave_groups), dim3(kBlock), args2, lds2, st)))
-        return rc;
+    if (int rc = launched(who, "W2^T dz2", hipLaunchKernel(k2, dim3((unsigned)wave_groups), dim3(kBlock), args2, lds2, st))) return rc;
     // (3) [dW2 | d b2] partials
-    const void *k3 = H == 32 ? (const void *)fe_mlp2_wgrad2_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp2_wgrad2_kernel<2> : (const void *)fe_mlp2_wgrad2_kernel<4>);
-    const int64_t items3 = g.splits * (H / 32 + 1);
-    if (int rc = launched("fe_mlp2_backward: dz2^T a1",
-                          hipLaunchKernel(k3, dim3((unsigned)capped_grid((items3 + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock),
-                                          args2, 0, st)))
-        return rc;
+    const void *k3 = with_nt(H, [](auto NT) { return (const void *)fe_mlp2_wgrad2_kernel<decltype(NT)::value>; });
+    const int64_t items3 = l.splits * (H / 32 + 1);
+    const int64_t grid3 = capped_grid((items3 + kBlock / 64 - 1) / (kBlock / 64));
+    if (int rc = launched(who, "dz2^T a1", hipLaunchKernel(k3, dim3((unsigned)grid3), dim3(kBlock), args2, 0, st))) return rc;
     // (4), (5) the first layer's weight gradient and the output layer's partials: fe_mlp_backward's kernels on dz1
-    const void *k4 = H == 32 ? (const void *)fe_mlp_wgrad_kernel<1>
-                             : (H == 64 ? (const void *)fe_mlp_wgrad_kernel<2> : (const void *)fe_mlp_wgrad_kernel<4>);
-    const int64_t items = g.splits * (g.FP / 32);
-    const int64_t grid4 = capped_grid((items + kBlock / 64 - 1) / (kBlock / 64));
-    if (int rc = launched("fe_mlp2_backward: first-layer weight gradient", hipLaunchKernel(k4, dim3((unsigned)grid4), dim3(kBlock), args, 0, st)))
-        return rc;
-    hipLaunchKernelGGL(fe_mlp_grad_reduce_kernel, dim3(grid_for((int64_t)H * (4 * W + 2) + H + 1)), dim3(kBlock), 0, st, g);
-    if (int rc = launched("fe_mlp2_backward: reduction")) return rc;
+    if (int rc = mlp_backward_layer1(g2.g, k.wgrad, who, "first-layer weight gradient", st)) return rc;
+    // (6) the second hidden layer's reduction
     hipLaunchKernelGGL(fe_mlp2_grad_reduce_kernel, dim3(grid_for((int64_t)H * (H + 1))), dim3(kBlock), 0, st, g2);
-    return launched("fe_mlp2_backward: W2 reduction");
+    return launched(who, "W2 reduction");
 }
 
 // Tile geometry of the fused LSTM kernels (LSTM and SAC heads) for `count` envs (rollout) or descriptors (forward): sets
@@ -1272,16 +1285,9 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
     const int SP = lstm_geometry(env, p, count, H, big, who);
     if (SP == 0) return FE_ERR_ARG;
     const size_t lds = big ? lstm_big_lds_bytes(p.EB, p.A, H) : lstm_lds_bytes(p.EB, p.A, H, SP);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        switch (H) {
-        case 32: return (const void *)fe_rollout_lstm_kernel<single, 1>;
-        case 64: return (const void *)fe_rollout_lstm_kernel<single, 2>;
-        case 128: return (const void *)fe_rollout_lstm_kernel<single, 4>;
-        case 256: return (const void *)fe_rollout_lstm_big_kernel<single, 4>;
-        case 512: return (const void *)fe_rollout_lstm_big_kernel<single, 8>;
-        default: return (const void *)fe_rollout_lstm_big_kernel<single, 16>;
-        }
+    const void *kern = with_bool(p.A == 1, [H, big](auto S) {  // (with_bool outermost: the instantiations keep their order)
+        if (!big) return with_nt(H, [](auto NT) { return (const void *)fe_rollout_lstm_kernel<decltype(S)::value, decltype(NT)::value>; });
+        return with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_rollout_lstm_big_kernel<decltype(S)::value, decltype(NT)::value>; });
     });
     return launch_resident(env, kern, lds, p, &r, "LSTM kernel", stream);
 }
@@ -1299,14 +1305,7 @@ static int launch_sac(fe_env *env, SacArgs &s, int64_t count, const char *who, v
     const int SP = lstm_geometry(env, p, count, H, false, who);
     if (SP == 0) return FE_ERR_ARG;
     const size_t lds = sac_lds_bytes(p.EB, p.A, H, SP);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        switch (H) {
-        case 32: return (const void *)fe_rollout_sac_kernel<single, 1>;
-        case 64: return (const void *)fe_rollout_sac_kernel<single, 2>;
-        default: return (const void *)fe_rollout_sac_kernel<single, 4>;
-        }
-    });
+    const void *kern = with_nt(p.A == 1, H, [](auto S, auto NT) { return (const void *)fe_rollout_sac_kernel<decltype(S)::value, decltype(NT)::value>; });
     return launch_resident(env, kern, lds, p, &s, "SAC kernel", stream);
 }
 
@@ -1610,9 +1609,8 @@ int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *
     r.rew_scratch = pop->scratch_rewards; r.done_scratch = pop->scratch_dones;
     r.n_train = nt; r.half = half; r.K = K; r.max_ep = pop->max_episodes; r.PB = PB; r.pair_tiles = (int32_t)pair_tiles;
     r.sigma = pop->noise_std; r.nu = pop->action_noise_std; r.seed = pop->seed; r.g = pop->generation; r.step0 = pop->step;
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        return H == 32 ? (const void *)fe_evo_rollout_kernel<single, 32> : (const void *)fe_evo_rollout_kernel<single, 64>;
+    const void *kern = with_nt(p.A == 1, H, [](auto S, auto NT) {  // H = 32 or 64 here, and the kernel takes H itself
+        return (const void *)fe_evo_rollout_kernel<decltype(S)::value, decltype(NT)::value == 1 ? 32 : 64>;
     });
     // one workgroup per tile (capped); the tile is fixed by the pair layout above, without fe_env_set_launch's override
     return launch_big_lds(env->device, kern, capped_grid(p.num_tiles), lds, p, r, stream, "fe_evo_rollout");
@@ -1886,8 +1884,7 @@ static int launch_twin_q(fe_env *env, CriticArgs &cq, int64_t count, const char 
     const int SP = lstm_geometry(env, p, count, H, false, who);
     if (SP == 0) return FE_ERR_ARG;
     const size_t lds = lstm_lds_bytes(p.EB, p.A, H, SP);
-    const void *kern = H == 32 ? (const void *)fe_twin_q_kernel<1>
-                               : (H == 64 ? (const void *)fe_twin_q_kernel<2> : (const void *)fe_twin_q_kernel<4>);
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_twin_q_kernel<decltype(NT)::value>; });
     int per_cu = 0;
     const hipError_t he = prepare_kernel(env->device, kern, kLstmBlock, lds, &per_cu);
     if (he != hipSuccess) return hip_fail(he, "twin critic kernel: hipFuncSetAttribute / occupancy query");
@@ -2046,8 +2043,7 @@ int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_wei
     hipLaunchKernelGGL(fe_critic_grad_pack_kernel, dim3(grid_for(critic_grad_wt_floats(H)), g.ncrit), dim3(kBlock), 0,
                        (hipStream_t)stream, g, H, const_cast<float *>(g.net[0].wt), const_cast<float *>(g.net[1].wt));
     if (int rc = launched("fe_twin_q_backward: weight transpose")) return rc;
-    const void *kern = H == 32 ? (const void *)fe_critic_grad_kernel<1>
-                               : (H == 64 ? (const void *)fe_critic_grad_kernel<2> : (const void *)fe_critic_grad_kernel<4>);
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_critic_grad_kernel<decltype(NT)::value>; });
     if (int rc = launch_grad(env, kern, critic_grad_lds_bytes(H), max_groups, g.ncrit, &g, &g.groups,
                              "critic gradient kernel: hipFuncSetAttribute / occupancy query", "fe_twin_q_backward: backward",
                              stream))
@@ -2105,8 +2101,7 @@ static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *
     hipLaunchKernelGGL(fe_sac_grad_pack_kernel, dim3(grid_for(sac_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
                        g, H);
     if (int rc = launched("fe_sac_backward: weight transpose")) return rc;
-    const void *kern = H == 32 ? (const void *)fe_sac_grad_kernel<1>
-                               : (H == 64 ? (const void *)fe_sac_grad_kernel<2> : (const void *)fe_sac_grad_kernel<4>);
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_sac_grad_kernel<decltype(NT)::value>; });
     if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
                              "SAC gradient kernel: hipFuncSetAttribute / occupancy query", "fe_sac_backward: backward", stream))
         return rc;
@@ -2173,8 +2168,7 @@ int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, con
     hipLaunchKernelGGL(fe_lstm_grad_pack_kernel, dim3(grid_for(lstm_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
                        g, H);
     if (int rc = launched("fe_lstm_backward: weight transpose")) return rc;
-    const void *kern = H == 32 ? (const void *)fe_lstm_grad_kernel<1>
-                               : (H == 64 ? (const void *)fe_lstm_grad_kernel<2> : (const void *)fe_lstm_grad_kernel<4>);
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_lstm_grad_kernel<decltype(NT)::value>; });
     if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
                              "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query", "fe_lstm_backward: backward",
                              stream))
@@ -2327,9 +2321,7 @@ int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float 
     g.g_bout = grads->b_out;
     hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
     if (int rc = launched("fe_lstm_backward_streamed: weight transpose")) return rc;
-    const void *kern = H == 256 ? (const void *)fe_lstm_sgrad_forward_kernel<4>
-                                : (H == 512 ? (const void *)fe_lstm_sgrad_forward_kernel<8>
-                                            : (const void *)fe_lstm_sgrad_forward_kernel<16>);
+    const void *kern = with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_lstm_sgrad_forward_kernel<decltype(NT)::value>; });
     // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
     for (int64_t c0 = 0; c0 < count; c0 += chunk) {
         sgrad_chunk(g, H, c0, count, chunk);
@@ -2538,14 +2530,7 @@ static int launch_sac_streamed(fe_env *env, SacArgs &s, int64_t count, const cha
     const size_t lds = sac_big_lds_bytes(p.EB, p.A, H);
     if (lds > kMaxLds)
         return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
-    const void *kern = with_bool(p.A == 1, [H](auto S) {
-        constexpr bool single = decltype(S)::value;
-        switch (H) {
-        case 256: return (const void *)fe_rollout_sac_big_kernel<single, 4>;
-        case 512: return (const void *)fe_rollout_sac_big_kernel<single, 8>;
-        default: return (const void *)fe_rollout_sac_big_kernel<single, 16>;
-        }
-    });
+    const void *kern = with_nt<64, 4>(p.A == 1, H, [](auto S, auto NT) { return (const void *)fe_rollout_sac_big_kernel<decltype(S)::value, decltype(NT)::value>; });
     return launch_resident(env, kern, lds, p, &s, "streamed SAC kernel", stream);
 }
 
@@ -2640,9 +2625,7 @@ int fe_sac_backward_streamed(fe_env *env, const float *logret_f32, const float *
     hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
     hipLaunchKernelGGL(fe_sac_sgrad_pack_kernel, dim3(grid_for((int64_t)H * H)), dim3(kBlock), 0, st, a, H);
     if (int rc = launched("fe_sac_backward_streamed: weight transposes")) return rc;
-    const void *kern = H == 256 ? (const void *)fe_lstm_sgrad_forward_kernel<4>
-                                : (H == 512 ? (const void *)fe_lstm_sgrad_forward_kernel<8>
-                                            : (const void *)fe_lstm_sgrad_forward_kernel<16>);
+    const void *kern = with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_lstm_sgrad_forward_kernel<decltype(NT)::value>; });
     // the chunks in ascending order (the head's boundaries): the first overwrites the gradients, the later ones add to them
     for (int64_t c0 = 0; c0 < count; c0 += chunk) {
         sgrad_chunk(g, H, c0, count, chunk);

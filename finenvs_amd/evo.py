@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .rollout import _FusedEvaluation
+from .rollout import _FusedEvaluation, log_return_f32
 
 
 # ---------------------------------------------------------------- the update (evo_agent.py:154-191, parallel_mlp.py:176-275)
@@ -110,9 +110,7 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
         self.num_params = 5 * W * self.H + 2 * self.H + 1
         self.obs_src = torch.empty((N,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((N, A), dtype=torch.float64, device=dev)
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
+        self._lr32 = log_return_f32(env)
         self.theta = torch.zeros((self.num_params,), dtype=torch.float32, device=dev)
         self.returns = torch.zeros((N,), dtype=torch.float32, device=dev)
         self.timesteps = torch.zeros((N,), dtype=torch.float32, device=dev)

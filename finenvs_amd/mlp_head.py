@@ -24,17 +24,18 @@ import torch.nn as nn
 from . import _lib
 from .rollout import FusedMLPRollout
 
-MLP_HEAD_HIDDEN_SIZES = (32, 64, 128)
+MLP_HEAD_HIDDEN_SIZES = FusedMLPRollout.HIDDEN_SIZES
 MLP_HEAD_LAYER_ACTIVATIONS = {"elu": nn.ELU, "relu": nn.ReLU, "tanh": nn.Tanh}
 MLP_HEAD_ACTIVATIONS = {"tanh": nn.Tanh, "none": nn.Identity}
 MLP_GRAD_KEYS = ("w1", "b1", "w2", "b2")  # fe_mlp_grads' fields, in mlp_head_parameters' order
 MLP_GRAD_CHUNK_PAIRS = _lib.MLP_GRAD_CHUNK_PAIRS  # pairs per split of the weight-gradient contraction
 
 
-class MLPHead(nn.Module):
-    """The reference's ``MLPNetwork((5W, H, 1), layer_activation, output_activation)`` as a plain module (no optimizer
-    inside): ``network = Sequential(Linear(5W, H), ELU() | ReLU() | Tanh(), Linear(H, 1), Tanh() | Identity())``.
-    ``output_activation``: ``"tanh"`` (the actor) or ``"none"`` (the critic)."""
+class _MLPModule(nn.Module):
+    """The reference's ``MLPNetwork((5W, H, ..., 1), layer_activation, output_activation)`` with ``HIDDEN_LAYERS`` hidden
+    layers of width H as a plain module (no optimizer inside); ``MLPHead`` and ``MLP2Head`` are its two depths."""
+
+    HIDDEN_LAYERS = 1
 
     def __init__(self, H: int = 128, W: int = 4, activation: str = "elu", output_activation: str = "tanh", device=None):
         super().__init__()
@@ -45,10 +46,11 @@ class MLPHead(nn.Module):
                              '"clamp" bounds an action, it is not an output a learner trains through')
         self.hidden_size, self.sequence_length = int(H), int(W)
         self.activation, self.output_activation = activation, output_activation
-        self.network = nn.Sequential(nn.Linear(5 * self.sequence_length, self.hidden_size, device=device),
-                                     MLP_HEAD_LAYER_ACTIVATIONS[activation](),
-                                     nn.Linear(self.hidden_size, 1, device=device),
-                                     MLP_HEAD_ACTIVATIONS[output_activation]())
+        layers, width = [], 5 * self.sequence_length
+        for _ in range(self.HIDDEN_LAYERS):
+            layers += [nn.Linear(width, self.hidden_size, device=device), MLP_HEAD_LAYER_ACTIVATIONS[activation]()]
+            width = self.hidden_size
+        self.network = nn.Sequential(*layers, nn.Linear(width, 1, device=device), MLP_HEAD_ACTIVATIONS[output_activation]())
 
     def forward(self, states: torch.Tensor) -> torch.Tensor:
         """(B, W, 5) or (B, 5W) -> (B, 1)."""
@@ -60,30 +62,57 @@ class MLPHead(nn.Module):
         return self.network(states)
 
 
-def check_mlp_head(module: nn.Module) -> Tuple[int, int, str, str]:
-    """(hidden size, window, activation, output activation) of a module the fused head can run; ValueError otherwise."""
+class MLPHead(_MLPModule):
+    """The reference's ``MLPNetwork((5W, H, 1), layer_activation, output_activation)`` as a plain module (no optimizer
+    inside): ``network = Sequential(Linear(5W, H), ELU() | ReLU() | Tanh(), Linear(H, 1), Tanh() | Identity())``.
+    ``output_activation``: ``"tanh"`` (the actor) or ``"none"`` (the critic)."""
+
+
+def _layer_activation(layer: nn.Module) -> str:
+    name = next((k for k, cls in MLP_HEAD_LAYER_ACTIVATIONS.items() if type(layer) is cls), None)
+    if name is None or (name == "elu" and layer.alpha != 1.0):
+        raise ValueError(f"the hidden activations must be ELU (alpha = 1), ReLU or Tanh (got {type(layer).__name__}"
+                         + (f" with alpha = {layer.alpha}" if name == "elu" else "") + ")")
+    return name
+
+
+def check_head(module: nn.Module, hidden_layers: int, shape_error: str) -> Tuple[int, int, str, str]:
+    """(hidden size, window, activation, output activation) of a module with ``hidden_layers`` hidden layers that a fused
+    head can run; ValueError otherwise -- ``shape_error`` when ``module.network`` is not that ``Sequential``."""
     net = getattr(module, "network", None)
-    if not isinstance(net, nn.Sequential) or len(net) != 4 or not isinstance(net[0], nn.Linear) \
-            or not isinstance(net[2], nn.Linear):
-        raise ValueError("the fused MLP head needs a module with `network = Sequential(Linear(5W, H), act, Linear(H, 1), out)`: "
-                         "one hidden layer (the reference's default of two needs another kernel)")
-    first, last = net[0], net[2]
+    linear = range(0, 2 * hidden_layers + 1, 2)
+    if not isinstance(net, nn.Sequential) or len(net) != 2 * hidden_layers + 2 \
+            or not all(isinstance(net[i], nn.Linear) for i in linear):
+        raise ValueError(shape_error)
+    layers = [net[i] for i in linear]
+    first, last = layers[0], layers[-1]
     H = int(first.out_features)
+    for layer in layers[1:-1]:
+        if layer.in_features != H or layer.out_features != H:
+            raise ValueError(f"both hidden layers must have the same width: Linear(5W, {H}) needs Linear({H}, {H}) "
+                             f"(got Linear({layer.in_features}, {layer.out_features}))")
     if H not in MLP_HEAD_HIDDEN_SIZES:
         raise ValueError(f"the fused MLP head runs H in {MLP_HEAD_HIDDEN_SIZES} (got {H})")
     if first.in_features % 5 != 0 or first.in_features < 5:
         raise ValueError(f"the first layer must take a flattened (W, 5) window: in_features = 5 W (got {first.in_features})")
-    if last.in_features != H or last.out_features != 1 or first.bias is None or last.bias is None:
-        raise ValueError(f"the last layer must be Linear({H}, 1) and both layers need a bias: one output per (env, asset) pair")
-    activation = next((k for k, cls in MLP_HEAD_LAYER_ACTIVATIONS.items() if type(net[1]) is cls), None)
-    if activation is None or (activation == "elu" and net[1].alpha != 1.0):
-        raise ValueError(f"the hidden activation must be ELU (alpha = 1), ReLU or Tanh (got {type(net[1]).__name__})")
-    if isinstance(net[3], nn.Tanh):
-        return H, first.in_features // 5, activation, "tanh"
-    if isinstance(net[3], nn.Identity):
-        return H, first.in_features // 5, activation, "none"
-    raise ValueError(f"the output activation must be Tanh or Identity (got {type(net[3]).__name__}): a clamp has no gradient "
-                     "to train on")
+    if last.in_features != H or last.out_features != 1:
+        raise ValueError(f"the last layer must be Linear({H}, 1): one output per (env, asset) pair")
+    if any(layer.bias is None for layer in layers):
+        raise ValueError(f"all {len(layers)} layers need a bias")
+    activations = [_layer_activation(net[i]) for i in range(1, 2 * hidden_layers, 2)]
+    if len(set(activations)) != 1:
+        raise ValueError(f"both hidden layers must use the same activation (got {' and '.join(activations)})")
+    output = "tanh" if isinstance(net[-1], nn.Tanh) else ("none" if isinstance(net[-1], nn.Identity) else None)
+    if output is None:
+        raise ValueError(f"the output activation must be Tanh or Identity (got {type(net[-1]).__name__}): a clamp has no "
+                         "gradient to train on")
+    return H, first.in_features // 5, activations[0], output
+
+
+def check_mlp_head(module: nn.Module) -> Tuple[int, int, str, str]:
+    """(hidden size, window, activation, output activation) of a module the fused head can run; ValueError otherwise."""
+    return check_head(module, 1, "the fused MLP head needs a module with `network = Sequential(Linear(5W, H), act, Linear(H, 1), "
+                                 "out)`: one hidden layer (the reference's default of two needs another kernel)")
 
 
 def mlp_head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
@@ -94,73 +123,65 @@ def mlp_head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
 
 
 class _MLPHeadValue(torch.autograd.Function):
-    """``FusedMLPRollout.forward`` as a differentiable function of the head's four parameters: the forward is
-    ``fe_mlp_forward``, the backward ``fe_mlp_backward`` (the same first layer, recomputed)."""
+    """``head.rollout.forward`` as a differentiable function of the head's parameters: the forward is ``fe_mlp_forward``
+    or ``fe_mlp2_forward``, the backward the head's ``BACKWARD`` entry (the hidden layers recomputed)."""
 
     @staticmethod
     def forward(ctx, head, src, pos, *params):
         roll = head.rollout
         out = roll.forward(src, pos)
         ctx.set_materialize_grads(False)
-        # the packed weights forward() ran with: backward packs nothing again and makes no copy to the host
-        ctx.head, ctx.packed = head, (roll.w1t, roll.wpos, roll.b1, roll.w2, roll.b2_dev)
+        # the weight buffers forward() ran with: backward packs nothing again and makes no copy to the host
+        ctx.head, ctx.packed = head, tuple(getattr(roll, name) for name in head.PACKED)
         ctx.save_for_backward(src, pos, out)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        out = [None] * 7
+        head = ctx.head
+        out = [None] * (3 + len(head.GRAD_KEYS))
         if g_out is None or not any(ctx.needs_input_grad[3:]):
             return tuple(out)
-        head = ctx.head
         src, pos, values = ctx.saved_tensors
         env, H, B = head.env, head.H, int(src.numel())
         W, dev = int(env.num_intervals), env._dev
-        shapes = {"w1": (H, 5 * W), "b1": (H,), "w2": (1, H), "b2": (1,)}
-        grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in MLP_GRAD_KEYS]
+        grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in head.grad_shapes(H, W)]
         if B:
             g_out = g_out.reshape(B).float().contiguous()
-            ws = torch.empty((int(env._lib.fe_mlp_grad_workspace_floats(H, W, B)),), dtype=torch.float32, device=dev)
-            weights = _lib.FeMlpWeights(*(t.data_ptr() for t in ctx.packed))
-            mg = _lib.FeMlpGrads(*(g.data_ptr() for g in grads))
+            ws = torch.empty((int(getattr(env._lib, head.WORKSPACE)(H, W, B)),), dtype=torch.float32, device=dev)
+            weights = head.WEIGHTS(*(t.data_ptr() for t in ctx.packed))
+            mg = head.GRADS(*(g.data_ptr() for g in grads))
             roll = head.rollout
-            _lib.check(env._lib.fe_mlp_backward(
+            _lib.check(getattr(env._lib, head.BACKWARD)(
                 env._handle, roll._lr32.data_ptr(), C.byref(weights), H, roll.act, roll.out_act, src.data_ptr(),
                 pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(), ws.data_ptr(), C.byref(mg), env._stream()), env._lib)
         else:
             for g in grads:
                 g.zero_()
-        for k in range(4):
+        for k, g in enumerate(grads):
             if ctx.needs_input_grad[3 + k]:
-                out[3 + k] = grads[k]
+                out[3 + k] = g
         return tuple(out)
 
 
-class FusedMLPHead:
-    """An ``MLPHead`` (or the reference's network of that shape) trained on observation descriptors.
-
-    ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_mlp_forward`` --
-    (B, 1) float32, differentiable with respect to the module's four parameters through ``fe_mlp_backward``;
-    ``backward()`` accumulates into their ``.grad`` as the torch module would.  ``.rollout`` is a ``FusedMLPRollout``
-    acting with the same packed buffers: ``run`` steps the env with them (sampled, into a trajectory chunk),
-    ``forward`` is the head without autograd.  The module's parameters are re-packed on the device at every call
-    (``refresh``: ``fe_mlp_pack`` and three small copies, nothing goes to the host), so an optimizer step is seen by
-    the next call and by the next ``rollout.run`` after a ``refresh()``.  The module must live on the env's device."""
+class _FusedHead:
+    """What ``FusedMLPHead`` and ``FusedMLP2Head`` share.  A depth names: ``GRAD_KEYS`` and ``grad_shapes(H, W)`` (the
+    gradients, in its parameters' order), ``WEIGHTS`` / ``GRADS`` (the ctypes structs), ``WORKSPACE`` / ``BACKWARD`` (the C
+    entries), ``PACKED`` (the rollout's attributes that fill ``WEIGHTS``: ``w1t``, ``wpos``, then one per parameter after
+    the first), ``_check`` / ``_parameters`` (of the module) and ``_make_rollout``."""
 
     def __init__(self, env, module: nn.Module):
-        self.H, W, self.activation, self.output_activation = check_mlp_head(module)
+        self.H, W, self.activation, self.output_activation = self._check(module)
         if W != int(env.num_intervals):
             raise ValueError(f"the module's first layer takes a window of {W} rows, the env renders {env.num_intervals}")
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused MLP head trains one asset (the env has {env.num_assets}), as the fused LSTM head does")
         self.env, self.module = env, module
-        w1, b1, w2, b2 = self._check_parameters()
-        self.rollout = FusedMLPRollout(env, w1.detach().t(), b1, w2, 0.0, self.activation, self.output_activation)
-        self.rollout.b2 = None  # the output bias lives on the device (rollout.b2_dev): nothing of this head's weights on the host
+        self.rollout = self._make_rollout(self._check_parameters())
         self.refresh()
 
     def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
-        params = mlp_head_parameters(self.module)
+        params = self._parameters(self.module)
         if any(p.dtype is not torch.float32 for p in params):
             raise ValueError("the fused MLP head's gradient needs float32 parameters")
         if any(p.device != torch.device(self.env._dev) for p in params):
@@ -168,18 +189,19 @@ class FusedMLPHead:
         return params
 
     def refresh(self) -> None:
-        """The module's current parameters into ``self.rollout``, packed on the device (``fe_mlp_pack``) into fresh
-        buffers: no copy to the host, and a forward whose ``backward()`` is still pending keeps the weights it ran with."""
-        w1, b1, w2, b2 = self._check_parameters()
+        """The module's current parameters into ``self.rollout``, on the device into fresh buffers (``fe_mlp_pack`` for
+        the first layer, a copy of each other tensor): no copy to the host, and a forward whose ``backward()`` is still
+        pending keeps the weights it ran with."""
+        params = self._check_parameters()
         env, roll, H, dev = self.env, self.rollout, self.H, self.env._dev
         W = int(env.num_intervals)
         w1t = torch.empty((H, 4 * W), dtype=torch.float32, device=dev)
         wpos = torch.empty((H,), dtype=torch.float32, device=dev)
-        _lib.check(env._lib.fe_mlp_pack(w1.detach().contiguous().data_ptr(), H, W, w1t.data_ptr(), wpos.data_ptr(),
+        _lib.check(env._lib.fe_mlp_pack(params[0].detach().contiguous().data_ptr(), H, W, w1t.data_ptr(), wpos.data_ptr(),
                                         env._stream()), env._lib)
         roll.w1t, roll.wpos = w1t, wpos
-        roll.b1, roll.w2 = b1.detach().reshape(H).clone(), w2.detach().reshape(H).clone()
-        roll.b2_dev = b2.detach().reshape(1).clone()
+        for name, p in zip(self.PACKED[2:], params[1:]):  # a (1, H) output weight is kept as (H)
+            setattr(roll, name, p.detach().reshape(p.shape[-1:] if p.shape[0] == 1 else p.shape).clone())
 
     def __call__(self, obs_src: torch.Tensor, obs_pos: torch.Tensor) -> torch.Tensor:
         """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B,)`` or ``(B, 1)`` float64):
@@ -196,3 +218,31 @@ class FusedMLPHead:
         if B:  # an empty batch packs nothing and launches nothing, in either direction
             self.refresh()
         return _MLPHeadValue.apply(self, src, pos, *params)
+
+
+class FusedMLPHead(_FusedHead):
+    """An ``MLPHead`` (or the reference's network of that shape) trained on observation descriptors.
+
+    ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_mlp_forward`` --
+    (B, 1) float32, differentiable with respect to the module's four parameters through ``fe_mlp_backward``;
+    ``backward()`` accumulates into their ``.grad`` as the torch module would.  ``.rollout`` is a ``FusedMLPRollout``
+    acting with the same packed buffers: ``run`` steps the env with them (sampled, into a trajectory chunk),
+    ``forward`` is the head without autograd.  The module's parameters are re-packed on the device at every call
+    (``refresh``: ``fe_mlp_pack`` and three small copies, nothing goes to the host), so an optimizer step is seen by
+    the next call and by the next ``rollout.run`` after a ``refresh()``.  The module must live on the env's device."""
+
+    GRAD_KEYS = MLP_GRAD_KEYS
+    WEIGHTS, GRADS = _lib.FeMlpWeights, _lib.FeMlpGrads
+    WORKSPACE, BACKWARD = "fe_mlp_grad_workspace_floats", "fe_mlp_backward"
+    PACKED = ("w1t", "wpos", "b1", "w2", "b2_dev")
+    _check, _parameters = staticmethod(check_mlp_head), staticmethod(mlp_head_parameters)
+
+    @staticmethod
+    def grad_shapes(H: int, W: int):
+        return (H, 5 * W), (H,), (1, H), (1,)
+
+    def _make_rollout(self, params) -> FusedMLPRollout:
+        w1, b1, w2, _ = params
+        rollout = FusedMLPRollout(self.env, w1.detach().t(), b1, w2, 0.0, self.activation, self.output_activation)
+        rollout.b2 = None  # the output bias lives on the device (rollout.b2_dev): nothing of this head's weights on the host
+        return rollout

@@ -375,7 +375,162 @@ class FusedLinearRollout(_FusedEvaluation):
         return actions, rewards, dones
 
 
-class FusedMLPRollout(_FusedEvaluation):
+def log_return_f32(env) -> torch.Tensor:
+    """The f32 copy of the log-return table the fused policies stream from (what ``states.float()`` would hold): the one
+    the env has bound, else a copy of its own."""
+    lr32 = getattr(env, "_log_return_f32", None)
+    return lr32 if lr32 is not None else env.log_return_environments.float().contiguous()
+
+
+def rollout_outputs(env, K: int, trajectory, record_actions: bool = True):
+    """Where a fused K-step rollout writes: ``(actions, rewards, dones, src_out, pos_out)``.  ``trajectory`` -- an empty
+    ``TrajectoryBuffer(K, N, A, states=True)`` on the env's device without capacity padding, or a ValueError -- gives its
+    chunk and the K + 1 descriptor rows; without one the tensors are fresh (``actions`` None unless ``record_actions``)
+    and no descriptors are kept."""
+    N, A, dev = env.num_envs, env.num_assets, env._dev
+    if trajectory is not None:
+        tr = trajectory
+        if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
+            raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
+                             "without capacity padding")
+        return tr.actions, tr.rewards, tr.dones, tr.obs_src, tr.obs_pos
+    actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
+    rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
+    dones = torch.empty((K, N), dtype=torch.int32, device=dev)
+    return actions, rewards, dones, None, None
+
+
+def training_rollout_outputs(env, K: int, record_actions: bool, noise, std, trajectory):
+    """The prologue of a training rollout's ``run``: ``rollout_outputs`` and the checked, contiguous ``noise`` (``(K, N,
+    A)`` f32 on the env's device, with ``std >= 0``) as a sixth element."""
+    outputs = rollout_outputs(env, K, trajectory, record_actions)
+    if noise is not None:
+        N, A, dev = env.num_envs, env.num_assets, env._dev
+        if std is None or not float(std) >= 0.0:
+            raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
+        if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
+            raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
+        noise = noise.contiguous()
+    return outputs + (noise,)
+
+
+def _descriptor_batch(env, obs_src: torch.Tensor, obs_pos: torch.Tensor):
+    """``(B, src (B,) int64, pos (B, A) float64)`` on the env's device, contiguous: the descriptors a ``forward`` reads."""
+    B = int(obs_src.numel())
+    src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+    pos = obs_pos.reshape(B, env.num_assets).to(device=env._dev, dtype=torch.float64).contiguous()
+    return B, src, pos
+
+
+def _forward_out(env, B: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """The caller's ``out`` checked, or a fresh ``(B, A)`` float32 tensor."""
+    A = env.num_assets
+    if out is None:
+        return torch.empty((B, A), dtype=torch.float32, device=env._dev)
+    if out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
+        raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
+    return out
+
+
+class _FusedMLPPolicy(_FusedEvaluation):
+    """What ``FusedMLPRollout`` and ``FusedMLP2Rollout`` share: the constructor's checks and buffers, the packing of the
+    first layer, ``forward`` and the sampled ``run``.  A subclass names its C entries (``_FORWARD``, ``_SAMPLED``) and
+    provides ``set_weights`` and ``_weights`` (the ctypes weight struct of its buffers)."""
+
+    HIDDEN_SIZES = (32, 64, 128)  # the H the kernels are instantiated for
+    ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2}
+    OUTPUT_ACTIVATIONS = {"tanh": 0, "clamp": 1, "none": 2}  # "none": a critic (forward() only; an action needs bounds)
+
+    def __init__(self, env, weights: tuple, activation: str, output_activation: str):
+        W, W1 = env.num_intervals, weights[0]
+        if W1.dim() != 2 or W1.shape[0] != 5 * W:
+            raise ValueError(f"W1 must be ({5 * W}, H): one row per flattened observation element")
+        H = int(W1.shape[1])
+        if H not in self.HIDDEN_SIZES:
+            raise ValueError("H must be 32, 64 or 128")
+        self._check_hidden(H, weights)
+        if activation not in self.ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(self.ACTIVATIONS)}")
+        if output_activation not in self.OUTPUT_ACTIVATIONS:
+            raise ValueError(f"output_activation must be one of {sorted(self.OUTPUT_ACTIVATIONS)}")
+        if env.redraw != "device" and not env.evaluate:
+            raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
+        self.env, self.H, self.act = env, H, self.ACTIVATIONS[activation]
+        self.out_act = self.OUTPUT_ACTIVATIONS[output_activation]
+        self.means = None
+        self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=env._dev)
+        self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=env._dev)
+        self._lr32 = log_return_f32(env)
+        self.set_weights(*weights)
+        self.sync_from_env()
+
+    def _check_hidden(self, H: int, weights: tuple) -> None:
+        """The shapes beyond the first layer's that the constructor refuses (none here)."""
+
+    def _pack_first_layer(self, W1: torch.Tensor) -> None:
+        """``w1t (H, 4W)`` and ``wpos (H)`` as ``fe_mlp_pack`` writes them: the log-return columns transposed, the
+        position column summed over the window."""
+        W, H, dev = self.env.num_intervals, self.H, self.env._dev
+        w = W1.detach().to(dtype=torch.float32, device="cpu").reshape(W, 5, H)
+        self.w1t = w[:, :4, :].reshape(4 * W, H).t().contiguous().to(dev)
+        wpos = torch.zeros((H,), dtype=torch.float32)
+        for j in range(W):  # sequential f32 sum, j ascending: part of the contract (oracle: mlp_pack)
+            wpos = wpos + w[j, 4, :]
+        self.wpos = wpos.to(dev)
+
+    def _f32(self, t: torch.Tensor, *shape: int) -> torch.Tensor:
+        return t.detach().to(dtype=torch.float32, device=self.env._dev).reshape(shape).contiguous()
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The head evaluated on ANY B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` float64 --
+        rows of a ``TrajectoryBuffer(states=True)``, gathered ones included) without stepping the env and without
+        materialising the observations: ``(B, A)`` float32 (C ABI ``fe_mlp_forward`` / ``fe_mlp2_forward``).  With
+        ``output_activation="none"`` this is the critic of the reference's ``PPOAgentMLP``: the values of all K + 1
+        states of a chunk in one launch."""
+        from . import _lib
+
+        env = self.env
+        B, src, pos = _descriptor_batch(env, obs_src, obs_pos)
+        out = _forward_out(env, B, out)
+        if B:
+            w = self._weights()
+            _lib.check(getattr(env._lib, self._FORWARD)(
+                env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, src.data_ptr(), pos.data_ptr(),
+                B, out.data_ptr(), env._stream()))
+        return out
+
+    def run(self, num_steps: int, record_actions: bool = True, noise: Optional[torch.Tensor] = None,
+            std: Optional[float] = None, record_means: bool = False, trajectory=None):
+        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32).
+
+        Training rollouts (``agent.step`` of finenvs/agents/PPO/PPO_agent.py:98-108), as ``FusedLSTMRollout.run``:
+        pass ``noise`` -- (K, N, A) f32 standard-normal draws from the caller's generator -- and ``std =
+        exp(log_standard_deviation)``; the action is ``clamp(mean + std * noise, -1, 1)``, the eval env of a
+        training-mode env acts on the mean (an evaluate-mode env has none: every env samples).  ``record_means`` keeps
+        the means in ``self.means`` ((K, N, A), what ``log_prob`` needs).  ``trajectory``: an empty
+        ``TrajectoryBuffer(K, N, A, states=True)`` without capacity padding -- the kernel writes actions, rewards, dones
+        and the K + 1 state descriptors straight into its chunk; the returned tensors are then views of it.
+        (C ABI ``fe_env_rollout_mlp_sampled`` / ``fe_env_rollout_mlp2_sampled``.)"""
+        from . import _lib
+
+        env, K = self.env, int(num_steps)
+        actions, rewards, dones, src_out, pos_out, noise = training_rollout_outputs(env, K, record_actions, noise, std,
+                                                                                    trajectory)
+        self._begin_run()
+        self.means = torch.empty((K, env.num_envs, env.num_assets), dtype=torch.float32, device=env._dev) if record_means else None
+        w = self._weights()
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        _lib.check(getattr(env._lib, self._SAMPLED)(
+            env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, K, self.obs_src.data_ptr(),
+            self.obs_pos.data_ptr(), ptr(noise), float(std) if noise is not None else 0.0, ptr(actions), ptr(self.means),
+            rewards.data_ptr(), dones.data_ptr(), ptr(src_out), ptr(pos_out), env._stream()))
+        self._end_run()
+        if trajectory is not None:
+            trajectory.mark_filled(K)
+        return actions, rewards, dones
+
+
+class FusedMLPRollout(_FusedMLPPolicy):
     """K env steps per launch with an in-kernel two-layer perceptron policy on the flattened observation window of
     every (env, asset) pair (SURVEY.md 8f.2 "linear/MLP head"; C ABI ``fe_env_rollout_mlp``):
 
@@ -387,48 +542,17 @@ class FusedMLPRollout(_FusedEvaluation):
     to HBM during the rollout.  ``W1`` is (5W, H) with rows in observation order (row 5j+c), ``b1``/``W2`` (H,),
     ``H`` in {32, 64, 128}."""
 
-    ACTIVATIONS = {"elu": 0, "relu": 1, "tanh": 2}
-    OUTPUT_ACTIVATIONS = {"tanh": 0, "clamp": 1, "none": 2}  # "none": a critic (forward() only; an action needs bounds)
+    _FORWARD, _SAMPLED = "fe_mlp_forward", "fe_env_rollout_mlp_sampled"
 
     def __init__(self, env, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: float = 0.0, activation: str = "elu",
                  output_activation: str = "clamp"):
         """``output_activation``: ``"clamp"`` (the default: clamp(p, -1, 1)), ``"tanh"`` (the reference's MLP actor,
         PPO/continuous_actor.py:81-101) or ``"none"`` (its critic, PPO/critic.py:35-50)."""
-        W = env.num_intervals
-        if W1.dim() != 2 or W1.shape[0] != 5 * W:
-            raise ValueError(f"W1 must be ({5 * W}, H): one row per flattened observation element")
-        H = int(W1.shape[1])
-        if H not in (32, 64, 128):
-            raise ValueError("H must be 32, 64 or 128")
-        if activation not in self.ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(self.ACTIVATIONS)}")
-        if output_activation not in self.OUTPUT_ACTIVATIONS:
-            raise ValueError(f"output_activation must be one of {sorted(self.OUTPUT_ACTIVATIONS)}")
-        if env.redraw != "device" and not env.evaluate:
-            raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
-        self.env, self.H, self.act = env, H, self.ACTIVATIONS[activation]
-        self.out_act = self.OUTPUT_ACTIVATIONS[output_activation]
-        self.means = None
-        dev = env._dev
-        self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
-        self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
-        # the f32 copy of the log-return table the first layer streams from (what states.float() would hold)
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
-        self.set_weights(W1, b1, W2, b2)
-        self.sync_from_env()
+        super().__init__(env, (W1, b1, W2, b2), activation, output_activation)
 
     def set_weights(self, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: float) -> None:
-        W, H, dev = self.env.num_intervals, self.H, self.env._dev
-        w = W1.detach().to(dtype=torch.float32, device="cpu").reshape(W, 5, H)
-        self.w1t = w[:, :4, :].reshape(4 * W, H).t().contiguous().to(dev)
-        wpos = torch.zeros((H,), dtype=torch.float32)
-        for j in range(W):  # sequential f32 sum, j ascending: part of the contract (oracle: mlp_pack)
-            wpos = wpos + w[j, 4, :]
-        self.wpos = wpos.to(dev)
-        self.b1 = b1.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
-        self.w2 = W2.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
+        self._pack_first_layer(W1)
+        self.b1, self.w2 = self._f32(b1, self.H), self._f32(W2, self.H)
         self.b2 = float(b2)
         # the output bias where the training entries read it (include/finenvs_amd_mlp_head.h); made on first use
         self.b2_dev = None
@@ -443,90 +567,28 @@ class FusedMLPRollout(_FusedEvaluation):
         return _lib.FeMlpWeights(self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
                                  self.b2_dev.data_ptr())
 
-    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The head evaluated on ANY B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` float64 --
-        rows of a ``TrajectoryBuffer(states=True)``, gathered ones included) without stepping the env and without
-        materialising the observations: ``(B, A)`` float32 (C ABI ``fe_mlp_forward``).  With
-        ``output_activation="none"`` this is the critic of the reference's ``PPOAgentMLP``: the values of all K + 1
-        states of a chunk in one launch."""
-        from . import _lib
-
-        env, A = self.env, self.env.num_assets
-        B = int(obs_src.numel())
-        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
-        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
-        if out is None:
-            out = torch.empty((B, A), dtype=torch.float32, device=env._dev)
-        elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
-            raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
-        if B:
-            w = self._weights()
-            _lib.check(env._lib.fe_mlp_forward(env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act,
-                                               src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), env._stream()))
-        return out
-
     def run(self, num_steps: int, record_actions: bool = True, noise: Optional[torch.Tensor] = None,
             std: Optional[float] = None, record_means: bool = False, trajectory=None):
-        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32).
-
-        Training rollouts (``agent.step`` of finenvs/agents/PPO/PPO_agent.py:98-108), as ``FusedLSTMRollout.run``:
-        pass ``noise`` -- (K, N, A) f32 standard-normal draws from the caller's generator -- and ``std =
-        exp(log_standard_deviation)``; the action is ``clamp(mean + std * noise, -1, 1)``, the eval env of a
-        training-mode env acts on the mean (an evaluate-mode env has none: every env samples).  ``record_means`` keeps
-        the means in ``self.means`` ((K, N, A), what ``log_prob`` needs).  ``trajectory``: an empty
-        ``TrajectoryBuffer(K, N, A, states=True)`` without capacity padding -- the kernel writes actions, rewards, dones
-        and the K + 1 state descriptors straight into its chunk; the returned tensors are then views of it.
-
-        A plain ``run(K)`` of a rollout with the default clamp output is ``fe_env_rollout_mlp``; everything else is
-        ``fe_env_rollout_mlp_sampled`` (include/finenvs_amd_mlp_head.h)."""
+        """As ``_FusedMLPPolicy.run``, except that a plain ``run(K)`` of a rollout with the default clamp output is
+        ``fe_env_rollout_mlp``; everything else is ``fe_env_rollout_mlp_sampled`` (include/finenvs_amd_mlp_head.h)."""
         from . import _lib
 
-        env, K = self.env, int(num_steps)
-        N, A = env.num_envs, env.num_assets
-        dev = env._dev
-        src_out = pos_out = None
-        if trajectory is not None:
-            tr = trajectory
-            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
-                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
-                                 "without capacity padding")
-            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
-            src_out, pos_out = tr.obs_src, tr.obs_pos
-        else:
-            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
-            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
-            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
-        if noise is not None:
-            if std is None or not float(std) >= 0.0:
-                raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
-            if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
-                raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
-            noise = noise.contiguous()
-        self._begin_run()
         plain = (self.out_act == 1 and noise is None and not record_means and trajectory is None and self.b2 is not None)
-        if plain:
-            self.means = None
-            _lib.check(env._lib.fe_env_rollout_mlp(
-                env._handle, self._lr32.data_ptr(), self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(),
-                self.w2.data_ptr(), self.b2, self.H, self.act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
-                actions.data_ptr() if record_actions else None, rewards.data_ptr(), dones.data_ptr(), env._stream()))
-        else:
-            self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
-            w = self._weights()
-            _lib.check(env._lib.fe_env_rollout_mlp_sampled(
-                env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, K, self.obs_src.data_ptr(),
-                self.obs_pos.data_ptr(), noise.data_ptr() if noise is not None else None,
-                float(std) if noise is not None else 0.0, actions.data_ptr() if actions is not None else None,
-                self.means.data_ptr() if record_means else None, rewards.data_ptr(), dones.data_ptr(),
-                src_out.data_ptr() if src_out is not None else None, pos_out.data_ptr() if pos_out is not None else None,
-                env._stream()))
+        if not plain:
+            return super().run(num_steps, record_actions, noise, std, record_means, trajectory)
+        env, K = self.env, int(num_steps)
+        actions, rewards, dones, _, _ = rollout_outputs(env, K, None, record_actions)
+        self._begin_run()
+        self.means = None
+        _lib.check(env._lib.fe_env_rollout_mlp(
+            env._handle, self._lr32.data_ptr(), self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(),
+            self.w2.data_ptr(), self.b2, self.H, self.act, K, self.obs_src.data_ptr(), self.obs_pos.data_ptr(),
+            actions.data_ptr() if record_actions else None, rewards.data_ptr(), dones.data_ptr(), env._stream()))
         self._end_run()
-        if trajectory is not None:
-            trajectory.mark_filled(K)
         return actions, rewards, dones
 
 
-class FusedMLP2Rollout(_FusedEvaluation):
+class FusedMLP2Rollout(_FusedMLPPolicy):
     """``FusedMLPRollout`` for the reference's default MLP of two hidden layers (``hidden_dims=(H, H)``,
     finenvs/agents/networks/multilayer_perceptron.py; C ABI include/finenvs_amd_mlp2_head.h):
 
@@ -537,121 +599,29 @@ class FusedMLP2Rollout(_FusedEvaluation):
     the first one's activations from registers.  Every ``run`` is ``fe_env_rollout_mlp2_sampled``, ``forward`` is
     ``fe_mlp2_forward``; no observation is written to HBM."""
 
-    ACTIVATIONS = FusedMLPRollout.ACTIVATIONS
-    OUTPUT_ACTIVATIONS = FusedMLPRollout.OUTPUT_ACTIVATIONS
+    _FORWARD, _SAMPLED = "fe_mlp2_forward", "fe_env_rollout_mlp2_sampled"
 
     def __init__(self, env, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor,
                  b3: float = 0.0, activation: str = "elu", output_activation: str = "clamp"):
-        W = env.num_intervals
-        if W1.dim() != 2 or W1.shape[0] != 5 * W:
-            raise ValueError(f"W1 must be ({5 * W}, H): one row per flattened observation element")
-        H = int(W1.shape[1])
-        if H not in (32, 64, 128):
-            raise ValueError("H must be 32, 64 or 128")
-        if tuple(W2.shape) != (H, H):
+        super().__init__(env, (W1, b1, W2, b2, W3, b3), activation, output_activation)
+
+    def _check_hidden(self, H: int, weights: tuple) -> None:
+        if tuple(weights[2].shape) != (H, H):
             raise ValueError(f"W2 must be ({H}, {H}): both hidden layers have the same width")
-        if activation not in self.ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(self.ACTIVATIONS)}")
-        if output_activation not in self.OUTPUT_ACTIVATIONS:
-            raise ValueError(f"output_activation must be one of {sorted(self.OUTPUT_ACTIVATIONS)}")
-        if env.redraw != "device" and not env.evaluate:
-            raise ValueError('the fused rollout needs redraw="device" (or evaluate mode): no host in the loop')
-        self.env, self.H, self.act = env, H, self.ACTIVATIONS[activation]
-        self.out_act = self.OUTPUT_ACTIVATIONS[output_activation]
-        self.means = None
-        dev = env._dev
-        self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
-        self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
-        self.set_weights(W1, b1, W2, b2, W3, b3)
-        self.sync_from_env()
 
     def set_weights(self, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor, b2: torch.Tensor, W3: torch.Tensor,
                     b3: float) -> None:
         """The first layer is packed as ``FusedMLPRollout.set_weights`` packs it; the rest is kept as given."""
-        W, H, dev = self.env.num_intervals, self.H, self.env._dev
-        w = W1.detach().to(dtype=torch.float32, device="cpu").reshape(W, 5, H)
-        self.w1t = w[:, :4, :].reshape(4 * W, H).t().contiguous().to(dev)
-        wpos = torch.zeros((H,), dtype=torch.float32)
-        for j in range(W):  # sequential f32 sum, j ascending, as fe_mlp_pack
-            wpos = wpos + w[j, 4, :]
-        self.wpos = wpos.to(dev)
-        self.b1 = b1.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
-        self.w2 = W2.detach().to(dtype=torch.float32, device=dev).reshape(H, H).contiguous()
-        self.b2 = b2.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
-        self.w3 = W3.detach().to(dtype=torch.float32, device=dev).reshape(H).contiguous()
-        self.b3_dev = torch.tensor([float(b3)], dtype=torch.float32).to(dev)
+        H = self.H
+        self._pack_first_layer(W1)
+        self.b1, self.w2, self.b2, self.w3 = self._f32(b1, H), self._f32(W2, H, H), self._f32(b2, H), self._f32(W3, H)
+        self.b3_dev = torch.tensor([float(b3)], dtype=torch.float32).to(self.env._dev)
 
     def _weights(self):
         from . import _lib
 
         return _lib.FeMlp2Weights(self.w1t.data_ptr(), self.wpos.data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
                                   self.b2.data_ptr(), self.w3.data_ptr(), self.b3_dev.data_ptr())
-
-    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The head on ANY B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B, A)`` float64): ``(B, A)``
-        float32 (C ABI ``fe_mlp2_forward``), without stepping the env and without materialising the observations."""
-        from . import _lib
-
-        env, A = self.env, self.env.num_assets
-        B = int(obs_src.numel())
-        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
-        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
-        if out is None:
-            out = torch.empty((B, A), dtype=torch.float32, device=env._dev)
-        elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
-            raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
-        if B:
-            w = self._weights()
-            _lib.check(env._lib.fe_mlp2_forward(env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act,
-                                                src.data_ptr(), pos.data_ptr(), B, out.data_ptr(), env._stream()))
-        return out
-
-    def run(self, num_steps: int, record_actions: bool = True, noise: Optional[torch.Tensor] = None,
-            std: Optional[float] = None, record_means: bool = False, trajectory=None):
-        """Returns (actions (K, N, A) f32 or None, rewards (K, N) f64, dones (K, N) int32); arguments and semantics as
-        ``FusedMLPRollout.run``: ``noise`` (K, N, A) f32 with ``std`` samples ``clamp(mean + std * noise, -1, 1)`` (the
-        eval env of a training-mode env acts on the mean), ``record_means`` keeps ``self.means``, ``trajectory`` is an
-        empty ``TrajectoryBuffer(K, N, A, states=True)`` the kernel fills with the K + 1 descriptor rows."""
-        from . import _lib
-
-        env, K = self.env, int(num_steps)
-        N, A = env.num_envs, env.num_assets
-        dev = env._dev
-        src_out = pos_out = None
-        if trajectory is not None:
-            tr = trajectory
-            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
-                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
-                                 "without capacity padding")
-            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
-            src_out, pos_out = tr.obs_src, tr.obs_pos
-        else:
-            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
-            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
-            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
-        if noise is not None:
-            if std is None or not float(std) >= 0.0:
-                raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
-            if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
-                raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
-            noise = noise.contiguous()
-        self._begin_run()
-        self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
-        w = self._weights()
-        _lib.check(env._lib.fe_env_rollout_mlp2_sampled(
-            env._handle, self._lr32.data_ptr(), C.byref(w), self.H, self.act, self.out_act, K, self.obs_src.data_ptr(),
-            self.obs_pos.data_ptr(), noise.data_ptr() if noise is not None else None,
-            float(std) if noise is not None else 0.0, actions.data_ptr() if actions is not None else None,
-            self.means.data_ptr() if record_means else None, rewards.data_ptr(), dones.data_ptr(),
-            src_out.data_ptr() if src_out is not None else None, pos_out.data_ptr() if pos_out is not None else None,
-            env._stream()))
-        self._end_run()
-        if trajectory is not None:
-            trajectory.mark_filled(K)
-        return actions, rewards, dones
 
 
 def lstm_row_order(H: int) -> torch.Tensor:
@@ -737,9 +707,7 @@ class FusedLSTMRollout(_FusedEvaluation):
         dev = env._dev
         self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
+        self._lr32 = log_return_f32(env)
         self.set_weights(weight_ih, weight_hh, bias_ih, bias_hh, weight_out, bias_out)
         self.sync_from_env()
 
@@ -777,16 +745,11 @@ class FusedLSTMRollout(_FusedEvaluation):
         descriptors first (``env.check_descriptors``: for descriptors that came from another rank or a caller's buffer)."""
         from . import _lib
 
-        env, A = self.env, self.env.num_assets
-        B = int(obs_src.numel())
-        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
-        pos = obs_pos.reshape(B, A).to(device=env._dev, dtype=torch.float64).contiguous()
+        env = self.env
+        B, src, pos = _descriptor_batch(env, obs_src, obs_pos)
         if check:
             env.check_descriptors(src)
-        if out is None:
-            out = torch.empty((B, A), dtype=torch.float32, device=env._dev)
-        elif out.dtype is not torch.float32 or out.numel() != B * A or not out.is_contiguous() or out.device != env._dev:
-            raise ValueError(f"out must be a contiguous float32 tensor of {B} x {A} elements on {env._dev}")
+        out = _forward_out(env, B, out)
         if B:
             resident = self.bout_dev is not None  # the bias through a device pointer: no value from the host
             fwd = env._lib.fe_lstm_forward_p if resident else env._lib.fe_lstm_forward
@@ -816,24 +779,8 @@ class FusedLSTMRollout(_FusedEvaluation):
         N, A = env.num_envs, env.num_assets
         dev = env._dev
         self._begin_run()
-        src_out = pos_out = None
-        if trajectory is not None:
-            tr = trajectory
-            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
-                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
-                                 "without capacity padding")
-            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
-            src_out, pos_out = tr.obs_src, tr.obs_pos
-        else:
-            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_actions else None
-            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
-            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
-        if noise is not None:
-            if std is None or not float(std) >= 0.0:
-                raise ValueError("noise needs std >= 0 (= exp(log_standard_deviation))")
-            if noise.dtype is not torch.float32 or noise.numel() != K * N * A or noise.device != dev:
-                raise ValueError(f"noise must be ({K}, {N}, {A}) float32 on {dev}")
-            noise = noise.contiguous()
+        actions, rewards, dones, src_out, pos_out, noise = training_rollout_outputs(env, K, record_actions, noise, std,
+                                                                                    trajectory)
         self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None
         resident = self.bout_dev is not None
         args = (env._handle, self._lr32.data_ptr(), self.whh.data_ptr(), self.wx.data_ptr(), self.wout.data_ptr(),

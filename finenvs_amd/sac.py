@@ -30,7 +30,7 @@ import torch.nn.functional as F
 from torch.distributions import Normal
 
 from . import _lib
-from .rollout import _FusedEvaluation, lstm_fragment_major, lstm_pack
+from .rollout import _FusedEvaluation, log_return_f32, lstm_fragment_major, lstm_pack, rollout_outputs
 
 SAC_HIDDEN_SIZES = (32, 64, 128)
 SAC_STREAMED_HIDDEN_SIZES = (256, 512, 1024)  # with streamed=True
@@ -248,9 +248,7 @@ class FusedSACRollout(_FusedEvaluation):
         dev = env._dev
         self.obs_src = torch.empty((env.num_envs,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((env.num_envs, env.num_assets), dtype=torch.float64, device=dev)
-        self._lr32 = getattr(env, "_log_return_f32", None)
-        if self._lr32 is None:
-            self._lr32 = env.log_return_environments.float().contiguous()
+        self._lr32 = log_return_f32(env)
         self.means = self.stds = None
         self.last: Dict[str, torch.Tensor] = {}  # means / stds of the latest sample()
         self.sync_from_env()
@@ -298,18 +296,7 @@ class FusedSACRollout(_FusedEvaluation):
         if K < 1:
             raise ValueError("num_steps must be >= 1")
         noise = self._check_noise(noise, (K, N, A))
-        src_out = pos_out = None
-        if trajectory is not None:
-            tr = trajectory
-            if not (tr.has_states and tr.T == K and tr.N == N and tr.C == N and tr.A == A and len(tr) == 0 and tr.device == dev):
-                raise ValueError("trajectory must be an empty TrajectoryBuffer(K, N, A, states=True) on the env's device "
-                                 "without capacity padding")
-            actions, rewards, dones = tr.actions, tr.rewards, tr.dones
-            src_out, pos_out = tr.obs_src, tr.obs_pos
-        else:
-            actions = torch.empty((K, N, A), dtype=torch.float32, device=dev)
-            rewards = torch.empty((K, N), dtype=torch.float64, device=dev)
-            dones = torch.empty((K, N), dtype=torch.int32, device=dev)
+        actions, rewards, dones, src_out, pos_out = rollout_outputs(env, K, trajectory)
         self._begin_run()
         w = self._weights()
         self.means = torch.empty((K, N, A), dtype=torch.float32, device=dev) if record_means else None

@@ -140,6 +140,37 @@ def test_argument_checks_need_no_device():
         assert _sampled(lib, std=std) == ERR and b"fe_env_rollout_mlp2_sampled: std must be >= 0" in lib.fe_last_error()
 
 
+# one refusal each, and pairs of refusals that apply at once: which one wins is the order of the checks
+_REFUSED = {
+    "backward": [dict(src=None), dict(lr32=None), dict(env=None), dict(weights=None), dict(grads=None), dict(count=-1),
+                 dict(H=48), dict(act=3), dict(out_act=-1), dict(out_act=1), dict(out_act=0, outputs=None),
+                 dict(workspace=None, H=48), dict(H=48, act=3), dict(act=3, out_act=3), dict(H=16, out_act=1),
+                 dict(out_act=1, outputs=None)],
+    "forward": [dict(out=None), dict(env=None), dict(weights=None), dict(count=-1), dict(H=256), dict(act=-1), dict(out_act=3),
+                dict(count=-1, H=48), dict(H=48, act=3), dict(act=3, out_act=3)],
+    "sampled": [dict(ssrc=None), dict(spos=None), dict(std=-0.5), dict(K=0), dict(rewards=None), dict(env=None),
+                dict(weights=None), dict(H=48), dict(act=3), dict(out_act=3), dict(ssrc=None, std=-0.5), dict(std=-0.5, K=0),
+                dict(K=0, H=48), dict(dones=None, weights=None), dict(H=48, act=3)],
+}
+
+
+@pytest.mark.parametrize("entry", sorted(_REFUSED))
+def test_both_depths_refuse_alike(entry):
+    """The one- and two-hidden-layer entries share their host path: the same arguments get the same return code and the
+    same message, apart from the entry's name (and the forward entry a message names)."""
+    from finenvs_amd import _lib
+    from tests import test_mlp_head_host as one
+
+    lib = _lib.load()
+    for kw in _REFUSED[entry]:
+        rc1 = getattr(one, "_" + entry)(lib, **kw)
+        msg1 = lib.fe_last_error()
+        rc2 = globals()["_" + entry](lib, **kw)
+        msg2 = lib.fe_last_error()
+        assert rc1 == rc2 == _lib.FE_ERR_ARG, kw
+        assert msg1 and msg2.replace(b"mlp2", b"mlp") == msg1, (kw, msg1, msg2)
+
+
 def _formula(H, W, count):
     """The workspace size as include/finenvs_amd_mlp2_head.h states it."""
     if count == 0:
