@@ -561,6 +561,19 @@ static int init_env(fe_env *env, const double *prices, const double *logret, int
     return FE_OK;
 }
 
+// The six gradients of one LSTM and its one-output layer, fe_lstm_grads or fe_critic_grads (templates: outside the
+// extern "C" block): every pointer is there ...
+template <class Grads>
+static bool head_grads_given(const Grads *g) {
+    return g && g->w_ih && g->w_hh && g->b_ih && g->b_hh && g->w_out && g->b_out;
+}
+
+// ... and into g_wih ... g_bout of a kernel's argument block.
+template <class Args, class Grads>
+static void head_grads_into(Args &g, const Grads &s) {
+    g.g_wih = s.w_ih; g.g_whh = s.w_hh; g.g_bih = s.b_ih; g.g_bhh = s.b_hh; g.g_wout = s.w_out; g.g_bout = s.b_out;
+}
+
 extern "C" {
 
 int fe_version(void) { return FE_ABI_VERSION; }
@@ -850,12 +863,12 @@ int fe_env_rollout_table(fe_env *env, const double *table, const double *wsum, d
     return launched("fe_env_rollout_table");
 }
 
-// The hidden sizes the MLP kernels are instantiated for (with_nt).
-static bool mlp_h_ok(int32_t H) { return H == 32 || H == 64 || H == 128; }
+// The hidden sizes the MLP kernels and the register-resident LSTM kernels are instantiated for (with_nt).
+static bool resident_h_ok(int32_t H) { return H == 32 || H == 64 || H == 128; }
 
 // What every MLP entry refuses about the network's shape, in `who`'s name.
 static int mlp_shape_checked(int32_t H, int32_t activation, const char *who) {
-    if (!mlp_h_ok(H)) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    if (!resident_h_ok(H)) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
     if (activation < 0 || activation > 2) return fail(FE_ERR_ARG, "%s: activation must be 0 (ELU), 1 (ReLU) or 2 (tanh)", who);
     return FE_OK;
 }
@@ -974,7 +987,7 @@ static MlpHeadKernels mlp_head_kernels(bool deep, bool single, int32_t H) {
 
 int fe_mlp_pack(const float *weight1, int32_t H, int32_t W, float *w1t, float *wpos, void *stream) {
     if (!weight1 || !w1t || !wpos) return fail(FE_ERR_ARG, "fe_mlp_pack: bad argument");
-    if (!mlp_h_ok(H)) return fail(FE_ERR_ARG, "fe_mlp_pack: H must be 32, 64 or 128 (got %d)", (int)H);
+    if (!resident_h_ok(H)) return fail(FE_ERR_ARG, "fe_mlp_pack: H must be 32, 64 or 128 (got %d)", (int)H);
     if (W < 1) return fail(FE_ERR_ARG, "fe_mlp_pack: W must be >= 1 (got %d)", (int)W);
     DeviceGuard guard(device_of(weight1));
     if (int rc = guard.status()) return rc;
@@ -1091,7 +1104,7 @@ static MlpGradLayout mlp_grad_layout(bool deep, int32_t H, int32_t W, int64_t co
 }
 
 static int64_t mlp_grad_workspace_floats(bool deep, int32_t H, int32_t W, int64_t count) {
-    if (!mlp_h_ok(H) || W < 1 || count < 0) return -1;
+    if (!resident_h_ok(H) || W < 1 || count < 0) return -1;
     return count == 0 ? 0 : mlp_grad_layout(deep, H, W, count).total;
 }
 
@@ -1211,6 +1224,24 @@ int fe_mlp2_backward(fe_env *env, const float *logret_f32, const fe_mlp2_weights
     return launched(who, "W2 reduction");
 }
 
+// ---- the LSTM family: the one-output head, the SAC actor and the twin critics, register-resident (H = 32 / 64 / 128) and
+// streamed (H = 256 / 512 / 1024).  An entry and its streamed namesake share one implementation, told which it serves. ----
+// The one-output head's weights as the shared code sees them (after MlpHeadView).  The output bias travels by value or,
+// bout_p non-null, is read on the device (the *_p entries of include/finenvs_amd_optim.h); a backward pass needs neither.
+struct LstmHeadView { const float *whh, *wx, *wout; float bout; const float *bout_p; };
+static bool lstm_view_given(const LstmHeadView &w) { return w.whh && w.wx && w.wout; }
+
+// The SAC actor's weights likewise: the two head biases by value or, non-null, on the device (the *_p and the streamed
+// entries, which refuse a null one before they fill this).
+struct SacActorView { const float *whh, *wx, *wl, *bl, *wmu, *wstd; float bmu, bstd; const float *bmu_p, *bstd_p; };
+static bool sac_view_given(const SacActorView &w) { return w.whh && w.wx && w.wl && w.bl && w.wmu && w.wstd; }
+
+// What an entry refuses when its kernel's workgroup does not fit the LDS at this H.
+static int lds_fits(size_t lds, int32_t H, const char *who) {
+    if (lds <= kMaxLds) return FE_OK;
+    return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+}
+
 // Tile geometry of the fused LSTM kernels (LSTM and SAC heads) for `count` envs (rollout) or descriptors (forward): sets
 // p.N, p.EB, p.num_tiles; returns the workgroup tile's (env, asset) pairs SP, or 0 after fail() when an env's sleeves do
 // not fit one tile.
@@ -1276,8 +1307,8 @@ static int launch_grad(const fe_env *env, const void *kern, size_t lds, int64_t 
 // descriptors (forward).
 static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who, void *stream) {
     const int32_t H = r.H;
-    const bool big = H == 256 || H == 512 || H == 1024;  // weights streamed from L2 (fragment-major whh)
-    if (H != 32 && H != 64 && H != 128 && !big)
+    const bool big = lstm_sgrad_hidden_ok(H);  // weights streamed from L2 (fragment-major whh)
+    if (!resident_h_ok(H) && !big)
         return fail(FE_ERR_ARG, "%s: H must be 32, 64, 128, 256, 512 or 1024 (got %d)", who, (int)H);
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
@@ -1296,7 +1327,7 @@ static int launch_lstm(fe_env *env, LstmArgs &r, int64_t count, const char *who,
 // samples.
 static int launch_sac(fe_env *env, SacArgs &s, int64_t count, const char *who, void *stream) {
     const int32_t H = s.l.H;
-    if (H != 32 && H != 64 && H != 128)
+    if (!resident_h_ok(H))
         return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the SAC head has no streamed or split kernel", who, (int)H);
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
@@ -1311,21 +1342,26 @@ static int launch_sac(fe_env *env, SacArgs &s, int64_t count, const char *who, v
 
 // The *_impl functions serve an entry that takes its output bias by value and its sibling of
 // include/finenvs_amd_optim.h that reads it through a device pointer (bout_p etc. non-null).
-static int rollout_lstm_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                             float bout, const float *bout_p, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src,
-                             double *obs_pos, const float *noise, float std, float *actions_out, float *means_out,
-                             double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
-                             void *stream) {
+// The head's part of a kernel's LstmArgs.
+static void lstm_args(LstmArgs &r, const float *logret_f32, const LstmHeadView &w, int32_t H, int32_t out_activation) {
+    r.lr32 = logret_f32; r.whh = w.whh; r.wx = w.wx; r.wout = w.wout; r.bout = w.bout; r.bout_p = w.bout_p; r.H = H;
+    r.out_act = out_activation;
+}
+
+static int rollout_lstm_impl(fe_env *env, const float *logret_f32, const LstmHeadView &w, int32_t H, int32_t out_activation,
+                             int32_t K, int64_t *obs_src, double *obs_pos, const float *noise, float std, float *actions_out,
+                             float *means_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
+                             double *states_pos_out, void *stream) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm: states_src_out and states_pos_out go together");
     if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "fe_env_rollout_lstm: std must be >= 0 when noise is given");
-    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
+    if (!env || !logret_f32 || !lstm_view_given(w) || !obs_src || !obs_pos || !rewards_out || !dones_out || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm: bad argument");
     if (out_activation < 0 || out_activation > 1) return fail(FE_ERR_ARG, "fe_env_rollout_lstm: out_activation must be 0 (tanh) or 1 (clamp)");
     if (int rc = require_bound(env, "fe_env_rollout_lstm")) return rc;
     LstmArgs r;
-    r.lr32 = logret_f32; r.whh = whh; r.wx = wx; r.wout = wout; r.bout = bout; r.H = H; r.out_act = out_activation; r.K = K;
-    r.bout_p = bout_p;
+    lstm_args(r, logret_f32, w, H, out_activation);
+    r.K = K;
     r.obs_src = obs_src; r.obs_pos = obs_pos; r.actions_out = actions_out; r.rew_out = rewards_out; r.done_out = dones_out;
     r.noise = noise; r.std = std; r.means_out = means_out; r.traj_src = states_src_out; r.traj_pos = states_pos_out;
     r.forward_only = 0;
@@ -1336,7 +1372,7 @@ int fe_env_rollout_lstm(fe_env *env, const float *logret_f32, const float *whh, 
                         float bout, int32_t H, int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos,
                         const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
                         int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
-    return rollout_lstm_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, K, obs_src, obs_pos, noise, std,
+    return rollout_lstm_impl(env, logret_f32, {whh, wx, wout, bout, nullptr}, H, out_activation, K, obs_src, obs_pos, noise, std,
                              actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream);
 }
 
@@ -1345,17 +1381,16 @@ int64_t fe_lstm_split_workspace_floats(int32_t H, int64_t pairs) {
     return 3 * ((pairs + 31) / 32) * (int64_t)H * 32;  // h (two buffers) + c, fragment-major: [column tile][H/8][64][4]
 }
 
-static int rollout_lstm_split_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx,
-                                   const float *wout, float bout, const float *bout_p, int32_t H, int32_t out_activation,
-                                   int32_t K, int64_t *obs_src, double *obs_pos, const float *noise, float std,
-                                   float *actions_out, float *means_out, double *rewards_out, int32_t *dones_out,
+static int rollout_lstm_split_impl(fe_env *env, const float *logret_f32, const LstmHeadView &w, int32_t H,
+                                   int32_t out_activation, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
+                                   float std, float *actions_out, float *means_out, double *rewards_out, int32_t *dones_out,
                                    int64_t *states_src_out, double *states_pos_out, float *workspace, void *stream) {
     if ((states_src_out == nullptr) != (states_pos_out == nullptr))
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: states_src_out and states_pos_out go together");
     if (noise && !(std >= 0.0f)) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: std must be >= 0 when noise is given");
-    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || !rewards_out || !dones_out || !workspace || K < 1)
+    if (!env || !logret_f32 || !lstm_view_given(w) || !obs_src || !obs_pos || !rewards_out || !dones_out || !workspace || K < 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: bad argument");
-    if (H != 256 && H != 512 && H != 1024)
+    if (!lstm_sgrad_hidden_ok(H))
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: H must be 256, 512 or 1024 (got %d)", (int)H);
     if (out_activation < 0 || out_activation > 1)
         return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split: out_activation must be 0 (tanh) or 1 (clamp)");
@@ -1374,7 +1409,7 @@ static int rollout_lstm_split_impl(fe_env *env, const float *logret_f32, const f
     const void *fk = with_bool(single, [](auto S) { return (const void *)fe_lstm_split_finish_kernel<decltype(S)::value>; });
     if (int rc = prepare_big_lds(env->device, fk, lds, "fe_env_rollout_lstm_split")) return rc;
     LstmSplitArgs s;
-    s.a.lr32 = logret_f32; s.a.whh = whh; s.a.wx = wx; s.a.wout = wout; s.a.bout = bout; s.a.bout_p = bout_p; s.a.H = H; s.a.out_act = out_activation;
+    lstm_args(s.a, logret_f32, w, H, out_activation);
     s.a.K = 1; s.a.obs_src = obs_src; s.a.obs_pos = obs_pos; s.a.std = std; s.a.traj_src = states_src_out; s.a.traj_pos = states_pos_out;
     s.a.forward_only = 0;
     s.hbuf = workspace; s.cbuf = workspace + 2 * CT * (int64_t)H * 32; s.pairs = NA;
@@ -1416,22 +1451,21 @@ int fe_env_rollout_lstm_split(fe_env *env, const float *logret_f32, const float 
                               const float *noise, float std, float *actions_out, float *means_out, double *rewards_out,
                               int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, float *workspace,
                               void *stream) {
-    return rollout_lstm_split_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, K, obs_src, obs_pos,
+    return rollout_lstm_split_impl(env, logret_f32, {whh, wx, wout, bout, nullptr}, H, out_activation, K, obs_src, obs_pos,
                                    noise, std, actions_out, means_out, rewards_out, dones_out, states_src_out,
                                    states_pos_out, workspace, stream);
 }
 
-static int lstm_forward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                             float bout, const float *bout_p, int32_t H, int32_t out_activation, const int64_t *obs_src,
-                             const double *obs_pos, int64_t count, float *out, void *stream) {
-    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || !out || count < 0)
+static int lstm_forward_impl(fe_env *env, const float *logret_f32, const LstmHeadView &w, int32_t H, int32_t out_activation,
+                             const int64_t *obs_src, const double *obs_pos, int64_t count, float *out, void *stream) {
+    if (!env || !logret_f32 || !lstm_view_given(w) || !obs_src || !obs_pos || !out || count < 0)
         return fail(FE_ERR_ARG, "fe_lstm_forward: bad argument");
     if (out_activation < 0 || out_activation > 2)
         return fail(FE_ERR_ARG, "fe_lstm_forward: out_activation must be 0 (tanh), 1 (clamp) or 2 (none)");
     if (count == 0) return FE_OK;
     LstmArgs r;
-    r.lr32 = logret_f32; r.whh = whh; r.wx = wx; r.wout = wout; r.bout = bout; r.H = H; r.out_act = out_activation; r.K = 1;
-    r.bout_p = bout_p;
+    lstm_args(r, logret_f32, w, H, out_activation);
+    r.K = 1;
     r.obs_src = const_cast<int64_t *>(obs_src); r.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
     r.actions_out = out; r.rew_out = nullptr; r.done_out = nullptr;
     r.noise = nullptr; r.std = 0.0f; r.means_out = nullptr; r.traj_src = nullptr; r.traj_pos = nullptr;
@@ -1442,7 +1476,7 @@ static int lstm_forward_impl(fe_env *env, const float *logret_f32, const float *
 int fe_lstm_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout, float bout,
                     int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
                     float *out, void *stream) {
-    return lstm_forward_impl(env, logret_f32, whh, wx, wout, bout, nullptr, H, out_activation, obs_src, obs_pos, count, out,
+    return lstm_forward_impl(env, logret_f32, {whh, wx, wout, bout, nullptr}, H, out_activation, obs_src, obs_pos, count, out,
                              stream);
 }
 
@@ -1794,85 +1828,21 @@ int fe_replay_sample_c(fe_env *env, const fe_replay_ring *ring, const int64_t *c
     return replay_sample_impl(env, ring, 0, 0, cursor, indices, count, states, next_states, actions, rewards, dones, stream);
 }
 
-// ---- include/finenvs_amd_sac.h: the SAC actor's head on the LSTM recurrence ----
-static void sac_args(SacArgs &s, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
-                     const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p, const float *bstd_p,
-                     int32_t H) {
-    s.bmu_p = bmu_p; s.bstd_p = bstd_p;
-    s.l.lr32 = logret_f32; s.l.whh = whh; s.l.wx = wx; s.l.wout = nullptr; s.l.bout = 0.0f; s.l.H = H; s.l.out_act = 0;
-    s.l.std = 0.0f;
-    s.wl = wl; s.bl = bl; s.wmu = wmu; s.bmu = bmu; s.wstd = wstd; s.bstd = bstd;
-}
-
-static int rollout_sac_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                            const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p,
-                            const float *bstd_p, int32_t H, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
-                            float *actions_out, float *means_out, float *stds_out, double *rewards_out, int32_t *dones_out,
-                            int64_t *states_src_out, double *states_pos_out, void *stream) {
-    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "fe_env_rollout_sac: states_src_out and states_pos_out go together");
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || !rewards_out ||
-        !dones_out || K < 1)
-        return fail(FE_ERR_ARG, "fe_env_rollout_sac: bad argument");
-    if (int rc = require_bound(env, "fe_env_rollout_sac")) return rc;
-    SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, bmu_p, bstd_p, H);
-    s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
-    s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
-    s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
-    s.stds_out = stds_out; s.logp_out = nullptr;
-    return launch_sac(env, s, env->cfg.N, "fe_env_rollout_sac", stream);
-}
-
-int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                       const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, int32_t K,
-                       int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out, float *means_out,
-                       float *stds_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
-                       double *states_pos_out, void *stream) {
-    return rollout_sac_impl(env, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, nullptr, nullptr, H, K, obs_src, obs_pos,
-                            noise, actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out,
-                            stream);
-}
-
-static int sac_forward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                            const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, const float *bmu_p,
-                            const float *bstd_p, int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count,
-                            const float *noise, float *actions_out, float *log_probs_out, float *means_out, float *stds_out,
-                            void *stream) {
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0)
-        return fail(FE_ERR_ARG, "fe_sac_forward: bad argument");
-    if (!noise && (actions_out || log_probs_out))
-        return fail(FE_ERR_ARG, "fe_sac_forward: actions_out and log_probs_out need noise");
-    if (count == 0) return FE_OK;
-    SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, bmu_p, bstd_p, H);
-    s.l.K = 1;
-    s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
-    s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
-    s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
-    s.stds_out = stds_out; s.logp_out = log_probs_out;
-    return launch_sac(env, s, count, "fe_sac_forward", stream);
-}
-
-int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
-                   const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, const int64_t *obs_src,
-                   const double *obs_pos, int64_t count, const float *noise, float *actions_out, float *log_probs_out,
-                   float *means_out, float *stds_out, void *stream) {
-    return sac_forward_impl(env, logret_f32, whh, wx, wl, bl, wmu, bmu, wstd, bstd, nullptr, nullptr, H, obs_src, obs_pos,
-                            count, noise, actions_out, log_probs_out, means_out, stds_out, stream);
-}
-
-// ---- include/finenvs_amd_critic.h: the twin LSTM critics and their Bellman targets ----
+// ---- include/finenvs_amd_critic.h and include/finenvs_amd_critic_streamed.h: the twin LSTM critics, their Bellman
+// targets and, at H = 256 / 512 / 1024, their streamed forms ----
 static bool critic_weights_ok(const fe_critic_weights *c) { return c && c->whh && c->wx && c->wout && c->bout; }
 
-// The checks both entry points share; `env` is dereferenced only after the ones that need no env.
-static int critic_check(const fe_env *env, const fe_critic_weights *c1, const fe_critic_weights *c2, int32_t H, const char *who) {
-    if (H != 32 && H != 64 && H != 128)
+// The checks the critics' entries share; `env` is dereferenced only after the ones that need no env.
+static int critic_check(const fe_env *env, int32_t H, bool streamed, const char *who) {
+    if (streamed && !lstm_sgrad_hidden_ok(H))
+        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); H = 32, 64 and 128 run the register-resident "
+                    "entries of finenvs_amd_critic.h / finenvs_amd_critic_grad.h", who, (int)H);
+    if (!streamed && !resident_h_ok(H))
         return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the twin critic has no streamed or split kernel", who, (int)H);
     if (env->p.A != 1)
         return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only (the reference's critic for A > 1 "
                     "is one nn.LSTM(5A + A, H) over the whole env, not a per-(env, asset) pair network)", who, (int)env->p.A);
-    return FE_OK;
+    return streamed ? lds_fits(critic_sgrad_forward_lds_bytes(H), H, who) : FE_OK;
 }
 
 // Shared by fe_twin_q_forward and fe_twin_q_target: the split grid -- blockIdx.y = critic -- of fe_twin_q_kernel, each
@@ -1904,322 +1874,9 @@ static void critic_args(CriticArgs &cq, const float *logret_f32, const fe_critic
     for (int i = 0; i < 2; ++i) cq.net[i] = CriticNet{c[i]->whh, c[i]->wx, c[i]->wout, c[i]->bout, q[i]};
 }
 
-int fe_twin_q_forward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                      int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
-                      float *q1_out, float *q2_out, void *stream) {
-    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !obs_src || !obs_pos || !actions ||
-        !q1_out || !q2_out || count < 0)
-        return fail(FE_ERR_ARG, "fe_twin_q_forward: bad argument");
-    if (int rc = critic_check(env, c1, c2, H, "fe_twin_q_forward")) return rc;
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    CriticArgs cq;
-    critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
-    cq.l.obs_src = const_cast<int64_t *>(obs_src); cq.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
-    cq.actions = actions;
-    return launch_twin_q(env, cq, count, "fe_twin_q_forward", stream);
-}
-
-// fe_twin_q_target and fe_twin_q_target_c: the same kernels, `cursor` null for the by-value entry (head / size ignored
-// and unchecked with a cursor: they are read on the device).
-static int twin_q_target_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                              int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *cursor,
-                              const int64_t *indices, int64_t count, const float *next_actions, const float *smooth_noise,
-                              float smooth_std, float smooth_clip, const float *log_probs, const float *alpha, float gamma,
-                              float reward_scale, float *targets_out, float *q1_out, float *q2_out, void *stream) {
-    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
-        !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
-        return fail(FE_ERR_ARG, "fe_twin_q_target: bad argument");
-    if (log_probs && !alpha) return fail(FE_ERR_ARG, "fe_twin_q_target: log_probs (SAC) need alpha");
-    if (smooth_noise && log_probs)
-        return fail(FE_ERR_ARG, "fe_twin_q_target: smooth_noise (TD3) and log_probs (SAC) are exclusive");
-    if (int rc = critic_check(env, c1, c2, H, "fe_twin_q_target")) return rc;
-    const int64_t C = ring->capacity;
-    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
-        return fail(FE_ERR_ARG, "fe_twin_q_target: size %lld / head %lld do not describe a non-empty ring of %lld slots",
-                    (long long)size, (long long)head, (long long)C);
-    if (ring->num_assets != 1) return fail(FE_ERR_ARG, "fe_twin_q_target: the ring holds %d assets, the env 1", (int)ring->num_assets);
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
-    CriticArgs cq;
-    critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
-    cq.indices = indices; cq.ring_src = ring->next_src; cq.ring_pos = ring->next_pos;
-    cq.ring_C = C; cq.start = start; cq.size = size; cq.cursor = cursor;
-    cq.actions = next_actions; cq.smooth_noise = smooth_noise; cq.smooth_std = smooth_std; cq.smooth_clip = smooth_clip;
-    if (int rc = launch_twin_q(env, cq, count, "fe_twin_q_target: critics", stream)) return rc;
-    TwinTargetArgs t;
-    t.q1 = q1_out; t.q2 = q2_out; t.indices = indices; t.ring_rew = ring->rewards; t.ring_done = ring->dones;
-    t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
-    t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
-    t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
-    t.cursor = cursor;
-    hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
-    return launched("fe_twin_q_target: epilogue");
-}
-
-int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                     int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
-                     int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
-                     float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
-                     float *targets_out, float *q1_out, float *q2_out, void *stream) {
-    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
-                              smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out,
-                              q1_out, q2_out, stream);
-}
-
-int fe_twin_q_target_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                       int32_t H, const fe_replay_ring *ring, const int64_t *cursor, const int64_t *indices,
-                       int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
-                       float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
-                       float *targets_out, float *q1_out, float *q2_out, void *stream) {
-    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_c: null cursor");
-    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions, smooth_noise,
-                              smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out, q1_out, q2_out,
-                              stream);
-}
-
-// ---- include/finenvs_amd_critic_grad.h: the twin critics' backward pass ----
-// Workspace: [wt of each critic][partials of each critic][stash of each critic][da of each critic].
-int64_t fe_twin_q_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t groups = grad_tiles(count, critic_grad_max_groups(H)).max_groups;
-    return 2 * (critic_grad_wt_floats(H) + groups * (critic_grad_part_floats(H) + bptt_stash_floats(H, W))) +
-           2 * count;
-}
-
-static bool critic_grads_ok(const fe_critic_grads *g) {
-    return g && g->w_ih && g->w_hh && g->b_ih && g->b_hh && g->w_out && g->b_out;
-}
-
-int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                       int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
-                       const float *dq1, const float *dq2, float *workspace, const fe_critic_grads *grads1,
-                       const fe_critic_grads *grads2, float *d_actions, void *stream) {
-    static const char *who = "fe_twin_q_backward";
-    if (!env || !logret_f32 || !obs_src || !obs_pos || !actions || !workspace || count < 0 ||
-        (dq1 && (!critic_weights_ok(c1) || (grads1 && !critic_grads_ok(grads1)) || (!grads1 && !d_actions))) ||
-        (dq2 && (!critic_weights_ok(c2) || (grads2 && !critic_grads_ok(grads2)) || (!grads2 && !d_actions))))
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (H != 32 && H != 64 && H != 128)
-        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only", who, (int)env->p.A);
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int W = env->p.W;
-    const auto [tiles, max_groups] = grad_tiles(count, critic_grad_max_groups(H));
-    CriticGradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos; g.actions = actions;
-    g.count = count; g.num_tiles = tiles; g.W = W; g.d_actions = d_actions;
-    const fe_critic_weights *cw[2] = {c1, c2};
-    const fe_critic_grads *cg[2] = {grads1, grads2};
-    const float *dq[2] = {dq1, dq2};
-    float *wt = workspace, *part = wt + 2 * critic_grad_wt_floats(H);
-    float *stash = part + 2 * max_groups * critic_grad_part_floats(H);
-    float *da = stash + 2 * max_groups * bptt_stash_floats(H, W);
-    for (int i = 0; i < 2; ++i) {
-        if (!dq[i]) continue;
-        CriticGradNet &n = g.net[g.ncrit];
-        n.whh = cw[i]->whh; n.wx = cw[i]->wx; n.wout = cw[i]->wout; n.dq = dq[i];
-        n.wt = wt + g.ncrit * critic_grad_wt_floats(H);
-        n.part = part + g.ncrit * max_groups * critic_grad_part_floats(H);
-        n.stash = stash + g.ncrit * max_groups * bptt_stash_floats(H, W);
-        n.da = da + g.ncrit * count;
-        if (cg[i]) {
-            n.g_wih = cg[i]->w_ih; n.g_whh = cg[i]->w_hh; n.g_bih = cg[i]->b_ih; n.g_bhh = cg[i]->b_hh;
-            n.g_wout = cg[i]->w_out; n.g_bout = cg[i]->b_out;
-        }
-        ++g.ncrit;
-    }
-    if (g.ncrit == 0) {
-        if (!d_actions) return FE_OK;
-        return launched(who, hipMemsetAsync(d_actions, 0, (size_t)count * sizeof(float), (hipStream_t)stream));
-    }
-    hipLaunchKernelGGL(fe_critic_grad_pack_kernel, dim3(grid_for(critic_grad_wt_floats(H)), g.ncrit), dim3(kBlock), 0,
-                       (hipStream_t)stream, g, H, const_cast<float *>(g.net[0].wt), const_cast<float *>(g.net[1].wt));
-    if (int rc = launched("fe_twin_q_backward: weight transpose")) return rc;
-    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_critic_grad_kernel<decltype(NT)::value>; });
-    if (int rc = launch_grad(env, kern, critic_grad_lds_bytes(H), max_groups, g.ncrit, &g, &g.groups,
-                             "critic gradient kernel: hipFuncSetAttribute / occupancy query", "fe_twin_q_backward: backward",
-                             stream))
-        return rc;
-    const int64_t elems = 4LL * H * (H + 32) + H + 1;
-    const int64_t work = elems > count ? elems : count;
-    hipLaunchKernelGGL(fe_critic_grad_reduce_kernel, dim3(grid_for(work), g.ncrit + 1), dim3(kBlock), 0, (hipStream_t)stream,
-                       g, H);
-    return launched("fe_twin_q_backward: reduction");
-}
-
-// ---- include/finenvs_amd_sac_grad.h: the SAC actor's backward pass ----
-// Workspace: [W_hh^T | W_l^T][partials of every workgroup][stash of every workgroup].
-int64_t fe_sac_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t groups = grad_tiles(count, sac_grad_max_groups(H)).max_groups;
-    return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + bptt_stash_floats(H, W));
-}
-
-static int sac_backward_impl(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                             const float *bl, const float *wmu, const float *wstd, float bstd, const float *bstd_p,
-                             int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
-                             const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
-                             float *workspace, const fe_sac_grads *grads, void *stream) {
-    static const char *who = "fe_sac_backward";
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !wstd || !obs_src || !obs_pos || count < 0 || !noise ||
-        !actions || !stds || (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih || !grads->w_hh ||
-        !grads->b_ih || !grads->b_hh || !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu || !grads->w_std ||
-        !grads->b_std)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (H != 32 && H != 64 && H != 128)
-        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused actor gradient runs A = 1 only (its consumer, the "
-                    "fused twin critic, does)", who, (int)env->p.A);
-    if (count == 0) return FE_OK;
-    const size_t lds = sac_grad_lds_bytes(H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int W = env->p.W;
-    const auto [tiles, max_groups] = grad_tiles(count, sac_grad_max_groups(H));
-    SacGradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
-    g.whh = whh; g.wx = wx; g.wl = wl; g.bl = bl; g.wmu = wmu; g.wstd = wstd; g.bstd = bstd; g.bstd_p = bstd_p;
-    g.noise = noise; g.actions = actions; g.stds = stds; g.d_actions = d_actions; g.d_log_probs = d_log_probs;
-    g.wt = workspace;
-    g.part = g.wt + sac_grad_wt_floats(H);
-    g.stash = g.part + max_groups * sac_grad_part_floats(H);
-    g.count = count; g.num_tiles = tiles; g.W = W;
-    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wl = grads->w_l;
-    g.g_bl = grads->b_l; g.g_wmu = grads->w_mu; g.g_bmu = grads->b_mu; g.g_wstd = grads->w_std; g.g_bstd = grads->b_std;
-    hipLaunchKernelGGL(fe_sac_grad_pack_kernel, dim3(grid_for(sac_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
-                       g, H);
-    if (int rc = launched("fe_sac_backward: weight transpose")) return rc;
-    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_sac_grad_kernel<decltype(NT)::value>; });
-    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
-                             "SAC gradient kernel: hipFuncSetAttribute / occupancy query", "fe_sac_backward: backward", stream))
-        return rc;
-    hipLaunchKernelGGL(fe_sac_grad_reduce_kernel, dim3(grid_for(sac_grad_part_floats(H))), dim3(kBlock), 0,
-                       (hipStream_t)stream, g, H);
-    return launched("fe_sac_backward: reduction");
-}
-
-int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
-                    const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H,
-                    const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
-                    const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
-                    float *workspace, const fe_sac_grads *grads, void *stream) {
-    (void)bmu;  // the gradient does not depend on it
-    return sac_backward_impl(env, logret_f32, whh, wx, wl, bl, wmu, wstd, bstd, nullptr, H, obs_src, obs_pos, count, noise,
-                             actions, stds, d_actions, d_log_probs, workspace, grads, stream);
-}
-
-// ---- include/finenvs_amd_lstm_grad.h: the one-output LSTM head's backward pass ----
-// Workspace: [W_hh^T][partials of every workgroup][stash of every workgroup].
-int64_t fe_lstm_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if ((H != 32 && H != 64 && H != 128) || W < 1 || count < 0) return -1;
-    const int64_t groups = grad_tiles(count, lstm_grad_max_groups(H)).max_groups;
-    return lstm_grad_wt_floats(H) + groups * (lstm_grad_part_floats(H) + bptt_stash_floats(H, W));
-}
-
-int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                     int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
-                     const float *outputs, const float *d_outputs, float *workspace, const fe_lstm_grads *grads,
-                     void *stream) {
-    static const char *who = "fe_lstm_backward";
-    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || count < 0 || !d_outputs || !workspace ||
-        !grads || !grads->w_ih || !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_out || !grads->b_out)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (out_activation != 0 && out_activation != 2)
-        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on "
-                    "(got %d)", who, (int)out_activation);
-    if (out_activation == 0 && !outputs)
-        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_lstm_forward returned", who);
-    if (H != 32 && H != 64 && H != 128)
-        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the streamed-weight forward of H >= 256 has no "
-                    "register-resident recurrence to mirror", who, (int)H);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused twin "
-                    "critic does)", who, (int)env->p.A);
-    if (count == 0) return FE_OK;
-    const size_t lds = lstm_grad_lds_bytes(H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int W = env->p.W;
-    const auto [tiles, max_groups] = grad_tiles(count, lstm_grad_max_groups(H));
-    LstmGradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
-    g.whh = whh; g.wx = wx; g.wout = wout; g.outputs = outputs; g.d_outputs = d_outputs;
-    g.wt = workspace;
-    g.part = g.wt + lstm_grad_wt_floats(H);
-    g.stash = g.part + max_groups * lstm_grad_part_floats(H);
-    g.count = count; g.num_tiles = tiles; g.W = W; g.out_act = out_activation;
-    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_out;
-    g.g_bout = grads->b_out;
-    hipLaunchKernelGGL(fe_lstm_grad_pack_kernel, dim3(grid_for(lstm_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
-                       g, H);
-    if (int rc = launched("fe_lstm_backward: weight transpose")) return rc;
-    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_lstm_grad_kernel<decltype(NT)::value>; });
-    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
-                             "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query", "fe_lstm_backward: backward",
-                             stream))
-        return rc;
-    hipLaunchKernelGGL(fe_lstm_grad_reduce_kernel, dim3(grid_for(lstm_grad_part_floats(H))), dim3(kBlock), 0,
-                       (hipStream_t)stream, g, H);
-    return launched("fe_lstm_backward: reduction");
-}
-
-
-// ---- include/finenvs_amd_lstm_grad_streamed.h: the one-output LSTM head's backward pass at H = 256 / 512 / 1024 ----
-int64_t fe_lstm_streamed_grad_chunk_pairs(int32_t H, int32_t W) {
-    if (!lstm_sgrad_hidden_ok(H) || W < 1) return -1;
-    return lstm_sgrad_chunk_pairs(H, W);
-}
-
-// Workspace: [W_hh^T][split sums][head block sums][gates][c][h_{t-1} | x_t | 1][h_W][dh][dc], the last six for the pairs
-// of one pass.
-int64_t fe_lstm_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
-    if (!lstm_sgrad_hidden_ok(H) || W < 1 || count < 0) return -1;
-    const int64_t pp = lstm_sgrad_padded_pairs(H, W, count);
-    return lstm_sgrad_wt_floats(H) + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H) +
-           lstm_sgrad_head_blocks(pp) * (H + 32) + pp * (lstm_sgrad_pair_floats(H, W) + 3LL * H);
-}
-
-// ---- what fe_lstm_backward_streamed and fe_twin_q_backward_streamed (and the streamed critics' forward) share ----
-// wt | part | hpart | gates from the workspace: the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest
-// pass (pp pairs).  g.W is set.
-static void sgrad_carve(LstmSGradArgs &g, float *workspace, int32_t H, int64_t pp) {
-    g.wt = workspace;
-    g.part = g.wt + lstm_sgrad_wt_floats(H);
-    g.hpart = g.part + lstm_sgrad_splits(H, g.W, pp) * lstm_sgrad_part_floats(H);
-    g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
-}
-
-// The chunk that starts at pair c0 of `count`: its sizes, its buffers behind g.gates, and whether it is the first.
-static void sgrad_chunk(LstmSGradArgs &g, int32_t H, int64_t c0, int64_t count, int64_t chunk) {
-    const int64_t W = g.W;
-    g.cnt = count - c0 < chunk ? count - c0 : chunk;
-    g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
-    g.splits = lstm_sgrad_splits(H, g.W, g.pp);
-    g.cst = g.gates + W * g.pp * 4 * H;
-    g.vst = g.cst + W * g.pp * H;
-    g.hw = g.vst + W * g.pp * (H + 32);
-    g.dh = g.hw + g.pp * H;
-    g.dc = g.dh + g.pp * H;
-    g.first = c0 == 0;
-}
-
-// One launch of a recurrence kernel (kLstmBlock threads, `a` its one argument) over `tiles` 32-pair tiles: at most the
-// resident workgroups, each looping over its tiles.  `what` names the kernel in a preparation error, `step` the launch.
+// One launch of a streamed recurrence kernel (kLstmBlock threads, `a` its one argument) over `tiles` 32-pair tiles: at
+// most the resident workgroups, each looping over its tiles.  `what` names the kernel in a preparation error, `step` the
+// launch.
 static int launch_sgrad_forward(const fe_env *env, const void *kern, size_t lds, void *a, int64_t tiles, const char *what,
                                 const char *step, hipStream_t st) {
     int per_cu = 0;
@@ -2232,14 +1889,180 @@ static int launch_sgrad_forward(const fe_env *env, const void *kern, size_t lds,
                                           args, lds, st));
 }
 
+static const char *const kCriticSGradPrepare = "streamed critic kernel: hipFuncSetAttribute / occupancy query";
+
+// The streamed critics' recurrence kernel, without the stash (values, targets) or with it (backward).  Defined further
+// down, where the code object has these instantiations: it lists them as the host code first names them (mlp_head_kernels).
+static const void *critic_sgrad_kernel(int32_t H, bool stash);
+
+// The streamed counterpart of launch_twin_q: the forward-only recurrence for both critics, one after the other (a:
+// descriptors, actions and ring already set).
+static int launch_twin_q_streamed(fe_env *env, CriticSGradArgs &a, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                                  int32_t H, int64_t count, float *q1_out, float *q2_out, const char *who, void *stream) {
+    const void *kern = critic_sgrad_kernel(H, /*stash=*/false);
+    const fe_critic_weights *c[2] = {c1, c2};
+    float *q[2] = {q1_out, q2_out};
+    a.g.W = env->p.W; a.g.cnt = count; a.g.pp = (count + 31) / 32 * 32;
+    for (int i = 0; i < 2; ++i) {
+        a.g.whh = c[i]->whh; a.g.wx = c[i]->wx; a.g.wout = c[i]->wout; a.bout = c[i]->bout; a.q_out = q[i];
+        if (int rc = launch_sgrad_forward(env, kern, critic_sgrad_forward_lds_bytes(H), &a, a.g.pp / 32, kCriticSGradPrepare, who,
+                                          (hipStream_t)stream))
+            return rc;
+    }
+    return FE_OK;
+}
+
+// fe_twin_q_forward and fe_twin_q_forward_streamed
+static int twin_q_forward_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                               int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                               float *q1_out, float *q2_out, void *stream, bool streamed, const char *who) {
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !obs_src || !obs_pos || !actions ||
+        !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = critic_check(env, H, streamed, who)) return rc;
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    if (streamed) {
+        CriticSGradArgs a;
+        memset(&a, 0, sizeof(a));
+        a.g.lr32 = logret_f32; a.g.obs_src = obs_src; a.g.obs_pos = obs_pos; a.actions = actions;
+        return launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, who, stream);
+    }
+    CriticArgs cq;
+    critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
+    cq.l.obs_src = const_cast<int64_t *>(obs_src); cq.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
+    cq.actions = actions;
+    return launch_twin_q(env, cq, count, who, stream);
+}
+
+int fe_twin_q_forward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                      int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                      float *q1_out, float *q2_out, void *stream) {
+    return twin_q_forward_impl(env, logret_f32, c1, c2, H, obs_src, obs_pos, actions, count, q1_out, q2_out, stream, false,
+                               "fe_twin_q_forward");
+}
+
+int fe_twin_q_forward_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                               const fe_critic_weights *c2, int32_t H, const int64_t *obs_src, const double *obs_pos,
+                               const float *actions, int64_t count, float *q1_out, float *q2_out, void *stream) {
+    return twin_q_forward_impl(env, logret_f32, c1, c2, H, obs_src, obs_pos, actions, count, q1_out, q2_out, stream, true,
+                               "fe_twin_q_forward_streamed");
+}
+
+// fe_twin_q_target, fe_twin_q_target_streamed and their _c forms: `cursor` null for a by-value entry (head / size ignored
+// and unchecked with a cursor: they are read on the device).  `who`: "fe_twin_q_target" or "fe_twin_q_target_streamed".
+static int twin_q_target_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                              int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *cursor,
+                              const int64_t *indices, int64_t count, const float *next_actions, const float *smooth_noise,
+                              float smooth_std, float smooth_clip, const float *log_probs, const float *alpha, float gamma,
+                              float reward_scale, float *targets_out, float *q1_out, float *q2_out, void *stream,
+                              bool streamed, const char *who) {
+    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
+        !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (log_probs && !alpha) return fail(FE_ERR_ARG, "%s: log_probs (SAC) need alpha", who);
+    if (smooth_noise && log_probs)
+        return fail(FE_ERR_ARG, "%s: smooth_noise (TD3) and log_probs (SAC) are exclusive", who);
+    if (int rc = critic_check(env, H, streamed, who)) return rc;
+    const int64_t C = ring->capacity;
+    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
+        return fail(FE_ERR_ARG, "%s: size %lld / head %lld do not describe a non-empty ring of %lld slots", who,
+                    (long long)size, (long long)head, (long long)C);
+    if (ring->num_assets != 1) return fail(FE_ERR_ARG, "%s: the ring holds %d assets, the env 1", who, (int)ring->num_assets);
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
+    const auto sampled = [&](auto &x) {  // the next states' descriptors in the ring and the actions taken there
+        x.indices = indices; x.ring_src = ring->next_src; x.ring_pos = ring->next_pos;
+        x.ring_C = C; x.start = start; x.size = size; x.cursor = cursor;
+        x.actions = next_actions; x.smooth_noise = smooth_noise; x.smooth_std = smooth_std; x.smooth_clip = smooth_clip;
+    };
+    if (streamed) {
+        CriticSGradArgs a;
+        memset(&a, 0, sizeof(a));
+        a.g.lr32 = logret_f32;
+        sampled(a);
+        if (int rc = launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, "fe_twin_q_target_streamed: critics", stream))
+            return rc;
+    } else {
+        CriticArgs cq;
+        critic_args(cq, logret_f32, c1, c2, H, q1_out, q2_out);
+        sampled(cq);
+        if (int rc = launch_twin_q(env, cq, count, "fe_twin_q_target: critics", stream)) return rc;
+    }
+    TwinTargetArgs t;
+    t.q1 = q1_out; t.q2 = q2_out; t.indices = indices; t.ring_rew = ring->rewards; t.ring_done = ring->dones;
+    t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
+    t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
+    t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
+    t.cursor = cursor;
+    hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
+    return launched(streamed ? "fe_twin_q_target_streamed: epilogue" : "fe_twin_q_target: epilogue");
+}
+
+int fe_twin_q_target(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                     int32_t H, const fe_replay_ring *ring, int64_t head, int64_t size, const int64_t *indices,
+                     int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
+                     float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
+                     float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
+                              smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out,
+                              q1_out, q2_out, stream, false, "fe_twin_q_target");
+}
+
+int fe_twin_q_target_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                       int32_t H, const fe_replay_ring *ring, const int64_t *cursor, const int64_t *indices,
+                       int64_t count, const float *next_actions, const float *smooth_noise, float smooth_std,
+                       float smooth_clip, const float *log_probs, const float *alpha, float gamma, float reward_scale,
+                       float *targets_out, float *q1_out, float *q2_out, void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_c: null cursor");
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions, smooth_noise,
+                              smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out, q1_out, q2_out,
+                              stream, false, "fe_twin_q_target");
+}
+
+int fe_twin_q_target_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                              const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, int64_t head,
+                              int64_t size, const int64_t *indices, int64_t count, const float *next_actions,
+                              const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
+                              const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
+                              float *q2_out, void *stream) {
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
+                              smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out,
+                              q1_out, q2_out, stream, true, "fe_twin_q_target_streamed");
+}
+
+int fe_twin_q_target_streamed_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
+                                const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, const int64_t *cursor,
+                                const int64_t *indices, int64_t count, const float *next_actions,
+                                const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
+                                const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
+                                float *q2_out, void *stream) {
+    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_streamed_c: null cursor");
+    return twin_q_target_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions, smooth_noise,
+                              smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale, targets_out, q1_out, q2_out,
+                              stream, true, "fe_twin_q_target_streamed");
+}
+
+// ---- what the streamed backward passes (head, twin critics, SAC actor at H = 256 / 512 / 1024) share ----
+// wt | part | hpart | gates from the workspace: the layout of fe_lstm_streamed_grad_workspace_floats, sized by the largest
+// pass (pp pairs).  g.W is set.
+static void sgrad_carve(LstmSGradArgs &g, float *workspace, int32_t H, int64_t pp) {
+    g.wt = workspace;
+    g.part = g.wt + lstm_sgrad_wt_floats(H);
+    g.hpart = g.part + lstm_sgrad_splits(H, g.W, pp) * lstm_sgrad_part_floats(H);
+    g.gates = g.hpart + lstm_sgrad_head_blocks(pp) * (H + 32);
+}
+
 // A chunk after its recurrence: head -> (dz [, dh]) x W -> [d_actions] -> [weight contraction -> final write], every launch
 // reported as "<who>: <stage>".  `da`: the critic's argument block around g when d_actions are wanted, else null.
 // `final_kernel` null: a frozen critic.
 // `sac`: the SAC actor's argument block around g (g IS sac->g): its head stages (z, head, dh_W) replace the one-output
 // head's, its last-layer contraction follows the LSTM's and its final kernel writes all ten tensors (final_kernel unused).
 static int sgrad_backward_chunk(const char *who, LstmSGradArgs &g, int32_t H, const CriticSGradArgs *da,
-                                void (*final_kernel)(LstmSGradArgs, int32_t), hipStream_t st,
-                                const SacSGradArgs *sac = nullptr) {
+                                void (*final_kernel)(LstmSGradArgs, int32_t), hipStream_t st, const SacSGradArgs *sac) {
     const int W = g.W;
     const int64_t tiles = g.pp / 32;
     if (sac) {
@@ -2285,169 +2108,45 @@ static int sgrad_backward_chunk(const char *who, LstmSGradArgs &g, int32_t H, co
     return launched(who, "final write");
 }
 
-int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
-                              int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
-                              int64_t count, const float *outputs, const float *d_outputs, float *workspace,
-                              const fe_lstm_grads *grads, void *stream) {
-    static const char *who = "fe_lstm_backward_streamed";
-    if (!env || !logret_f32 || !whh || !wx || !wout || !obs_src || !obs_pos || count < 0 || !d_outputs || !workspace ||
-        !grads || !grads->w_ih || !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_out || !grads->b_out)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (out_activation != 0 && out_activation != 2)
-        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on "
-                    "(got %d)", who, (int)out_activation);
-    if (out_activation == 0 && !outputs)
-        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_lstm_forward returned", who);
-    if (!lstm_sgrad_hidden_ok(H))
-        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); fe_lstm_backward runs H = 32, 64 and 128", who,
-                    (int)H);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused twin "
-                    "critic does)", who, (int)env->p.A);
-    if (count == 0) return FE_OK;
-    const size_t lds = lstm_sgrad_forward_lds_bytes(H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int W = env->p.W;
-    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
-    hipStream_t st = (hipStream_t)stream;
-    LstmSGradArgs g;
-    memset(&g, 0, sizeof(g));
-    g.lr32 = logret_f32; g.whh = whh; g.wx = wx; g.wout = wout; g.W = W; g.out_act = out_activation;
-    sgrad_carve(g, workspace, H, pp);
-    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wout = grads->w_out;
-    g.g_bout = grads->b_out;
-    hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
-    if (int rc = launched("fe_lstm_backward_streamed: weight transpose")) return rc;
-    const void *kern = with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_lstm_sgrad_forward_kernel<decltype(NT)::value>; });
-    // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
+// A streamed backward pass over `count` pairs, chunk by chunk in ascending order: the first chunk overwrites the
+// gradients, the later ones add to them.  Per chunk: g's sizes, its buffers behind g.gates and its descriptors, then what
+// `at(c0)` points the caller's own per-pair arrays at, the recurrence (`kern` on `fwd`, which is g or the argument block
+// around it; `what` names the kernel in a preparation error) and sgrad_backward_chunk with `da`, `final_kernel`, `sac`.
+extern "C++" {  // (a template)
+template <class F>
+static int sgrad_chunks(const fe_env *env, const char *who, LstmSGradArgs &g, int32_t H, int64_t count, const int64_t *obs_src,
+                        const double *obs_pos, const void *kern, size_t lds, void *fwd, const char *what,
+                        const CriticSGradArgs *da, void (*final_kernel)(LstmSGradArgs, int32_t), const SacSGradArgs *sac,
+                        hipStream_t st, F &&at) {
+    char step[64];
+    snprintf(step, sizeof(step), "%s: recurrence", who);
+    const int64_t W = g.W, chunk = lstm_sgrad_chunk_pairs(H, g.W);
     for (int64_t c0 = 0; c0 < count; c0 += chunk) {
-        sgrad_chunk(g, H, c0, count, chunk);
+        g.cnt = count - c0 < chunk ? count - c0 : chunk;
+        g.pp = (g.cnt + 31) / 32 * 32;  // the last chunk may be shorter: same buffers, fewer rows of them
+        g.splits = lstm_sgrad_splits(H, g.W, g.pp);
+        g.cst = g.gates + W * g.pp * 4 * H;
+        g.vst = g.cst + W * g.pp * H;
+        g.hw = g.vst + W * g.pp * (H + 32);
+        g.dh = g.hw + g.pp * H;
+        g.dc = g.dh + g.pp * H;
+        g.first = c0 == 0;
         g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0;
-        g.outputs = outputs ? outputs + c0 : nullptr; g.d_outputs = d_outputs + c0;
-        if (int rc = launch_sgrad_forward(env, kern, lds, &g, g.pp / 32,
-                                          "streamed LSTM head gradient kernel: hipFuncSetAttribute / occupancy query",
-                                          "fe_lstm_backward_streamed: recurrence", st))
-            return rc;
-        if (int rc = sgrad_backward_chunk(who, g, H, nullptr, fe_lstm_sgrad_final_kernel, st)) return rc;
+        at(c0);
+        if (int rc = launch_sgrad_forward(env, kern, lds, fwd, g.pp / 32, what, step, st)) return rc;
+        if (int rc = sgrad_backward_chunk(who, g, H, da, final_kernel, st, sac)) return rc;
     }
     return FE_OK;
 }
+}  // extern "C++"
 
-// ---- include/finenvs_amd_critic_streamed.h: the twin critics at H = 256 / 512 / 1024 ----
-static int critic_streamed_check(const fe_env *env, int32_t H, const char *who) {
-    if (!lstm_sgrad_hidden_ok(H))
-        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); H = 32, 64 and 128 run the register-resident "
-                    "entries of finenvs_amd_critic.h / finenvs_amd_critic_grad.h", who, (int)H);
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only (the reference's critic for A > 1 "
-                    "is one nn.LSTM(5A + A, H) over the whole env, not a per-(env, asset) pair network)", who, (int)env->p.A);
-    if (critic_sgrad_forward_lds_bytes(H) > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H,
-                    critic_sgrad_forward_lds_bytes(H), kMaxLds);
-    return FE_OK;
-}
-
-static const char *const kCriticSGradPrepare = "streamed critic kernel: hipFuncSetAttribute / occupancy query";
-
-// The forward-only recurrence for both critics, one after the other (a: descriptors, actions and ring already set).
-static int launch_twin_q_streamed(fe_env *env, CriticSGradArgs &a, const fe_critic_weights *c1, const fe_critic_weights *c2,
-                                  int32_t H, int64_t count, float *q1_out, float *q2_out, const char *who, void *stream) {
-    const void *kern = critic_sgrad_forward_kernel_for<false>(H);
-    const fe_critic_weights *c[2] = {c1, c2};
-    float *q[2] = {q1_out, q2_out};
-    a.g.W = env->p.W; a.g.cnt = count; a.g.pp = (count + 31) / 32 * 32;
-    for (int i = 0; i < 2; ++i) {
-        a.g.whh = c[i]->whh; a.g.wx = c[i]->wx; a.g.wout = c[i]->wout; a.bout = c[i]->bout; a.q_out = q[i];
-        if (int rc = launch_sgrad_forward(env, kern, critic_sgrad_forward_lds_bytes(H), &a, a.g.pp / 32, kCriticSGradPrepare, who,
-                                          (hipStream_t)stream))
-            return rc;
-    }
-    return FE_OK;
-}
-
-int fe_twin_q_forward_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
-                               const fe_critic_weights *c2, int32_t H, const int64_t *obs_src, const double *obs_pos,
-                               const float *actions, int64_t count, float *q1_out, float *q2_out, void *stream) {
-    static const char *who = "fe_twin_q_forward_streamed";
-    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !obs_src || !obs_pos || !actions ||
-        !q1_out || !q2_out || count < 0)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = critic_streamed_check(env, H, who)) return rc;
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    CriticSGradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.lr32 = logret_f32; a.g.obs_src = obs_src; a.g.obs_pos = obs_pos; a.actions = actions;
-    return launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, who, stream);
-}
-
-// fe_twin_q_target_streamed and fe_twin_q_target_streamed_c: `cursor` null for the by-value entry (as twin_q_target_impl).
-static int twin_q_target_streamed_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
-                                       const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, int64_t head,
-                                       int64_t size, const int64_t *cursor, const int64_t *indices, int64_t count,
-                                       const float *next_actions, const float *smooth_noise, float smooth_std,
-                                       float smooth_clip, const float *log_probs, const float *alpha, float gamma,
-                                       float reward_scale, float *targets_out, float *q1_out, float *q2_out, void *stream) {
-    static const char *who = "fe_twin_q_target_streamed";
-    if (!env || !logret_f32 || !critic_weights_ok(c1) || !critic_weights_ok(c2) || !replay_ring_ok(ring) || !indices ||
-        !next_actions || !targets_out || !q1_out || !q2_out || count < 0)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (log_probs && !alpha) return fail(FE_ERR_ARG, "%s: log_probs (SAC) need alpha", who);
-    if (smooth_noise && log_probs)
-        return fail(FE_ERR_ARG, "%s: smooth_noise (TD3) and log_probs (SAC) are exclusive", who);
-    if (int rc = critic_streamed_check(env, H, who)) return rc;
-    const int64_t C = ring->capacity;
-    if (!cursor && (size < 1 || size > C || head < 0 || head >= C))
-        return fail(FE_ERR_ARG, "%s: size %lld / head %lld do not describe a non-empty ring of %lld slots", who,
-                    (long long)size, (long long)head, (long long)C);
-    if (ring->num_assets != 1) return fail(FE_ERR_ARG, "%s: the ring holds %d assets, the env 1", who, (int)ring->num_assets);
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    const int64_t start = cursor ? 0 : ((head - size) % C + C) % C;
-    CriticSGradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.g.lr32 = logret_f32; a.actions = next_actions;
-    a.indices = indices; a.ring_src = ring->next_src; a.ring_pos = ring->next_pos;
-    a.ring_C = C; a.start = start; a.size = size; a.cursor = cursor;
-    a.smooth_noise = smooth_noise; a.smooth_std = smooth_std; a.smooth_clip = smooth_clip;
-    if (int rc = launch_twin_q_streamed(env, a, c1, c2, H, count, q1_out, q2_out, "fe_twin_q_target_streamed: critics", stream))
-        return rc;
-    TwinTargetArgs t;
-    t.q1 = q1_out; t.q2 = q2_out; t.indices = indices; t.ring_rew = ring->rewards; t.ring_done = ring->dones;
-    t.ring_C = C; t.start = start; t.size = size; t.count = count; t.log_probs = log_probs; t.alpha = alpha;
-    t.gamma = gamma; t.reward_scale = reward_scale; t.targets = targets_out;
-    t.errors = reinterpret_cast<unsigned long long *>(ring->errors);
-    t.cursor = cursor;
-    hipLaunchKernelGGL(fe_twin_q_target_kernel, dim3(grid_for(count)), dim3(kBlock), 0, (hipStream_t)stream, t);
-    return launched("fe_twin_q_target_streamed: epilogue");
-}
-
-int fe_twin_q_target_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
-                              const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, int64_t head,
-                              int64_t size, const int64_t *indices, int64_t count, const float *next_actions,
-                              const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
-                              const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
-                              float *q2_out, void *stream) {
-    return twin_q_target_streamed_impl(env, logret_f32, c1, c2, H, ring, head, size, nullptr, indices, count, next_actions,
-                                       smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale,
-                                       targets_out, q1_out, q2_out, stream);
-}
-
-int fe_twin_q_target_streamed_c(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
-                                const fe_critic_weights *c2, int32_t H, const fe_replay_ring *ring, const int64_t *cursor,
-                                const int64_t *indices, int64_t count, const float *next_actions,
-                                const float *smooth_noise, float smooth_std, float smooth_clip, const float *log_probs,
-                                const float *alpha, float gamma, float reward_scale, float *targets_out, float *q1_out,
-                                float *q2_out, void *stream) {
-    if (!cursor) return fail(FE_ERR_ARG, "fe_twin_q_target_streamed_c: null cursor");
-    return twin_q_target_streamed_impl(env, logret_f32, c1, c2, H, ring, 0, 0, cursor, indices, count, next_actions,
-                                       smooth_noise, smooth_std, smooth_clip, log_probs, alpha, gamma, reward_scale,
-                                       targets_out, q1_out, q2_out, stream);
+// ---- include/finenvs_amd_critic_grad.h and the backward entry of include/finenvs_amd_critic_streamed.h ----
+// Workspace: [wt of each critic][partials of each critic][stash of each critic][da of each critic].
+int64_t fe_twin_q_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!resident_h_ok(H) || W < 1 || count < 0) return -1;
+    const int64_t groups = grad_tiles(count, critic_grad_max_groups(H)).max_groups;
+    return 2 * (critic_grad_wt_floats(H) + groups * (critic_grad_part_floats(H) + bptt_stash_floats(H, W))) +
+           2 * count;
 }
 
 // The workspace of fe_lstm_backward_streamed, used by one critic after the other; d_actions is written in place.
@@ -2455,69 +2154,325 @@ int64_t fe_twin_q_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t c
     return fe_lstm_streamed_grad_workspace_floats(H, W, count);
 }
 
+// fe_twin_q_backward and fe_twin_q_backward_streamed.  A critic without dq takes no part; one without grads is frozen
+// and only passes d_actions on.
+static int twin_q_backward_impl(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                                int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                                const float *dq1, const float *dq2, float *workspace, const fe_critic_grads *grads1,
+                                const fe_critic_grads *grads2, float *d_actions, void *stream, bool streamed, const char *who) {
+    if (!env || !logret_f32 || !obs_src || !obs_pos || !actions || !workspace || count < 0 ||
+        (dq1 && (!critic_weights_ok(c1) || (grads1 && !head_grads_given(grads1)) || (!grads1 && !d_actions))) ||
+        (dq2 && (!critic_weights_ok(c2) || (grads2 && !head_grads_given(grads2)) || (!grads2 && !d_actions))))
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (streamed) {
+        if (int rc = critic_check(env, H, true, who)) return rc;
+    } else {  // (the resident entry words its two refusals more briefly than critic_check)
+        if (!resident_h_ok(H)) return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+        if (env->p.A != 1)
+            return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused critic runs A = 1 only", who, (int)env->p.A);
+    }
+    if (count == 0) return FE_OK;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const fe_critic_weights *cw[2];
+    const fe_critic_grads *cg[2];
+    const float *dq[2];
+    int ncrit = 0;  // the critics that take part, in order
+    if (dq1) { cw[ncrit] = c1; cg[ncrit] = grads1; dq[ncrit++] = dq1; }
+    if (dq2) { cw[ncrit] = c2; cg[ncrit] = grads2; dq[ncrit++] = dq2; }
+    if (ncrit == 0) {
+        if (!d_actions) return FE_OK;
+        return launched(who, hipMemsetAsync(d_actions, 0, (size_t)count * sizeof(float), st));
+    }
+    const int W = env->p.W;
+    if (streamed) {
+        const int64_t pp = lstm_sgrad_padded_pairs(H, W, count);
+        const void *kern = critic_sgrad_kernel(H, /*stash=*/true);
+        for (int i = 0; i < ncrit; ++i) {
+            CriticSGradArgs a;
+            memset(&a, 0, sizeof(a));
+            LstmSGradArgs &g = a.g;
+            g.lr32 = logret_f32; g.whh = cw[i]->whh; g.wx = cw[i]->wx; g.wout = cw[i]->wout; g.W = W; g.out_act = 2;
+            sgrad_carve(g, workspace, H, pp);
+            if (cg[i]) head_grads_into(g, *cg[i]);
+            a.da_add = d_actions && i > 0;  // a critic before this one has written d_actions
+            hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
+            if (int rc = launched(who, "weight transpose")) return rc;
+            const int rc = sgrad_chunks(env, who, g, H, count, obs_src, obs_pos, kern, critic_sgrad_forward_lds_bytes(H), &a,
+                                        kCriticSGradPrepare, d_actions ? &a : nullptr,
+                                        cg[i] ? fe_critic_sgrad_final_kernel : nullptr, nullptr, st, [&](int64_t c0) {
+                                            g.d_outputs = dq[i] + c0;
+                                            a.actions = actions + c0;
+                                            a.da = d_actions ? d_actions + c0 : nullptr;
+                                        });
+            if (rc) return rc;
+        }
+        return FE_OK;
+    }
+    const auto [tiles, max_groups] = grad_tiles(count, critic_grad_max_groups(H));
+    CriticGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos; g.actions = actions;
+    g.count = count; g.num_tiles = tiles; g.W = W; g.d_actions = d_actions;
+    float *wt = workspace, *part = wt + 2 * critic_grad_wt_floats(H);
+    float *stash = part + 2 * max_groups * critic_grad_part_floats(H);
+    float *da = stash + 2 * max_groups * bptt_stash_floats(H, W);
+    g.ncrit = ncrit;
+    for (int i = 0; i < ncrit; ++i) {
+        CriticGradNet &n = g.net[i];
+        n.whh = cw[i]->whh; n.wx = cw[i]->wx; n.wout = cw[i]->wout; n.dq = dq[i];
+        n.wt = wt + i * critic_grad_wt_floats(H);
+        n.part = part + i * max_groups * critic_grad_part_floats(H);
+        n.stash = stash + i * max_groups * bptt_stash_floats(H, W);
+        n.da = da + i * count;
+        if (cg[i]) head_grads_into(n, *cg[i]);
+    }
+    hipLaunchKernelGGL(fe_critic_grad_pack_kernel, dim3(grid_for(critic_grad_wt_floats(H)), g.ncrit), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H, const_cast<float *>(g.net[0].wt), const_cast<float *>(g.net[1].wt));
+    if (int rc = launched("fe_twin_q_backward: weight transpose")) return rc;
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_critic_grad_kernel<decltype(NT)::value>; });
+    if (int rc = launch_grad(env, kern, critic_grad_lds_bytes(H), max_groups, g.ncrit, &g, &g.groups,
+                             "critic gradient kernel: hipFuncSetAttribute / occupancy query", "fe_twin_q_backward: backward",
+                             stream))
+        return rc;
+    const int64_t elems = 4LL * H * (H + 32) + H + 1;
+    const int64_t work = elems > count ? elems : count;
+    hipLaunchKernelGGL(fe_critic_grad_reduce_kernel, dim3(grid_for(work), g.ncrit + 1), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    return launched("fe_twin_q_backward: reduction");
+}
+
+int fe_twin_q_backward(fe_env *env, const float *logret_f32, const fe_critic_weights *c1, const fe_critic_weights *c2,
+                       int32_t H, const int64_t *obs_src, const double *obs_pos, const float *actions, int64_t count,
+                       const float *dq1, const float *dq2, float *workspace, const fe_critic_grads *grads1,
+                       const fe_critic_grads *grads2, float *d_actions, void *stream) {
+    return twin_q_backward_impl(env, logret_f32, c1, c2, H, obs_src, obs_pos, actions, count, dq1, dq2, workspace, grads1,
+                                grads2, d_actions, stream, false, "fe_twin_q_backward");
+}
+
 int fe_twin_q_backward_streamed(fe_env *env, const float *logret_f32, const fe_critic_weights *c1,
                                 const fe_critic_weights *c2, int32_t H, const int64_t *obs_src, const double *obs_pos,
                                 const float *actions, int64_t count, const float *dq1, const float *dq2,
                                 float *workspace, const fe_critic_grads *grads1, const fe_critic_grads *grads2,
                                 float *d_actions, void *stream) {
-    static const char *who = "fe_twin_q_backward_streamed";
-    if (!env || !logret_f32 || !obs_src || !obs_pos || !actions || !workspace || count < 0 ||
-        (dq1 && (!critic_weights_ok(c1) || (grads1 && !critic_grads_ok(grads1)) || (!grads1 && !d_actions))) ||
-        (dq2 && (!critic_weights_ok(c2) || (grads2 && !critic_grads_ok(grads2)) || (!grads2 && !d_actions))))
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = critic_streamed_check(env, H, who)) return rc;
-    if (count == 0) return FE_OK;
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (!dq1 && !dq2) {
-        if (!d_actions) return FE_OK;
-        return launched(who, hipMemsetAsync(d_actions, 0, (size_t)count * sizeof(float), st));
-    }
-    const int W = env->p.W;
-    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
-    const void *kern = critic_sgrad_forward_kernel_for<true>(H);
-    const fe_critic_weights *cw[2] = {c1, c2};
-    const fe_critic_grads *cg[2] = {grads1, grads2};
-    const float *dq[2] = {dq1, dq2};
-    int ran = 0;  // critics that have written d_actions
-    for (int i = 0; i < 2; ++i) {
-        if (!dq[i]) continue;
-        CriticSGradArgs a;
-        memset(&a, 0, sizeof(a));
-        LstmSGradArgs &g = a.g;
-        g.lr32 = logret_f32; g.whh = cw[i]->whh; g.wx = cw[i]->wx; g.wout = cw[i]->wout; g.W = W; g.out_act = 2;
-        sgrad_carve(g, workspace, H, pp);
-        if (cg[i]) {
-            g.g_wih = cg[i]->w_ih; g.g_whh = cg[i]->w_hh; g.g_bih = cg[i]->b_ih; g.g_bhh = cg[i]->b_hh;
-            g.g_wout = cg[i]->w_out; g.g_bout = cg[i]->b_out;
-        }
-        a.da_add = ran > 0;
-        hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
-        if (int rc = launched("fe_twin_q_backward_streamed: weight transpose")) return rc;
-        // the chunks in ascending order: the first overwrites the gradients, the later ones add to them
-        for (int64_t c0 = 0; c0 < count; c0 += chunk) {
-            sgrad_chunk(g, H, c0, count, chunk);
-            g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0; g.d_outputs = dq[i] + c0;
-            a.actions = actions + c0;
-            a.da = d_actions ? d_actions + c0 : nullptr;
-            if (int rc = launch_sgrad_forward(env, kern, critic_sgrad_forward_lds_bytes(H), &a, g.pp / 32, kCriticSGradPrepare,
-                                              "fe_twin_q_backward_streamed: recurrence", st))
-                return rc;
-            if (int rc = sgrad_backward_chunk(who, g, H, a.da ? &a : nullptr, cg[i] ? fe_critic_sgrad_final_kernel : nullptr, st))
-                return rc;
-        }
-        if (d_actions) ++ran;
-    }
-    return FE_OK;
+    return twin_q_backward_impl(env, logret_f32, c1, c2, H, obs_src, obs_pos, actions, count, dq1, dq2, workspace, grads1,
+                                grads2, d_actions, stream, true, "fe_twin_q_backward_streamed");
 }
 
-// ---- include/finenvs_amd_sac_streamed.h: the SAC actor at H = 256 / 512 / 1024 ----
+// ---- include/finenvs_amd_sac_grad.h: the SAC actor's backward pass ----
+// Workspace: [W_hh^T | W_l^T][partials of every workgroup][stash of every workgroup].
+int64_t fe_sac_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!resident_h_ok(H) || W < 1 || count < 0) return -1;
+    const int64_t groups = grad_tiles(count, sac_grad_max_groups(H)).max_groups;
+    return sac_grad_wt_floats(H) + groups * (sac_grad_part_floats(H) + bptt_stash_floats(H, W));
+}
+
+// The streamed SAC entries' refusal of another H; `small` names the entry that runs H = 32, 64 and 128.
 static int sac_streamed_hidden(int32_t H, const char *who, const char *small) {
     if (lstm_sgrad_hidden_ok(H)) return FE_OK;
     return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); %s runs H = 32, 64 and 128", who, (int)H, small);
 }
 
+// What fe_sac_backward (and its _p sibling) and fe_sac_backward_streamed refuse before they look at count; their launch
+// sequences share nothing and stay with the entries.
+static int sac_backward_checked(const fe_env *env, const float *logret_f32, const SacActorView &w, int32_t H,
+                                const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                                const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                                const float *workspace, const fe_sac_grads *grads, bool streamed, const char *who) {
+    if (!env || !logret_f32 || !sac_view_given(w) || !obs_src || !obs_pos || count < 0 || !noise || !actions || !stds ||
+        (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih || !grads->w_hh || !grads->b_ih || !grads->b_hh ||
+        !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu || !grads->w_std || !grads->b_std)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (streamed) {
+        if (int rc = sac_streamed_hidden(H, who, "fe_sac_backward")) return rc;
+    } else if (!resident_h_ok(H)) {
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d)", who, (int)H);
+    }
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused actor gradient runs A = 1 only (its consumer, the "
+                    "fused twin critic, does)", who, (int)env->p.A);
+    return FE_OK;
+}
+
+// fe_sac_backward and fe_sac_backward_p (the gradient does not depend on bmu)
+static int sac_backward_impl(fe_env *env, const float *logret_f32, const SacActorView &w, int32_t H, const int64_t *obs_src,
+                             const double *obs_pos, int64_t count, const float *noise, const float *actions,
+                             const float *stds, const float *d_actions, const float *d_log_probs, float *workspace,
+                             const fe_sac_grads *grads, void *stream) {
+    static const char *who = "fe_sac_backward";
+    if (int rc = sac_backward_checked(env, logret_f32, w, H, obs_src, obs_pos, count, noise, actions, stds, d_actions,
+                                      d_log_probs, workspace, grads, false, who))
+        return rc;
+    if (count == 0) return FE_OK;
+    const size_t lds = sac_grad_lds_bytes(H);
+    if (int rc = lds_fits(lds, H, who)) return rc;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const auto [tiles, max_groups] = grad_tiles(count, sac_grad_max_groups(H));
+    SacGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
+    g.whh = w.whh; g.wx = w.wx; g.wl = w.wl; g.bl = w.bl; g.wmu = w.wmu; g.wstd = w.wstd; g.bstd = w.bstd; g.bstd_p = w.bstd_p;
+    g.noise = noise; g.actions = actions; g.stds = stds; g.d_actions = d_actions; g.d_log_probs = d_log_probs;
+    g.wt = workspace;
+    g.part = g.wt + sac_grad_wt_floats(H);
+    g.stash = g.part + max_groups * sac_grad_part_floats(H);
+    g.count = count; g.num_tiles = tiles; g.W = W;
+    g.g_wih = grads->w_ih; g.g_whh = grads->w_hh; g.g_bih = grads->b_ih; g.g_bhh = grads->b_hh; g.g_wl = grads->w_l;
+    g.g_bl = grads->b_l; g.g_wmu = grads->w_mu; g.g_bmu = grads->b_mu; g.g_wstd = grads->w_std; g.g_bstd = grads->b_std;
+    hipLaunchKernelGGL(fe_sac_grad_pack_kernel, dim3(grid_for(sac_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    if (int rc = launched("fe_sac_backward: weight transpose")) return rc;
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_sac_grad_kernel<decltype(NT)::value>; });
+    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
+                             "SAC gradient kernel: hipFuncSetAttribute / occupancy query", "fe_sac_backward: backward", stream))
+        return rc;
+    hipLaunchKernelGGL(fe_sac_grad_reduce_kernel, dim3(grid_for(sac_grad_part_floats(H))), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H);
+    return launched("fe_sac_backward: reduction");
+}
+
+int fe_sac_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                    const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H,
+                    const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
+                    const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
+                    float *workspace, const fe_sac_grads *grads, void *stream) {
+    return sac_backward_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, bmu, bstd, nullptr, nullptr}, H, obs_src, obs_pos,
+                             count, noise, actions, stds, d_actions, d_log_probs, workspace, grads, stream);
+}
+
+// ---- include/finenvs_amd_lstm_grad.h and include/finenvs_amd_lstm_grad_streamed.h: the one-output LSTM head's backward
+// pass, register-resident and streamed ----
+// Workspace: [W_hh^T][partials of every workgroup][stash of every workgroup].
+int64_t fe_lstm_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!resident_h_ok(H) || W < 1 || count < 0) return -1;
+    const int64_t groups = grad_tiles(count, lstm_grad_max_groups(H)).max_groups;
+    return lstm_grad_wt_floats(H) + groups * (lstm_grad_part_floats(H) + bptt_stash_floats(H, W));
+}
+
+// What fe_lstm_backward and fe_lstm_backward_streamed refuse before they look at count; their launch sequences share
+// nothing and stay with the entries.
+static int lstm_backward_checked(const fe_env *env, const float *logret_f32, const LstmHeadView &w, int32_t H,
+                                 int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                                 const float *outputs, const float *d_outputs, const float *workspace,
+                                 const fe_lstm_grads *grads, bool streamed, const char *who) {
+    if (!env || !logret_f32 || !lstm_view_given(w) || !obs_src || !obs_pos || count < 0 || !d_outputs || !workspace ||
+        !head_grads_given(grads))
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (out_activation != 0 && out_activation != 2)
+        return fail(FE_ERR_ARG, "%s: out_activation must be 0 (tanh) or 2 (none); 1 (clamp) has no gradient to train on "
+                    "(got %d)", who, (int)out_activation);
+    if (out_activation == 0 && !outputs)
+        return fail(FE_ERR_ARG, "%s: out_activation 0 (tanh) needs outputs, the values fe_lstm_forward returned", who);
+    if (streamed && !lstm_sgrad_hidden_ok(H))
+        return fail(FE_ERR_ARG, "%s: H must be 256, 512 or 1024 (got %d); fe_lstm_backward runs H = 32, 64 and 128", who,
+                    (int)H);
+    if (!streamed && !resident_h_ok(H))
+        return fail(FE_ERR_ARG, "%s: H must be 32, 64 or 128 (got %d): the streamed-weight forward of H >= 256 has no "
+                    "register-resident recurrence to mirror", who, (int)H);
+    if (env->p.A != 1)
+        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused head gradient runs A = 1 only (as the fused twin "
+                    "critic does)", who, (int)env->p.A);
+    return FE_OK;
+}
+
+int fe_lstm_backward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                     int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos, int64_t count,
+                     const float *outputs, const float *d_outputs, float *workspace, const fe_lstm_grads *grads,
+                     void *stream) {
+    static const char *who = "fe_lstm_backward";
+    if (int rc = lstm_backward_checked(env, logret_f32, {whh, wx, wout, 0.0f, nullptr}, H, out_activation, obs_src, obs_pos,
+                                       count, outputs, d_outputs, workspace, grads, false, who))
+        return rc;
+    if (count == 0) return FE_OK;
+    const size_t lds = lstm_grad_lds_bytes(H);
+    if (int rc = lds_fits(lds, H, who)) return rc;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    const auto [tiles, max_groups] = grad_tiles(count, lstm_grad_max_groups(H));
+    LstmGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.obs_src = obs_src; g.obs_pos = obs_pos;
+    g.whh = whh; g.wx = wx; g.wout = wout; g.outputs = outputs; g.d_outputs = d_outputs;
+    g.wt = workspace;
+    g.part = g.wt + lstm_grad_wt_floats(H);
+    g.stash = g.part + max_groups * lstm_grad_part_floats(H);
+    g.count = count; g.num_tiles = tiles; g.W = W; g.out_act = out_activation;
+    head_grads_into(g, *grads);
+    hipLaunchKernelGGL(fe_lstm_grad_pack_kernel, dim3(grid_for(lstm_grad_wt_floats(H))), dim3(kBlock), 0, (hipStream_t)stream,
+                       g, H);
+    if (int rc = launched("fe_lstm_backward: weight transpose")) return rc;
+    const void *kern = with_nt(H, [](auto NT) { return (const void *)fe_lstm_grad_kernel<decltype(NT)::value>; });
+    if (int rc = launch_grad(env, kern, lds, max_groups, 1, &g, &g.groups,
+                             "LSTM head gradient kernel: hipFuncSetAttribute / occupancy query", "fe_lstm_backward: backward",
+                             stream))
+        return rc;
+    hipLaunchKernelGGL(fe_lstm_grad_reduce_kernel, dim3(grid_for(lstm_grad_part_floats(H))), dim3(kBlock), 0,
+                       (hipStream_t)stream, g, H);
+    return launched("fe_lstm_backward: reduction");
+}
+
+
+// ---- include/finenvs_amd_lstm_grad_streamed.h: the one-output LSTM head's backward pass at H = 256 / 512 / 1024 ----
+int64_t fe_lstm_streamed_grad_chunk_pairs(int32_t H, int32_t W) {
+    if (!lstm_sgrad_hidden_ok(H) || W < 1) return -1;
+    return lstm_sgrad_chunk_pairs(H, W);
+}
+
+// Workspace: [W_hh^T][split sums][head block sums][gates][c][h_{t-1} | x_t | 1][h_W][dh][dc], the last six for the pairs
+// of one pass.
+int64_t fe_lstm_streamed_grad_workspace_floats(int32_t H, int32_t W, int64_t count) {
+    if (!lstm_sgrad_hidden_ok(H) || W < 1 || count < 0) return -1;
+    const int64_t pp = lstm_sgrad_padded_pairs(H, W, count);
+    return lstm_sgrad_wt_floats(H) + lstm_sgrad_splits(H, W, pp) * lstm_sgrad_part_floats(H) +
+           lstm_sgrad_head_blocks(pp) * (H + 32) + pp * (lstm_sgrad_pair_floats(H, W) + 3LL * H);
+}
+
+// The recurrence kernel of the streamed head's and the streamed SAC actor's backward pass.
+static const void *lstm_sgrad_forward_kernel_for(int32_t H) {
+    return with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_lstm_sgrad_forward_kernel<decltype(NT)::value>; });
+}
+
+// (declared with launch_twin_q_streamed; here for the order of the instantiations)
+static const void *critic_sgrad_kernel(int32_t H, bool stash) {
+    return !stash ? critic_sgrad_forward_kernel_for<false>(H) : critic_sgrad_forward_kernel_for<true>(H);
+}
+
+int fe_lstm_backward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wout,
+                              int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
+                              int64_t count, const float *outputs, const float *d_outputs, float *workspace,
+                              const fe_lstm_grads *grads, void *stream) {
+    static const char *who = "fe_lstm_backward_streamed";
+    if (int rc = lstm_backward_checked(env, logret_f32, {whh, wx, wout, 0.0f, nullptr}, H, out_activation, obs_src, obs_pos,
+                                       count, outputs, d_outputs, workspace, grads, true, who))
+        return rc;
+    if (count == 0) return FE_OK;
+    const size_t lds = lstm_sgrad_forward_lds_bytes(H);
+    if (int rc = lds_fits(lds, H, who)) return rc;
+    DeviceGuard guard(env->device);
+    if (int rc = guard.status()) return rc;
+    const int W = env->p.W;
+    hipStream_t st = (hipStream_t)stream;
+    LstmSGradArgs g;
+    memset(&g, 0, sizeof(g));
+    g.lr32 = logret_f32; g.whh = whh; g.wx = wx; g.wout = wout; g.W = W; g.out_act = out_activation;
+    sgrad_carve(g, workspace, H, lstm_sgrad_padded_pairs(H, W, count));
+    head_grads_into(g, *grads);
+    hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
+    if (int rc = launched("fe_lstm_backward_streamed: weight transpose")) return rc;
+    return sgrad_chunks(env, who, g, H, count, obs_src, obs_pos, lstm_sgrad_forward_kernel_for(H), lds, &g,
+                        "streamed LSTM head gradient kernel: hipFuncSetAttribute / occupancy query", nullptr,
+                        fe_lstm_sgrad_final_kernel, nullptr, st, [&](int64_t c0) {
+                            g.outputs = outputs ? outputs + c0 : nullptr;
+                            g.d_outputs = d_outputs + c0;
+                        });
+}
+
+// ---- include/finenvs_amd_sac.h and include/finenvs_amd_sac_streamed.h: the SAC actor's head on the LSTM recurrence,
+// register-resident (launch_sac, above) and at H = 256 / 512 / 1024 ----
 // Shared by fe_env_rollout_sac_streamed and fe_sac_forward_streamed: the fused form at every count (no split by time step).
 static int launch_sac_streamed(fe_env *env, SacArgs &s, int64_t count, const char *who, void *stream) {
     const int32_t H = s.l.H;
@@ -2528,10 +2483,75 @@ static int launch_sac_streamed(fe_env *env, SacArgs &s, int64_t count, const cha
     const int SP = lstm_geometry(env, p, count, H, true, who);
     if (SP == 0) return FE_ERR_ARG;
     const size_t lds = sac_big_lds_bytes(p.EB, p.A, H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    if (int rc = lds_fits(lds, H, who)) return rc;
     const void *kern = with_nt<64, 4>(p.A == 1, H, [](auto S, auto NT) { return (const void *)fe_rollout_sac_big_kernel<decltype(S)::value, decltype(NT)::value>; });
     return launch_resident(env, kern, lds, p, &s, "streamed SAC kernel", stream);
+}
+
+// The actor's part of a kernel's SacArgs.
+static void sac_args(SacArgs &s, const float *logret_f32, const SacActorView &w, int32_t H) {
+    s.bmu_p = w.bmu_p; s.bstd_p = w.bstd_p;
+    s.l.lr32 = logret_f32; s.l.whh = w.whh; s.l.wx = w.wx; s.l.wout = nullptr; s.l.bout = 0.0f; s.l.H = H; s.l.out_act = 0;
+    s.l.std = 0.0f;
+    s.wl = w.wl; s.bl = w.bl; s.wmu = w.wmu; s.bmu = w.bmu; s.wstd = w.wstd; s.bstd = w.bstd;
+}
+
+// fe_env_rollout_sac, its _p sibling (both report as fe_env_rollout_sac) and fe_env_rollout_sac_streamed.  The resident
+// entries refuse H in launch_sac, after the state is known to be bound.
+static int rollout_sac_impl(fe_env *env, const float *logret_f32, const SacActorView &w, int32_t H, int32_t K, int64_t *obs_src,
+                            double *obs_pos, const float *noise, float *actions_out, float *means_out, float *stds_out,
+                            double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
+                            void *stream, bool streamed, const char *who) {
+    const bool given = env && logret_f32 && sac_view_given(w) && obs_src && obs_pos && rewards_out && dones_out && K >= 1;
+    // unpaired descriptor outputs: the resident entries' first refusal, the streamed entry's second
+    if ((states_src_out == nullptr) != (states_pos_out == nullptr) && (given || !streamed))
+        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
+    if (!given) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (streamed) {
+        if (int rc = sac_streamed_hidden(H, who, "fe_env_rollout_sac")) return rc;
+    }
+    if (int rc = require_bound(env, who)) return rc;
+    SacArgs s;
+    sac_args(s, logret_f32, w, H);
+    s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
+    s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
+    s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
+    s.stds_out = stds_out; s.logp_out = nullptr;
+    return streamed ? launch_sac_streamed(env, s, env->cfg.N, who, stream) : launch_sac(env, s, env->cfg.N, who, stream);
+}
+
+// fe_sac_forward, its _p sibling (both report as fe_sac_forward) and fe_sac_forward_streamed.  The resident entries
+// refuse H in launch_sac, after count == 0 has returned.
+static int sac_forward_impl(fe_env *env, const float *logret_f32, const SacActorView &w, int32_t H, const int64_t *obs_src,
+                            const double *obs_pos, int64_t count, const float *noise, float *actions_out,
+                            float *log_probs_out, float *means_out, float *stds_out, void *stream, bool streamed,
+                            const char *who) {
+    if (!env || !logret_f32 || !sac_view_given(w) || !obs_src || !obs_pos || count < 0)
+        return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (!noise && (actions_out || log_probs_out))
+        return fail(FE_ERR_ARG, "%s: actions_out and log_probs_out need noise", who);
+    if (streamed) {
+        if (int rc = sac_streamed_hidden(H, who, "fe_sac_forward")) return rc;
+    }
+    if (count == 0) return FE_OK;
+    SacArgs s;
+    sac_args(s, logret_f32, w, H);
+    s.l.K = 1;
+    s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
+    s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
+    s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
+    s.stds_out = stds_out; s.logp_out = log_probs_out;
+    return streamed ? launch_sac_streamed(env, s, count, who, stream) : launch_sac(env, s, count, who, stream);
+}
+
+int fe_env_rollout_sac(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
+                       const float *bl, const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, int32_t K,
+                       int64_t *obs_src, double *obs_pos, const float *noise, float *actions_out, float *means_out,
+                       float *stds_out, double *rewards_out, int32_t *dones_out, int64_t *states_src_out,
+                       double *states_pos_out, void *stream) {
+    return rollout_sac_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, bmu, bstd, nullptr, nullptr}, H, K, obs_src, obs_pos,
+                            noise, actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out,
+                            stream, false, "fe_env_rollout_sac");
 }
 
 int fe_env_rollout_sac_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
@@ -2539,42 +2559,27 @@ int fe_env_rollout_sac_streamed(fe_env *env, const float *logret_f32, const floa
                                 int32_t H, int32_t K, int64_t *obs_src, double *obs_pos, const float *noise,
                                 float *actions_out, float *means_out, float *stds_out, double *rewards_out,
                                 int32_t *dones_out, int64_t *states_src_out, double *states_pos_out, void *stream) {
-    static const char *who = "fe_env_rollout_sac_streamed";
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos ||
-        !rewards_out || !dones_out || K < 1)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if ((states_src_out == nullptr) != (states_pos_out == nullptr))
-        return fail(FE_ERR_ARG, "%s: states_src_out and states_pos_out go together", who);
-    if (int rc = sac_streamed_hidden(H, who, "fe_env_rollout_sac")) return rc;
-    if (int rc = require_bound(env, who)) return rc;
-    SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H);
-    s.l.K = K; s.l.obs_src = obs_src; s.l.obs_pos = obs_pos; s.l.noise = noise; s.l.actions_out = actions_out;
-    s.l.means_out = means_out; s.l.rew_out = rewards_out; s.l.done_out = dones_out; s.l.traj_src = states_src_out;
-    s.l.traj_pos = states_pos_out; s.l.forward_only = 0;
-    s.stds_out = stds_out; s.logp_out = nullptr;
-    return launch_sac_streamed(env, s, env->cfg.N, who, stream);
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_env_rollout_sac_streamed: bad argument");
+    return rollout_sac_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, K, obs_src, obs_pos, noise,
+                            actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out, stream,
+                            true, "fe_env_rollout_sac_streamed");
+}
+
+int fe_sac_forward(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl, const float *bl,
+                   const float *wmu, float bmu, const float *wstd, float bstd, int32_t H, const int64_t *obs_src,
+                   const double *obs_pos, int64_t count, const float *noise, float *actions_out, float *log_probs_out,
+                   float *means_out, float *stds_out, void *stream) {
+    return sac_forward_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, bmu, bstd, nullptr, nullptr}, H, obs_src, obs_pos,
+                            count, noise, actions_out, log_probs_out, means_out, stds_out, stream, false, "fe_sac_forward");
 }
 
 int fe_sac_forward_streamed(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
                             const float *bl, const float *wmu, const float *bmu, const float *wstd, const float *bstd,
                             int32_t H, const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise,
                             float *actions_out, float *log_probs_out, float *means_out, float *stds_out, void *stream) {
-    static const char *who = "fe_sac_forward_streamed";
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos || count < 0)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (!noise && (actions_out || log_probs_out))
-        return fail(FE_ERR_ARG, "%s: actions_out and log_probs_out need noise", who);
-    if (int rc = sac_streamed_hidden(H, who, "fe_sac_forward")) return rc;
-    if (count == 0) return FE_OK;
-    SacArgs s;
-    sac_args(s, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H);
-    s.l.K = 1;
-    s.l.obs_src = const_cast<int64_t *>(obs_src); s.l.obs_pos = const_cast<double *>(obs_pos);  // read only in this mode
-    s.l.noise = noise; s.l.actions_out = actions_out; s.l.means_out = means_out; s.l.rew_out = nullptr; s.l.done_out = nullptr;
-    s.l.traj_src = nullptr; s.l.traj_pos = nullptr; s.l.forward_only = 1;
-    s.stds_out = stds_out; s.logp_out = log_probs_out;
-    return launch_sac_streamed(env, s, count, who, stream);
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_sac_forward_streamed: bad argument");
+    return sac_forward_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, obs_src, obs_pos, count,
+                            noise, actions_out, log_probs_out, means_out, stds_out, stream, true, "fe_sac_forward_streamed");
 }
 
 // Workspace: [W_l^T][split sums of d W_l][head block sums][z][the head's dz], sized by the largest pass, then the workspace
@@ -2590,23 +2595,17 @@ int fe_sac_backward_streamed(fe_env *env, const float *logret_f32, const float *
                              const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
                              float *workspace, const fe_sac_grads *grads, void *stream) {
     static const char *who = "fe_sac_backward_streamed";
-    if (!env || !logret_f32 || !whh || !wx || !wl || !bl || !wmu || !bmu || !wstd || !bstd || !obs_src || !obs_pos ||
-        count < 0 || !noise || !actions || !stds || (!d_actions && !d_log_probs) || !workspace || !grads || !grads->w_ih ||
-        !grads->w_hh || !grads->b_ih || !grads->b_hh || !grads->w_l || !grads->b_l || !grads->w_mu || !grads->b_mu ||
-        !grads->w_std || !grads->b_std)
-        return fail(FE_ERR_ARG, "%s: bad argument", who);
-    if (int rc = sac_streamed_hidden(H, who, "fe_sac_backward")) return rc;
-    if (env->p.A != 1)
-        return fail(FE_ERR_ARG, "%s: the env has %d assets; the fused actor gradient runs A = 1 only (its consumer, the "
-                    "fused twin critic, does)", who, (int)env->p.A);
+    if (!bmu || !bstd) return fail(FE_ERR_ARG, "%s: bad argument", who);
+    if (int rc = sac_backward_checked(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, obs_src, obs_pos,
+                                      count, noise, actions, stds, d_actions, d_log_probs, workspace, grads, true, who))
+        return rc;
     if (count == 0) return FE_OK;
     const size_t lds = lstm_sgrad_forward_lds_bytes(H);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "%s: H = %d needs %zu bytes of LDS per workgroup, the device has %zu", who, (int)H, lds, kMaxLds);
+    if (int rc = lds_fits(lds, H, who)) return rc;
     DeviceGuard guard(env->device);
     if (int rc = guard.status()) return rc;
     const int W = env->p.W;
-    const int64_t chunk = lstm_sgrad_chunk_pairs(H, W), pp = lstm_sgrad_padded_pairs(H, W, count);
+    const int64_t pp = lstm_sgrad_padded_pairs(H, W, count);
     hipStream_t st = (hipStream_t)stream;
     SacSGradArgs a;
     memset(&a, 0, sizeof(a));
@@ -2625,21 +2624,15 @@ int fe_sac_backward_streamed(fe_env *env, const float *logret_f32, const float *
     hipLaunchKernelGGL(fe_lstm_sgrad_pack_kernel, dim3(grid_for(lstm_sgrad_wt_floats(H))), dim3(kBlock), 0, st, g, H);
     hipLaunchKernelGGL(fe_sac_sgrad_pack_kernel, dim3(grid_for((int64_t)H * H)), dim3(kBlock), 0, st, a, H);
     if (int rc = launched("fe_sac_backward_streamed: weight transposes")) return rc;
-    const void *kern = with_nt<64, 4>(H, [](auto NT) { return (const void *)fe_lstm_sgrad_forward_kernel<decltype(NT)::value>; });
-    // the chunks in ascending order (the head's boundaries): the first overwrites the gradients, the later ones add to them
-    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
-        sgrad_chunk(g, H, c0, count, chunk);
-        a.wl_splits = sac_sgrad_wl_splits(H, g.pp);
-        g.obs_src = obs_src + c0; g.obs_pos = obs_pos + c0;
-        a.noise = noise + c0; a.actions = actions + c0; a.stds = stds + c0;
-        a.d_actions = d_actions ? d_actions + c0 : nullptr; a.d_log_probs = d_log_probs ? d_log_probs + c0 : nullptr;
-        if (int rc = launch_sgrad_forward(env, kern, lds, &g, g.pp / 32,
-                                          "streamed SAC gradient kernel: hipFuncSetAttribute / occupancy query",
-                                          "fe_sac_backward_streamed: recurrence", st))
-            return rc;
-        if (int rc = sgrad_backward_chunk(who, g, H, nullptr, nullptr, st, &a)) return rc;
-    }
-    return FE_OK;
+    // (the chunks are the head's)
+    return sgrad_chunks(env, who, g, H, count, obs_src, obs_pos, lstm_sgrad_forward_kernel_for(H), lds, &g,
+                        "streamed SAC gradient kernel: hipFuncSetAttribute / occupancy query", nullptr, nullptr, &a, st,
+                        [&](int64_t c0) {
+                            a.wl_splits = sac_sgrad_wl_splits(H, g.pp);
+                            a.noise = noise + c0; a.actions = actions + c0; a.stds = stds + c0;
+                            a.d_actions = d_actions ? d_actions + c0 : nullptr;
+                            a.d_log_probs = d_log_probs ? d_log_probs + c0 : nullptr;
+                        });
 }
 
 // ---- include/finenvs_amd_optim.h: the entries above with their output biases in device memory ----
@@ -2647,7 +2640,7 @@ int fe_lstm_forward_p(fe_env *env, const float *logret_f32, const float *whh, co
                       const float *bout, int32_t H, int32_t out_activation, const int64_t *obs_src, const double *obs_pos,
                       int64_t count, float *out, void *stream) {
     if (!bout) return fail(FE_ERR_ARG, "fe_lstm_forward_p: bad argument");
-    return lstm_forward_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, obs_src, obs_pos, count, out,
+    return lstm_forward_impl(env, logret_f32, {whh, wx, wout, 0.0f, bout}, H, out_activation, obs_src, obs_pos, count, out,
                              stream);
 }
 
@@ -2657,7 +2650,7 @@ int fe_env_rollout_lstm_p(fe_env *env, const float *logret_f32, const float *whh
                           double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
                           void *stream) {
     if (!bout) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_p: bad argument");
-    return rollout_lstm_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, K, obs_src, obs_pos, noise, std,
+    return rollout_lstm_impl(env, logret_f32, {whh, wx, wout, 0.0f, bout}, H, out_activation, K, obs_src, obs_pos, noise, std,
                              actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out, stream);
 }
 
@@ -2667,7 +2660,7 @@ int fe_env_rollout_lstm_split_p(fe_env *env, const float *logret_f32, const floa
                                 double *rewards_out, int32_t *dones_out, int64_t *states_src_out, double *states_pos_out,
                                 float *workspace, void *stream) {
     if (!bout) return fail(FE_ERR_ARG, "fe_env_rollout_lstm_split_p: bad argument");
-    return rollout_lstm_split_impl(env, logret_f32, whh, wx, wout, 0.0f, bout, H, out_activation, K, obs_src, obs_pos, noise,
+    return rollout_lstm_split_impl(env, logret_f32, {whh, wx, wout, 0.0f, bout}, H, out_activation, K, obs_src, obs_pos, noise,
                                    std, actions_out, means_out, rewards_out, dones_out, states_src_out, states_pos_out,
                                    workspace, stream);
 }
@@ -2678,9 +2671,9 @@ int fe_env_rollout_sac_p(fe_env *env, const float *logret_f32, const float *whh,
                          float *means_out, float *stds_out, double *rewards_out, int32_t *dones_out,
                          int64_t *states_src_out, double *states_pos_out, void *stream) {
     if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_env_rollout_sac_p: bad argument");
-    return rollout_sac_impl(env, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H, K, obs_src, obs_pos, noise,
-                            actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out,
-                            stream);
+    return rollout_sac_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, K, obs_src, obs_pos, noise,
+                            actions_out, means_out, stds_out, rewards_out, dones_out, states_src_out, states_pos_out, stream,
+                            false, "fe_env_rollout_sac");
 }
 
 int fe_sac_forward_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
@@ -2688,8 +2681,8 @@ int fe_sac_forward_p(fe_env *env, const float *logret_f32, const float *whh, con
                      const int64_t *obs_src, const double *obs_pos, int64_t count, const float *noise, float *actions_out,
                      float *log_probs_out, float *means_out, float *stds_out, void *stream) {
     if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_sac_forward_p: bad argument");
-    return sac_forward_impl(env, logret_f32, whh, wx, wl, bl, wmu, 0.0f, wstd, 0.0f, bmu, bstd, H, obs_src, obs_pos, count,
-                            noise, actions_out, log_probs_out, means_out, stds_out, stream);
+    return sac_forward_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, obs_src, obs_pos, count,
+                            noise, actions_out, log_probs_out, means_out, stds_out, stream, false, "fe_sac_forward");
 }
 
 int fe_sac_backward_p(fe_env *env, const float *logret_f32, const float *whh, const float *wx, const float *wl,
@@ -2698,8 +2691,8 @@ int fe_sac_backward_p(fe_env *env, const float *logret_f32, const float *whh, co
                       const float *actions, const float *stds, const float *d_actions, const float *d_log_probs,
                       float *workspace, const fe_sac_grads *grads, void *stream) {
     if (!bmu || !bstd) return fail(FE_ERR_ARG, "fe_sac_backward_p: bad argument");
-    return sac_backward_impl(env, logret_f32, whh, wx, wl, bl, wmu, wstd, 0.0f, bstd, H, obs_src, obs_pos, count, noise,
-                             actions, stds, d_actions, d_log_probs, workspace, grads, stream);
+    return sac_backward_impl(env, logret_f32, {whh, wx, wl, bl, wmu, wstd, 0.0f, 0.0f, bmu, bstd}, H, obs_src, obs_pos, count,
+                             noise, actions, stds, d_actions, d_log_probs, workspace, grads, stream);
 }
 
 // ---- include/finenvs_amd_optim.h: Adam, the soft update and the packing of every registered network, one launch ----
