@@ -334,6 +334,32 @@ MLP2_HEAD_SIGNATURES = {
     "fe_mlp2_backward": (C.c_int, [_vp, _vp, _mw2, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, C.POINTER(FeMlp2Grads), _vp]),
 }
 
+# include/finenvs_amd_mlp_critic.h: the twin MLP critics Q(s, a) (finenvs_amd/mlp_critic.py)
+MLPQ_GRAD_CHUNK_PAIRS = 512  # FE_MLPQ_GRAD_CHUNK_PAIRS
+
+
+class FeMlpqWeights(C.Structure):
+    """struct fe_mlpq_weights of include/finenvs_amd_mlp_critic.h."""
+
+    _fields_ = [("w1t", _vp), ("wpos", _vp), ("wact", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp)]
+
+
+class FeMlpqGrads(C.Structure):
+    """struct fe_mlpq_grads of include/finenvs_amd_mlp_critic.h."""
+
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp)]
+
+
+_qw, _qg = C.POINTER(FeMlpqWeights), C.POINTER(FeMlpqGrads)
+_mlpq_target_tail = [_vp, _i64, _vp, _vp, C.c_float, C.c_float, _vp, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]
+MLP_CRITIC_SIGNATURES = {
+    "fe_twin_mlpq_forward": (C.c_int, [_vp, _vp, _qw, _qw, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "fe_twin_mlpq_target": (C.c_int, [_vp, _vp, _qw, _qw, _i32, _i32, C.POINTER(FeReplayRing), _i64, _i64] + _mlpq_target_tail),
+    "fe_twin_mlpq_target_c": (C.c_int, [_vp, _vp, _qw, _qw, _i32, _i32, C.POINTER(FeReplayRing), _vp] + _mlpq_target_tail),
+    "fe_twin_mlpq_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_twin_mlpq_backward": (C.c_int, [_vp, _vp, _qw, _qw, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _qg, _qg, _vp, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -362,7 +388,8 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **CRITIC_SIGNATURES, **CRITIC_GRAD_SIGNATURES, **SAC_GRAD_SIGNATURES,
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
-                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES}.items():
+                         **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES,
+                         **MLP_CRITIC_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -201,39 +201,13 @@ class _TwinQ(torch.autograd.Function):
         return tuple(out)
 
 
-class FusedTwinCritic:
-    """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
-
-    The critics' parameters are re-packed on the device at every call (a few small launches, no host round trip), so an
-    optimizer step or a soft update is seen by the next call.  Both critics must live on the env's device.
-
-    ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that both critics are registered with, as networks or as
-    targets.  Nothing is packed per call then: every launch reads that optimizer's packed buffers, which its ``step()``
-    keeps current.  Those buffers are rewritten in place: a ``weights.step()`` or ``weights.repack()`` between a
-    forward and its ``backward()`` is a RuntimeError.
-
-    ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent weights stream from L2
-    (include/finenvs_amd_critic_streamed.h).  It is an opt-in because that backward is several launches per LSTM time
-    step and per critic, and its workspace grows with the batch, up to ``fe_lstm_streamed_grad_chunk_pairs`` pairs
-    (2 GiB of activations; the two critics share it), unlike the bounded one of H <= 128; H <= 128 runs the
-    register-resident way whether or not ``streamed`` is passed."""
-
-    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module, weights=None, streamed: bool = False):
-        if int(env.num_assets) != 1:
-            raise ValueError(f"the fused twin critic runs one asset (the env has {env.num_assets}): the reference's critic "
-                             "for A > 1 is one nn.LSTM(5A + A, H) over the whole env's window, not a per-(env, asset) pair "
-                             "network")
-        H1, H2 = check_critic(critic_1, streamed), check_critic(critic_2, streamed)
-        if H1 != H2:
-            raise ValueError(f"the two critics must have the same hidden size (got {H1} and {H2})")
-        self.env, self.critic_1, self.critic_2, self.H = env, critic_1, critic_2, H1
-        self.streamed = H1 > 128  # which entries run: a function of H alone
-        self._check_devices()
-        self.weights = weights
-        if weights is not None:
-            weights.packed(critic_1), weights.packed(critic_2)  # ValueError if a critic is not registered with it
-        self._lr32 = log_return_f32(env)
-        self.last: Dict[str, torch.Tensor] = {}
+class _FusedTwin:
+    """What ``FusedTwinCritic`` and ``FusedTwinMLPCritic`` (finenvs_amd/mlp_critic.py) share: everything that does not
+    depend on the network -- the checks of devices, vectors and indices, the ring's descriptors, the NaN rule for an index
+    outside ``[0, size)``, ``ReplayDraw`` handling, the critic loss and the target launches' argument lists.  A family
+    provides ``forward``, ``q``, ``_weights()`` (the two ctypes weight structs), ``_shape_args()`` (what its C entries
+    take between the weights and the descriptors: ``H``, or ``H`` and the activation), ``_target_entry(cursor)`` and
+    ``_check_target_actor``."""
 
     def _check_devices(self) -> None:
         dev = torch.device(self.env._dev)
@@ -241,59 +215,11 @@ class FusedTwinCritic:
             if any(p.device != dev for p in c.parameters()):
                 raise ValueError(f"{name}'s parameters must live on the env's device {dev}")
 
-    def _weights(self):
-        self._check_devices()
-        if self.weights is not None:
-            w = [self.weights.packed(c) for c in (self.critic_1, self.critic_2)]
-        else:
-            w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
-        self._packed = w  # kept alive until the launch has been queued
-        return [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
-                for x in w]
-
     def _vector(self, t, B: int, name: str, dtype=torch.float32) -> torch.Tensor:
         if not isinstance(t, torch.Tensor) or t.dtype is not dtype or t.numel() != B or t.device != torch.device(self.env._dev):
             raise ValueError(f"{name} must be a {dtype} tensor of {B} elements ((B,) or (B, 1)) on {self.env._dev}, got "
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
         return t.reshape(B).contiguous()
-
-    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
-        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
-        env = self.env
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        act = self._vector(actions, B, "actions")
-        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        if B:
-            c1, c2 = self._weights()
-            entry = env._lib.fe_twin_q_forward_streamed if self.streamed else env._lib.fe_twin_q_forward
-            _lib.check(entry(
-                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, src.data_ptr(), pos.data_ptr(),
-                act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
-        return q1, q2
-
-    __call__ = forward
-
-    # ---------------------------------------------------------------- the gradient half
-    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """``forward`` as a differentiable function (C ABI ``fe_twin_q_backward``, include/finenvs_amd_critic_grad.h):
-        ``(q1, q2)`` (B, 1) float32, the same values bit for bit.  ``backward()`` accumulates into the ``.grad`` of both
-        critics' parameters and of ``actions`` (float32, (B, 1) or (B,)) as the torch modules would: the critic loss of
-        SAC/critic.py:30-45 / TD3/critic.py:31-46, ``dQ/da`` for TD3/actor.py ``compute_loss`` and the SAC actor loss.
-        A critic whose output gets no gradient does not run; one whose parameters are frozen has no weight
-        reduction."""
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        self._vector(actions, B, "actions")
-        params = critic_parameters(self.critic_1) + critic_parameters(self.critic_2)
-        if any(p.dtype is not torch.float32 for p in params):
-            raise ValueError("the fused critic's gradient needs float32 parameters")
-        q1, q2 = _TwinQ.apply(self, src, pos, actions, *params)
-        return q1, q2
 
     def critic_loss(self, buffer, indices: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """``MSE(q1, y) + MSE(q2, y)`` of both critics (SAC/critic.py:30-45 compute_loss, once per critic) on the
@@ -356,19 +282,130 @@ class FusedTwinCritic:
             tail = (idx.data_ptr(), B, next_actions.data_ptr(), ptr(smooth_noise), float(smooth_std), float(smooth_clip),
                     ptr(log_probs), ptr(alpha), float(gamma), float(reward_scale), y.data_ptr(), q1.data_ptr(),
                     q2.data_ptr(), env._stream())
-            lib = env._lib
+            net = (env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), *self._shape_args(), C.byref(buffer._desc))
+            entry = self._target_entry(cursor=draw is not None)
             if draw is None:
-                entry = lib.fe_twin_q_target_streamed if self.streamed else lib.fe_twin_q_target
-                _lib.check(entry(
-                    env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
-                    buffer.head, buffer.size(), *tail), env._lib)
+                _lib.check(entry(*net, buffer.head, buffer.size(), *tail), env._lib)
             else:  # head and size from the cursor, when the launches run
-                entry = lib.fe_twin_q_target_streamed_c if self.streamed else lib.fe_twin_q_target_c
-                _lib.check(entry(
-                    env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, C.byref(buffer._desc),
-                    buffer.cursor.data_ptr(), *tail), env._lib)
+                _lib.check(entry(*net, buffer.cursor.data_ptr(), *tail), env._lib)
         self.last = {"indices": idx, "next_actions": next_actions.reshape(B, 1), "q1": q1, "q2": q2}
         return y
+
+    def td3_targets(self, buffer, indices: Optional[torch.Tensor], target_actor, noise: Optional[torch.Tensor] = None,
+                    gamma: float = 0.99, policy_std: float = 0.2, policy_clip: float = 0.5, reward_scale: float = 1.0,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+        """``TD3Agent.compute_targets`` (TD3_agent.py:231-251): the target actor (``FusedTwinCritic``: a
+        ``FusedLSTMRollout``, ``FusedTwinMLPCritic``: a ``FusedMLP2Rollout``; ``output_activation="tanh"``) on the sampled
+        next descriptors, the smoothed action ``clamp(a + clamp(noise * policy_std, -policy_clip, policy_clip), -1, 1)`` with ``noise`` (B, 1) standard normals (default ``torch.randn``),
+        both target critics and ``y = r + gamma * (1 - d) * min(q1, q2)``.  (B, 1) float32."""
+        draw = as_draw(buffer, indices, "td3_targets")
+        self._check_target_actor(target_actor)
+        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
+        B = int(idx.numel())
+        src, pos = self._next_descriptors(buffer, idx, draw)
+        actions = target_actor.forward(src, pos)
+        if noise is None:
+            noise = torch.randn((B, 1), device=self.env._dev)
+        noise = self._vector(noise, B, "noise")
+        return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale, draw)
+
+
+class FusedTwinCritic(_FusedTwin):
+    """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
+
+    The critics' parameters are re-packed on the device at every call (a few small launches, no host round trip), so an
+    optimizer step or a soft update is seen by the next call.  Both critics must live on the env's device.
+
+    ``weights``: a ``FusedAdam`` (finenvs_amd/optim.py) that both critics are registered with, as networks or as
+    targets.  Nothing is packed per call then: every launch reads that optimizer's packed buffers, which its ``step()``
+    keeps current.  Those buffers are rewritten in place: a ``weights.step()`` or ``weights.repack()`` between a
+    forward and its ``backward()`` is a RuntimeError.
+
+    ``streamed=True`` also admits H in {256, 512, 1024}, the sizes whose recurrent weights stream from L2
+    (include/finenvs_amd_critic_streamed.h).  It is an opt-in because that backward is several launches per LSTM time
+    step and per critic, and its workspace grows with the batch, up to ``fe_lstm_streamed_grad_chunk_pairs`` pairs
+    (2 GiB of activations; the two critics share it), unlike the bounded one of H <= 128; H <= 128 runs the
+    register-resident way whether or not ``streamed`` is passed."""
+
+    def __init__(self, env, critic_1: nn.Module, critic_2: nn.Module, weights=None, streamed: bool = False):
+        if int(env.num_assets) != 1:
+            raise ValueError(f"the fused twin critic runs one asset (the env has {env.num_assets}): the reference's critic "
+                             "for A > 1 is one nn.LSTM(5A + A, H) over the whole env's window, not a per-(env, asset) pair "
+                             "network")
+        H1, H2 = check_critic(critic_1, streamed), check_critic(critic_2, streamed)
+        if H1 != H2:
+            raise ValueError(f"the two critics must have the same hidden size (got {H1} and {H2})")
+        self.env, self.critic_1, self.critic_2, self.H = env, critic_1, critic_2, H1
+        self.streamed = H1 > 128  # which entries run: a function of H alone
+        self._check_devices()
+        self.weights = weights
+        if weights is not None:
+            weights.packed(critic_1), weights.packed(critic_2)  # ValueError if a critic is not registered with it
+        self._lr32 = log_return_f32(env)
+        self.last: Dict[str, torch.Tensor] = {}
+
+    def _weights(self):
+        self._check_devices()
+        if self.weights is not None:
+            w = [self.weights.packed(c) for c in (self.critic_1, self.critic_2)]
+        else:
+            w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
+        self._packed = w  # kept alive until the launch has been queued
+        return [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
+                for x in w]
+
+    def _shape_args(self):
+        return (self.H,)
+
+    def _target_entry(self, cursor: bool):
+        lib = self.env._lib
+        if cursor:
+            return lib.fe_twin_q_target_streamed_c if self.streamed else lib.fe_twin_q_target_c
+        return lib.fe_twin_q_target_streamed if self.streamed else lib.fe_twin_q_target
+
+    def _check_target_actor(self, target_actor) -> None:
+        from .rollout import FusedLSTMRollout
+
+        if not isinstance(target_actor, FusedLSTMRollout) or target_actor.out_act != 0:
+            raise ValueError('target_actor must be a FusedLSTMRollout with output_activation="tanh"')
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
+        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
+        env = self.env
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        act = self._vector(actions, B, "actions")
+        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        if B:
+            c1, c2 = self._weights()
+            entry = env._lib.fe_twin_q_forward_streamed if self.streamed else env._lib.fe_twin_q_forward
+            _lib.check(entry(
+                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, src.data_ptr(), pos.data_ptr(),
+                act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
+        return q1, q2
+
+    __call__ = forward
+
+    # ---------------------------------------------------------------- the gradient half
+    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """``forward`` as a differentiable function (C ABI ``fe_twin_q_backward``, include/finenvs_amd_critic_grad.h):
+        ``(q1, q2)`` (B, 1) float32, the same values bit for bit.  ``backward()`` accumulates into the ``.grad`` of both
+        critics' parameters and of ``actions`` (float32, (B, 1) or (B,)) as the torch modules would: the critic loss of
+        SAC/critic.py:30-45 / TD3/critic.py:31-46, ``dQ/da`` for TD3/actor.py ``compute_loss`` and the SAC actor loss.
+        A critic whose output gets no gradient does not run; one whose parameters are frozen has no weight
+        reduction."""
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        self._vector(actions, B, "actions")
+        params = critic_parameters(self.critic_1) + critic_parameters(self.critic_2)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError("the fused critic's gradient needs float32 parameters")
+        q1, q2 = _TwinQ.apply(self, src, pos, actions, *params)
+        return q1, q2
 
     def sac_targets(self, buffer, indices: Optional[torch.Tensor], actor_roll, noise: Optional[torch.Tensor] = None,
                     gamma: float = 0.99, log_alpha: Optional[torch.Tensor] = None, reward_scale: float = 1.0,
@@ -398,27 +435,6 @@ class FusedTwinCritic:
         y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale, draw)
         self.last.update(log_probs=log_probs, alpha=alpha)
         return y
-
-    def td3_targets(self, buffer, indices: Optional[torch.Tensor], target_actor, noise: Optional[torch.Tensor] = None,
-                    gamma: float = 0.99, policy_std: float = 0.2, policy_clip: float = 0.5, reward_scale: float = 1.0,
-                    batch_size: Optional[int] = None) -> torch.Tensor:
-        """``TD3Agent.compute_targets`` (TD3_agent.py:231-251): the target actor (a ``FusedLSTMRollout`` with
-        ``output_activation="tanh"``) on the sampled next descriptors, the smoothed action ``clamp(a + clamp(noise *
-        policy_std, -policy_clip, policy_clip), -1, 1)`` with ``noise`` (B, 1) standard normals (default ``torch.randn``),
-        both target critics and ``y = r + gamma * (1 - d) * min(q1, q2)``.  (B, 1) float32."""
-        from .rollout import FusedLSTMRollout
-
-        draw = as_draw(buffer, indices, "td3_targets")
-        if not isinstance(target_actor, FusedLSTMRollout) or target_actor.out_act != 0:
-            raise ValueError('target_actor must be a FusedLSTMRollout with output_activation="tanh"')
-        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
-        B = int(idx.numel())
-        src, pos = self._next_descriptors(buffer, idx, draw)
-        actions = target_actor.forward(src, pos)
-        if noise is None:
-            noise = torch.randn((B, 1), device=self.env._dev)
-        noise = self._vector(noise, B, "noise")
-        return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale, draw)
 
 
 # ---------------------------------------------------------------- the torch restatements (host or device)

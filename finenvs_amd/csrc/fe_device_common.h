@@ -54,12 +54,19 @@ constexpr int kStoreAuxMulti = 2;
 template <typename OT>
 constexpr bool kHoistFirst = FE_HOIST_FIRST != 0 && (sizeof(OT) == 8 || FE_F32_WAVES <= 5);
 
+#ifndef FE_ERROR_BUFFER_ELSEWHERE
 thread_local char g_err[512] = "";
+#endif
 
 }  // namespace
 
 // Records the message fe_last_error returns and passes `code` through.  fe_csv.cpp calls it by this name: hidden
 // visibility keeps it internal to the library, not an exported symbol.
+#ifdef FE_ERROR_BUFFER_ELSEWHERE
+// A second translation unit of the library (fe_mlp_critic.hip) defines FE_ERROR_BUFFER_ELSEWHERE before it includes this
+// header: the one error buffer and fe_set_error's definition stay in fe_env.hip, this unit only calls it.
+extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...);
+#else
 extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -67,15 +74,22 @@ extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, cons
     va_end(ap);
     return code;
 }
+#endif
 
 namespace {
 
 constexpr auto &fail = fe_set_error;
 
+#ifdef FE_ERROR_BUFFER_ELSEWHERE
+int hip_fail(hipError_t e, const char *what) {
+    return fe_set_error(FE_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+#else
 int hip_fail(hipError_t e, const char *what) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
     return FE_ERR_HIP;
 }
+#endif
 
 // Exact unsigned 32-bit division by a launch-time constant (Granlund & Montgomery 1994).
 struct FastDiv {

@@ -2805,3 +2805,18 @@ int fe_ppo_value_loss(const float *values, const float *returns, int64_t count, 
 }
 
 }  // extern "C"
+
+// ---- what the library's second translation unit (fe_mlp_critic.hip) needs of this one: hidden visibility, as
+// fe_set_error is shared with fe_csv.cpp.  Host code only: this unit's device code object is what it was. ----
+// An env's window, asset count and device.
+extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(const fe_env *env, int32_t *W, int32_t *A, int *device) {
+    *W = env->p.W;
+    *A = env->p.A;
+    *device = env->device;
+}
+
+// prepare_big_lds for a kernel of the other unit: one cache of (device, kernel) attributes for the whole library.
+extern "C" __attribute__((visibility("hidden"))) int fe_prepare_big_lds_internal(int device, const void *kern, size_t lds,
+                                                                                 const char *who) {
+    return prepare_big_lds(device, kern, lds, who);
+}

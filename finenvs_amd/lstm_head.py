@@ -387,14 +387,21 @@ def ppo_critic_loss(head: "Union[FusedLSTMHead, FusedMLPHead]", src: torch.Tenso
 def td3_actor_loss(head: FusedLSTMHead, buffer, indices: torch.Tensor, twin) -> torch.Tensor:
     """``Actor.compute_loss`` (TD3/actor.py:50-56) on the transitions ``indices`` (logical, (B,)) of ``buffer``:
     ``-twin.q(src, pos, head(src, pos))[0].mean()`` on the ring's state descriptors, nothing rendered (the reference
-    passes its first critic).  ``backward()`` also accumulates into that critic's ``.grad`` unless it is frozen (as in
+    passes its first critic).  ``head`` / ``twin``: a ``FusedLSTMHead`` with a ``FusedTwinCritic``, or a ``FusedMLP2Head``
+    (tanh output) with a ``FusedTwinMLPCritic`` (finenvs_amd/mlp_critic.py).  ``backward()`` also accumulates into that critic's ``.grad`` unless it is frozen (as in
     torch); an index outside ``[0, size)`` makes the loss NaN.  ``indices`` may be a ``ReplayDraw`` of a ``cursor=True``
     buffer (no host integer enters then: capturable)."""
     from .critic import FusedTwinCritic
+    from .mlp2_head import FusedMLP2Head
+    from .mlp_critic import FusedTwinMLPCritic
     from .replay import as_draw
 
     draw = as_draw(buffer, indices, "td3_actor_loss")
-    if not isinstance(twin, FusedTwinCritic) or twin.env is not head.env:
+    if isinstance(head, FusedMLP2Head) or isinstance(twin, FusedTwinMLPCritic):  # the MLP family: both or neither
+        if not isinstance(head, FusedMLP2Head) or not isinstance(twin, FusedTwinMLPCritic) or twin.env is not head.env:
+            raise ValueError("a FusedMLP2Head goes with a FusedTwinMLPCritic of its env, an LSTM head with a FusedTwinCritic: "
+                             "the two families do not mix")
+    elif not isinstance(twin, FusedTwinCritic) or twin.env is not head.env:
         raise ValueError("twin must be a FusedTwinCritic of this head's env")
     if indices is None:
         raise ValueError("td3_actor_loss needs the indices of the sampled transitions")

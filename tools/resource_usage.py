@@ -1,9 +1,13 @@
 """Register / scratch table of every kernel in the product library (gfx950 cross-compile, no GPU needed).
 
-    python tools/resource_usage.py [-DKNOB=V ...] [--only PREFIX] [--out profiles/r03_resource_usage.txt]
+    python tools/resource_usage.py [-DKNOB=V ...] [--only PREFIX] [--source fe_mlp_critic.hip]
+                                   [--out profiles/r03_resource_usage.txt]
 
 ``--only PREFIX`` keeps the kernels whose name starts with PREFIX (profiles/critic_streamed_resource_usage.txt:
 ``--only fe_critic_sgrad_``).
+
+``--source NAME`` reads another translation unit of finenvs_amd/csrc than fe_env.hip
+(profiles/mlp_critic_resource_usage.txt: ``--source fe_mlp_critic.hip``).
 
 Compiles finenvs_amd/csrc/fe_env.hip with -Rpass-analysis=kernel-resource-usage (to a scratch .so under /tmp, the
 product library is not touched) and prints one line per kernel.  tests/test_resource_usage.py asserts on the same
@@ -33,19 +37,23 @@ def demangle(names):
     return [re.sub(r"\(anonymous namespace\)::", "", line).strip() for line in out.splitlines()]
 
 
-def kernel_table(defines=()):
-    """[{name, sgpr, vgpr, agpr, scratch, occupancy, sgpr_spill, vgpr_spill, lds}] for every kernel of the build.  One
-    compile per process and set of defines: the test modules that assert on the table share it."""
-    return [dict(row) for row in _kernel_table(tuple(defines))]
+def kernel_table(defines=(), source="fe_env.hip"):
+    """[{name, sgpr, vgpr, agpr, scratch, occupancy, sgpr_spill, vgpr_spill, lds}] for every kernel of the translation
+    unit ``source`` of finenvs_amd/csrc.  One compile per process, unit and set of defines: the test modules that assert
+    on the table share it."""
+    return [dict(row) for row in _kernel_table(tuple(defines), source)]
 
 
 @functools.lru_cache(maxsize=None)
-def _kernel_table(defines):
+def _kernel_table(defines, source="fe_env.hip"):
     from finenvs_amd.csrc import build as B
 
     with tempfile.TemporaryDirectory(prefix="fe_ru_") as tmp:
-        cmd = [B.HIPCC] + B.FLAGS + list(defines) + ["-Rpass-analysis=kernel-resource-usage"]
-        cmd += [os.path.join(B.HERE, "fe_env.hip"), "-o", os.path.join(tmp, "ru.so")]
+        flags = list(B.FLAGS)
+        if source != "fe_env.hip":  # a unit that calls into fe_env.hip's host code is compiled, not linked
+            flags[flags.index("-shared")] = "-c"
+        cmd = [B.HIPCC] + flags + list(defines) + ["-Rpass-analysis=kernel-resource-usage"]
+        cmd += [os.path.join(B.HERE, source), "-o", os.path.join(tmp, "ru.so")]
         err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     rows = []
     for block in re.split(r"remark: Function Name: ", err)[1:]:
@@ -96,7 +104,8 @@ def format_table(rows):
 
 if __name__ == "__main__":
     defs = [a for a in sys.argv[1:] if a.startswith("-D")]
-    rows = kernel_table(defs)
+    source = sys.argv[sys.argv.index("--source") + 1] if "--source" in sys.argv else "fe_env.hip"
+    rows = kernel_table(defs, source)
     if "--only" in sys.argv:
         prefix = sys.argv[sys.argv.index("--only") + 1]
         rows = [r for r in rows if r["name"].startswith(prefix)]
@@ -104,6 +113,8 @@ if __name__ == "__main__":
     if "--out" in sys.argv:
         path = sys.argv[sys.argv.index("--out") + 1]
         head = "# hipcc -O3 -ffp-contract=off --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage " + " ".join(defs) + "\n"
+        if source != "fe_env.hip":
+            head = head.rstrip() + f"   ({source})\n"
         with open(path, "w") as f:
             f.write(head + text + "\n")
     print(text)
