@@ -6,7 +6,10 @@ import torch
 from tests.helpers import crafted_descriptors
 
 
-@pytest.mark.parametrize("D,L,W,B", [(12, 60, 4, 33), (12, 60, 1, 1), (12, 430, 390, 33), (12, 60, 4, 1057)])
+# the last eight: the twin MLP critics' cases, their targets' batch of 513 and the rings' 520 slots (D = 12, L = max(60, W + 40))
+@pytest.mark.parametrize("D,L,W,B", [(12, 60, 4, 33), (12, 60, 1, 1), (12, 430, 390, 33), (12, 60, 4, 1057),
+                                     (12, 60, 1, 33), (12, 60, 7, 33), (12, 60, 16, 257), (12, 80, 40, 33),
+                                     (12, 60, 7, 513), (12, 60, 7, 520), (12, 60, 16, 520), (12, 60, 1, 520)])
 def test_crafted_descriptors_meet_their_conditions(D, L, W, B):
     src, pos = crafted_descriptors(D, L, W, B, seed=5)
     assert src.dtype is torch.int64 and tuple(src.shape) == (B,) and src.device.type == "cpu"

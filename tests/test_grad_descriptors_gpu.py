@@ -15,15 +15,20 @@ Per case and per kind of loss the family's own test uses:
   f64 module;
 * the same yardstick on the POSITION COLUMN alone -- ``w_ih[:, 4]`` of the LSTM head, the critics and the SAC actor,
   ``w1[:, 4::5]`` of the MLP heads, all three maxima over the slice -- and ``max|g64 slice| > 0``;
-* MLP and MLP2: ``w1.grad[:, 5 j + 4]`` is the same bits for every window row j.
+* MLP, MLP2 and the twin MLP critics: ``w1.grad[:, 5 j + 4]`` is the same bits for every window row j;
+* the twin MLP critics (the cases of the MLP heads; the arms ``critic``, ``actor`` and ``min`` of their own suite): the
+  yardstick also on the ACTION COLUMN ``w1[:, 5W]`` alone and on ``d_actions``, per critic the arm runs -- the maxima over
+  ``w1`` are taken over 4W log-return columns and the position column as well, so a small error in the one action column
+  could pass under them -- and ``td3_targets`` on a ring whose next-state descriptors are crafted.
 
 B = 33 is one full tile of 32 pairs and one ragged pair, 257 several tiles, and the third B of a family crosses its chunk
 (512 pairs for the MLP heads, ``fe_lstm_streamed_grad_chunk_pairs`` for the streamed head).
 
 Anchors, one per family, bit for bit: with ``pos = 1.0`` everywhere (the critics: ``actions = 1.0`` too) the position
 operand of the input-weight contraction IS the bias operand, so ``d w_ih[:, 4]`` must be ``d b_ih`` (the critics:
-``d w_ih[:, 5]`` as well).  Every family forms the two in one contraction -- the kernel lines are named in each anchor's
-docstring -- so none needed the yardstick form of the comparison.
+``d w_ih[:, 5]`` as well; the MLP critics: ``d w1[:, 5 j + 4]`` and ``d w1[:, 5W]`` must be ``d b1``).  Every family
+forms them in one contraction -- the kernel lines are named in each anchor's docstring -- so none needed the yardstick
+form of the comparison.
 
 Worst err / tol per case over kinds, (all whole tensors and values, the position slices), measured on an MI355X:
 MEASURED below.
@@ -38,6 +43,7 @@ from tests import test_critic_streamed_gpu as tcs
 from tests import test_lstm_grad_gpu as tl
 from tests import test_lstm_grad_streamed_gpu as ts
 from tests import test_mlp2_head_gpu as t2
+from tests import test_mlp_critic_gpu as tq
 from tests import test_mlp_head_gpu as th
 from tests import test_sac_grad_gpu as tsac
 from tests.helpers import crafted_descriptors_for
@@ -65,13 +71,18 @@ MEASURED = {
     ("mlp", 64, 4, 1057): (0.195, 0.045), ("mlp", 128, 72, 33): (0.072, 0.072),
     ("mlp2", 32, 1, 33): (0.032, 0.013), ("mlp2", 64, 7, 33): (0.048, 0.048), ("mlp2", 128, 16, 257): (0.076, 0.030),
     ("mlp2", 64, 4, 1057): (0.149, 0.099), ("mlp2", 128, 40, 33): (0.288, 0.120),
+    # slices: the position slice, the action column and d_actions of every arm
+    ("mlp critics", 32, 1, 33): (0.013, 0.010), ("mlp critics", 64, 7, 33): (0.027, 0.027),
+    ("mlp critics", 128, 16, 257): (0.029, 0.029), ("mlp critics", 64, 4, 1057): (0.118, 0.029),
+    ("mlp critics", 128, 40, 33): (0.032, 0.031),
 }
 # No draw had to be conditioned beyond the siblings' own rules, and no slice missed: every PPO input came from seed 7, and
 # ``t2._conditioned_module`` re-drew two MLP2 modules whose f64 copy reaches max|p| >= 4 (saturation) on these batches:
 # the value head of (32, 1, 33), seed 54 -> 1054 (4.008), and the actor of (64, 4, 1057), seed 88 -> 1088 (4.053).  With the position read replaced by 0.0f in the backward alone (fe_lstm_grad_kernels.h:83,
 # fe_lstm_stream_sgrad_body.h:64, fe_mlp_head_kernels.h:431, one at a time) every case and anchor of the family above
 # fails by three to five orders of magnitude, while the siblings' cases with B <= 4096 at H <= 128 and H >= 256 all stay
-# green (NOTES.md).
+# green (NOTES.md).  The twin MLP critics: ``tq._conditioned`` replaced no critic seed (20 + H + W and 21 + H + W meet the
+# conditions on every case's crafted batch) and no descriptor seed was changed; the mutants these cases catch: NOTES.md.
 
 
 def _ratio(gf, gt, gd):
@@ -432,6 +443,114 @@ def test_mlp2_head(H, W, B, activation, obs_dtype):
     _mlp_case(t2, "mlp2", FusedMLP2Head, t2._conditioned_module, t2.WMAX, H, W, B, activation, obs_dtype)
 
 
+# ------------------------------------------------------------------------------------------------- the twin MLP critics
+def _mlpq_slices(tally, kind, twin, W, g, g32, g64):
+    """The yardstick on the position slice, the action column and ``d_actions`` alone, all three maxima over the slice; the
+    position gradient is one value per hidden unit, copied into the W slots ``5 j + 4``."""
+    H = twin.H
+    for c in ((0,) if kind == "actor" else (0, 1)):  # the actor arm runs critic 1 only
+        w, w32, w64 = g[6 * c], g32[6 * c], g64[6 * c]
+        assert tuple(w.shape) == (H, 5 * W + 1)
+        tally.slice = max(tally.slice, _within(f"{kind} c{c + 1}.w1[:, 4::5]", w[:, 4::5], w32[:, 4::5], w64[:, 4::5]))
+        tally.slice = max(tally.slice, _within(f"{kind} c{c + 1}.w1[:, 5W]", w[:, 5 * W], w32[:, 5 * W], w64[:, 5 * W]))
+        cols = w[:, :5 * W].reshape(H, W, 5)[..., 4]
+        tl.assert_bits(cols.contiguous(), cols[:, :1].expand(-1, W).contiguous())
+    tally.slice = max(tally.slice, _within(f"{kind} d_actions", g[12], g32[12], g64[12]))
+
+
+@pytest.mark.parametrize("H,W,B,activation,obs_dtype", MLP_CASES)
+def test_twin_mlp_critics(H, W, B, activation, obs_dtype):
+    """tests/test_mlp_critic_gpu.py::test_gradients_against_f64_torch on crafted descriptors, with the values, the position
+    slice ``w1[:, 4::5]``, the action column ``w1[:, 5W]`` (column ``K4 + 1`` of ``fe_mlpq_wgrad_kernel``, which the
+    whole-tensor maximum of ``w1`` hides behind the 4W log-return columns) and ``d_actions`` under the yardstick alone."""
+    from finenvs_amd import _lib
+    from finenvs_amd.mlp_critic import FusedTwinMLPCritic
+
+    W = _lib.MLP2_MAX_WINDOW[128] if W == "largest" else W
+    env = th._env(min(B, 4096), W, obs_dtype=obs_dtype)
+    src, pos = crafted_descriptors_for(env, B, seed=800 + H + W)
+    states = env.render(src, pos)
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    actions = torch.rand((B, 1), generator=gen, device="cuda") * 2 - 1
+    critics = [tq._conditioned(states, actions, H, W, 20 + H + W + i, activation) for i in (0, 1)]
+    kink = tq._conditions(critics[0], states, actions) | tq._conditions(critics[1], states, actions)
+    assert int(kink.sum()) <= 0.02 * B
+    with torch.no_grad():
+        q64 = [copy.deepcopy(c).double()(states.double(), actions.double()) for c in critics]
+        q32 = [c(states.float(), actions) for c in critics]
+    y = (0.5 * (q64[0] + q64[1]) + 0.3 * torch.randn((B, 1), generator=gen, device="cuda", dtype=F64)).float()
+    twin = FusedTwinMLPCritic(env, *critics)
+    tally = _Tally(("mlp critics", H, W, B))
+    for i, q in enumerate(twin.forward(src, pos, actions)):
+        tally.whole = max(tally.whole, _within(f"q{i + 1}", q, q32[i], q64[i]))
+    for kind in ("critic", "actor", "min"):
+        keep = ~kink
+        if kind == "min":  # f32 and f64 may pick different critics where the two values nearly tie
+            tie = (q64[0] - q64[1]).abs() < 1e-4
+            assert int((kink | tie).sum()) <= 0.02 * B
+            keep = keep & ~tie
+        loss, g = tq._fused_grads(kind, twin, src, pos, actions, keep, y)
+        l32, g32 = tq._torch_grads(kind, critics, states, actions, keep, y, F32)
+        l64, g64 = tq._torch_grads(kind, critics, states, actions, keep, y, F64)
+        assert len(g) == len(g32) == len(g64) == 2 * len(tq.NAMES) + 1
+        tally.whole = max(tally.whole, tq._compare(kind, g, g32, g64))
+        err, tol = abs(float(loss) - float(l64)), 2e-5 * abs(float(l64)) + 4 * abs(float(l32) - float(l64)) + 1e-7
+        assert err <= tol, (kind, "loss", err, tol)
+        _mlpq_slices(tally, kind, twin, W, g, g32, g64)
+    tally.report()
+
+
+@pytest.mark.parametrize("H,W,activation,B", [(64, 7, "relu", 513), (128, 16, "tanh", 33), (32, 1, "elu", 33)])
+def test_twin_mlp_critic_targets_on_crafted_next_descriptors(H, W, activation, B):
+    """tests/test_mlp_critic_gpu.py::test_td3_targets_against_torch_on_rendered_next_states with the ring's next-state
+    descriptors of ALL its slots replaced by crafted ones (windows all over the table, its first and its last, positions
+    that are not zero), ReLU, Tanh and W in {1, 7, 16}.  Measured err / tol on an MI355X: (64, 7, relu, 513) 0.023,
+    (128, 16, tanh, 33) 0.029, (32, 1, elu, 33) 0.016."""
+    from finenvs_amd.critic import torch_td3_targets
+    from finenvs_amd.mlp_critic import FusedTwinMLPCritic
+
+    gamma, scale = 0.97, 0.5
+    env = th._env(190, W)
+    buffer, store = tq._filled(env, H, 2, max_size=3 * 190 - 50)
+    store(1)  # wrapped: head != 0
+    C_ = buffer.max_size
+    assert buffer.head != 0 and buffer.size() == C_
+    src, pos = crafted_descriptors_for(env, C_, seed=900 + H + W)
+    with torch.no_grad():
+        buffer.next_src.copy_(src)
+        buffer.next_pos.copy_(pos)
+        buffer.dones[1::5] = 1.0
+    c1, c2 = tq._critic(H, W, 50, activation), tq._critic(H, W, 51, activation)
+    actor = tq._actor(H, W, 52, activation)
+    with torch.no_grad():
+        actor.network[4].weight.mul_(3.0)  # actions over the whole range, some beyond the clamp after smoothing
+    target = t2._rollout(env, actor)
+    twin = FusedTwinMLPCritic(env, c1, c2)
+    gen = torch.Generator(device="cuda").manual_seed(B + W)
+    idx = torch.randint(0, buffer.size(), (B,), generator=gen, device="cuda")
+    idx[0], idx[B - 1] = buffer.size() - 1, 0  # the newest and the oldest transition
+    eps = torch.randn((B, 1), generator=gen, device="cuda")
+    y = twin.td3_targets(buffer, idx, target, eps, gamma, 0.2, 0.5, scale)
+    b = buffer.get_mini_batch(B, indices=idx)
+    slots = buffer.physical(idx)
+    ys = []
+    for dtype in (F32, F64):
+        a, d1, d2 = (copy.deepcopy(m).to(dtype) for m in (actor, c1, c2))
+        ys.append(torch_td3_targets(lambda x: a(x.to(dtype)), d1, d2, b["rewards"].to(dtype), b["next_states"].to(dtype),
+                                    b["dones"].to(dtype), eps.to(dtype), gamma, 0.2, 0.5, scale).double())
+    _within(f"td3_targets ({H}, {W}, {activation}, {B})", y, ys[0], ys[1])
+    last = twin.last
+    expr = b["rewards"] * scale + gamma * (1 - b["dones"]) * torch.minimum(last["q1"], last["q2"])
+    tl.assert_bits(y, expr)  # the TD3 epilogue
+    a = torch.clamp(last["next_actions"] + torch.clamp(eps * 0.2, -0.5, 0.5), -1, 1)
+    assert bool((a.abs() == 1).any()) and bool((a.abs() < 1).any())
+    q1, q2 = twin.forward(buffer.next_src[slots], buffer.next_pos[slots].reshape(B), a)
+    tl.assert_bits(q1, last["q1"])  # the TD3 smoothing in the kernel
+    tl.assert_bits(q2, last["q2"])
+    done = b["dones"].reshape(-1) == 1
+    assert bool(done.any()) and not bool(done.all()) and torch.equal(y[done], (b["rewards"] * scale)[done])
+
+
 # ------------------------------------------------------------------------------------------------- anchors, bit for bit
 def _unit_descriptors(env, B, seed):
     src, pos = crafted_descriptors_for(env, B, seed=seed)
@@ -574,3 +693,25 @@ def test_anchor_mlp2_head_position_columns_are_the_bias_gradient():
     env = th._env(B, W)
     src, pos = _unit_descriptors(env, B, 707)
     _mlp_anchor(t2, FusedMLP2Head(env, t2._module(H, W, 20, "elu", "tanh")), src, pos, W)
+
+
+def test_anchor_twin_mlp_critics_position_and_action_columns_are_the_bias_gradient():
+    """``fe_mlpq_wgrad_kernel`` (``fe_mlp_critic_kernels.h:364-366``) feeds columns ``K4``, ``K4 + 1`` and ``K4 + 2`` of one
+    MFMA chain ``(float)obs_pos``, the action and the constant 1 -- at W = 4 columns 16, 17 and 18 of the one 32-column
+    tile -- against the same ``dz1`` rows; ``fe_mlpq_grad_reduce_kernel`` (``:396-404``) adds the splits of each in f64 in
+    the same order, copies column ``K4`` into the W slots ``5 j + 4`` and sends ``K4 + 1`` to ``w1[:, 5 W]`` and ``K4 + 2``
+    to ``b1``.  With ``pos = 1.0`` and ``actions = 1.0`` the three operands are the same numbers.  Bit for bit."""
+    from finenvs_amd.mlp_critic import FusedTwinMLPCritic
+
+    H, W, B = 64, 4, 33
+    env = th._env(B, W)
+    src, pos = _unit_descriptors(env, B, 708)
+    twin = FusedTwinMLPCritic(env, tq._critic(H, W, 10), tq._critic(H, W, 11))
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    y = torch.randn((B, 1), generator=gen, device="cuda") - 1.0
+    keep = torch.ones((B, 1), dtype=torch.bool, device="cuda")
+    _, g = tq._fused_grads("critic", twin, src, pos, torch.ones((B, 1), device="cuda"), keep, y)
+    for k in (0, 6):
+        for j in range(W):
+            _same_bits_and_not_zero(g[k][:, 5 * j + 4], g[k + 1])
+        _same_bits_and_not_zero(g[k][:, 5 * W], g[k + 1])

@@ -22,6 +22,7 @@ FusedMLP2Rollout).
   gradient buffers, ``out``, ``means_out`` and the descriptor rows, and NaN-filled buffers give the bits of
   sentinel-filled ones;
 * the window limit at H = 128, refusals, and examples/ppo_mlp_fused.py with ``hidden_layers=2``.
+* banded inputs, an uneven count of 65 569 pairs and the argument layouts: tests/test_mlp_memory_contract_gpu.py.
 """
 import copy
 import ctypes as C

@@ -16,6 +16,8 @@ Shapes (H, W, B): (32, 4, 33) a ragged last 32-pair block, (64, 7, 513) a crosse
   rendered next states, an out-of-range index, a ``ReplayDraw``, a ``GraphedUpdate`` replay against an eager twin;
 * behaviour (determinism, ``.grad`` accumulation, a frozen critic, B = 0), the memory contract, the window limit, the
   refusals that read the env, and examples/td3_mlp_fused.py.
+* banded inputs, an uneven count of 65 569 pairs, every form of the backward and the argument layouts:
+  tests/test_mlp_memory_contract_gpu.py; crafted descriptors and the action column alone: tests/test_grad_descriptors_gpu.py.
 """
 import copy
 import ctypes as C
@@ -607,7 +609,7 @@ def test_memory_contract_of_forward_and_backward(H, W, B):
     n_ws = int(lib.fe_twin_mlpq_grad_workspace_floats(H, W, B))
     sizes = {"w1": H * (5 * W + 1), "b1": H, "w2": H * H, "b2": H, "w3": H, "b3": 1}
     results = []
-    for poison in (float("nan"), 0.0):
+    for poison in (float("nan"), SENTINEL):
         big_ws, ws = _window(n_ws, F32, poison)
         big_da, da = _window(B, F32, poison)
         wins = [{k: _window(n, F32, poison) for k, n in sizes.items()} for _ in range(2)]
@@ -625,7 +627,7 @@ def test_memory_contract_of_forward_and_backward(H, W, B):
         assert bool(torch.isfinite(da).all())
         results.append([x[k][1].clone() for x in wins for k in NAMES] + [da.clone()])
     for a, b in zip(*results):
-        assert_bits(a, b, "a NaN-filled workspace against a zero-filled one")
+        assert_bits(a, b, "a NaN-filled workspace against a sentinel-filled one")
     _zero(c1, c2)
     a = actions.clone().requires_grad_(True)
     q1, q2 = twin.q(src, pos, a)

@@ -21,6 +21,7 @@
 * examples/ppo_mlp_fused.py with ``fused_update=True`` trains without rendering anything, the kernel acts with the updated
   weights, and one Adam step of a fused head agrees with an eager torch twin on the rendered mini-batch within the
   gradient yardstick propagated through Adam (bound stated at ``_adam_bound``).
+* banded inputs, an uneven count of 65 569 pairs and the argument layouts: tests/test_mlp_memory_contract_gpu.py.
 """
 import copy
 import ctypes as C
