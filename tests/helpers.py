@@ -42,6 +42,66 @@ def assert_bits(a, b, what=""):
         raise AssertionError(f"{what}: {bad.shape[0]} mismatching elements, first at {i}: {a[i]!r} vs {b[i]!r}")
 
 
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+_SHIFT32 = np.uint64(32)
+EVO_DOMAIN_Z, EVO_DOMAIN_ACT = 0x45565A00, 0x45564100  # word c3 of the two counters (include/finenvs_amd_evo.h)
+
+
+def philox4x32_10(key, c0, c1, c2, c3):
+    """Philox4x32-10 (Salmon et al., SC'11; the Random123 recurrence), all four output words, vectorised: the counter
+    words broadcast against each other, the result is four uint32 arrays of the broadcast shape.  ``key`` is the pair
+    ``(k0, k1)`` or one integer below 2^64 whose low half is ``k0`` (how the library keys its streams with a seed)."""
+    if isinstance(key, (tuple, list)):
+        k0, k1 = (int(k) & 0xFFFFFFFF for k in key)
+    else:
+        k0, k1 = int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF
+    c = [np.asarray(x).astype(np.uint64) & _U32 for x in np.broadcast_arrays(c0, c1, c2, c3)]
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c[0], _PHILOX_M1 * c[2]  # 32 x 32 bits: below 2^64
+        c = [(p1 >> _SHIFT32) ^ c[1] ^ np.uint64(k0), p1 & _U32, (p0 >> _SHIFT32) ^ c[3] ^ np.uint64(k1), p0 & _U32]
+        k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+    return tuple(x.astype(np.uint32) for x in c)
+
+
+def box_muller_radius(w):
+    """``(u, r)`` of a uint32 word in f64: ``u = ((w >> 8) + 1) / 2^24`` in (0, 1], ``r = sqrt(-2 ln u)``."""
+    u = ((np.asarray(w).astype(np.uint64) >> np.uint64(8)).astype(np.float64) + 1.0) / 2.0 ** 24
+    return u, np.sqrt(-2.0 * np.log(u))
+
+
+def box_muller4(w0, w1, w2, w3):
+    """The Box-Muller transform of include/finenvs_amd_evo.h on four Philox words, evaluated in f64: the radius from the
+    top 24 bits of ``w0`` (``w2``), the angle ``(w1 >> 8) / 2^24`` (``w3``) in revolutions; normals 0 and 1 are
+    ``r0 cos``, ``r0 sin``, normals 2 and 3 the same from ``(w2, w3)``.  Returns an array with a last axis of 4."""
+    out = []
+    for wu, wt in ((w0, w1), (w2, w3)):
+        _, r = box_muller_radius(wu)
+        t = (np.asarray(wt).astype(np.uint64) >> np.uint64(8)).astype(np.float64) / 2.0 ** 24
+        out += [r * np.cos(2.0 * np.pi * t), r * np.sin(2.0 * np.pi * t)]
+    return np.stack(out, axis=-1)
+
+
+def evo_z_reference(seed, g, pairs, P):
+    """``z_{g,p,j}`` of include/finenvs_amd_evo.h for ``p`` in ``pairs`` and ``j < P``, ``(len(pairs), P)`` f64: word
+    ``j % 4`` of the transform of Philox(key = seed, counter = (j / 4, p, g, 0x45565a00)).  Written from the header's
+    text; the device code is not consulted."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1)
+    q = np.arange((int(P) + 3) // 4, dtype=np.int64)
+    z = box_muller4(*philox4x32_10(seed, q[None, :], pairs[:, None], int(g), EVO_DOMAIN_Z))
+    return z.reshape(pairs.size, -1)[:, :int(P)]
+
+
+def evo_action_noise_reference(seed, g, step, n, a):
+    """The action noise ``xi`` of env ``n``, asset ``a`` at step ``step`` of generation ``g`` (the four broadcast), f64: word
+    ``a % 4`` of the transform of Philox(key = seed, counter = (n, step, g, 0x45564100 | a / 4))."""
+    step, n, a = np.broadcast_arrays(np.asarray(step, dtype=np.int64), np.asarray(n, dtype=np.int64),
+                                     np.asarray(a, dtype=np.int64))
+    z = box_muller4(*philox4x32_10(seed, n, step, int(g), EVO_DOMAIN_ACT | (a // 4)))
+    return np.take_along_axis(z, (a % 4)[..., None], axis=-1)[..., 0]
+
+
 def crafted_descriptors(D, L, W, B, seed, pos_scale=0.5):
     """``(src int64 (B,), pos float64 (B, 1))`` on the CPU: B observation descriptors of a one-asset log-return table of D
     days x L rows (``row_elems = 4``), drawn without an env -- windows the env's own reset states never hold, and
