@@ -157,3 +157,120 @@ def econ_kwargs(g):
         initial_margin_requirement=float(g["imr"]),
         maintenance_margin_requirement=float(g["mmr"]),
     )
+
+
+# ----------------------------------------------------------------------------------------------- saturated ("hot") modules
+def cpu_states(days, bars, W, seed, src, pos):
+    """``env.render(src, pos)`` of the one-asset env the gradient suites build (``synthetic_series(days, 1, bars, seed, 0)``)
+    without a GPU: ``(B, W, 5)`` f64 on the CPU, rows ``src / 4 + j`` of the oracle's log-return table and the position in
+    column 4.  Also returns the table's ``(D, L)``."""
+    import torch
+
+    from finenvs_amd.data import synthetic
+    from oracle import fe_oracle
+
+    fe_oracle.build()
+    prices, day_id, _ = synthetic.synthetic_series(days, 1, bars, seed, 0.0)
+    _, LR, *_ = fe_oracle.tables_from_series(prices, day_id, W)
+    D, L, _ = LR.shape
+    table = torch.from_numpy(np.ascontiguousarray(LR, dtype=np.float64)).reshape(D * L, 4)
+    rows = (src.cpu().reshape(-1, 1) // 4) + torch.arange(W).reshape(1, W)
+    states = torch.cat([table[rows], pos.cpu().double().reshape(-1, 1, 1).expand(-1, W, 1)], dim=2)
+    assert not bool(torch.isnan(states).any())
+    return states, (D, L)
+
+
+class modules_on_cpu:
+    """Inside the block ``nn.Module.cuda()`` returns the module as it is, so that the GPU suites' own module builders
+    (``_module``, ``_critic``, ``_actor``: they draw on the CPU and end in ``.cuda()``) can be called without a GPU.  For
+    the CPU tests of conditions on those builders; nothing inside may launch a kernel."""
+
+    def __enter__(self):
+        import torch
+
+        self._cuda = torch.nn.Module.cuda
+        torch.nn.Module.cuda = lambda module, device=None: module
+
+    def __exit__(self, *exc):
+        import torch
+
+        torch.nn.Module.cuda = self._cuda
+
+
+def heat(module, gate_scale, out_scale):
+    """Make a family's module "hot", in place: the recurrent layer of an LSTM module (``weight_ih``, ``weight_hh``, both
+    biases) or the first layer and its bias of an MLP module (``network``) times ``gate_scale``; the layer that feeds the
+    output (``last_layer[0]`` of the LSTM head and critic, ``mu_layer`` of the SAC actor, the last ``Linear`` of an MLP)
+    times ``out_scale``.  Returns the module."""
+    import torch
+
+    with torch.no_grad():
+        if hasattr(module, "lstm"):
+            for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                getattr(module.lstm, name).mul_(gate_scale)
+            out = module.mu_layer if hasattr(module, "mu_layer") else module.last_layer[0]
+        else:
+            linear = [m for m in module.network if isinstance(m, torch.nn.Linear)]
+            linear[0].weight.mul_(gate_scale)
+            linear[0].bias.mul_(gate_scale)
+            out = linear[-1]
+        out.weight.mul_(out_scale)
+        out.bias.mul_(out_scale)
+    return module
+
+
+def hot_preactivations(module, states, actions=None, eps=None):
+    """``(z, p)`` of the f64 copy of a family's module on rendered ``states`` (``actions``: the critics' second input;
+    ``eps``: the SAC actor's noise): ``z`` every gate pre-activation of the LSTM at every step, ``(B, W, 4H)``, or every
+    pre-activation of the MLP's first hidden layer, ``(B, H)``; ``p`` the pre-activation of the output ``(B, 1)`` (the
+    SAC actor: ``u = mu + eps s``)."""
+    import copy
+
+    import torch
+
+    m = copy.deepcopy(module).double()
+    x = states.double()
+    B = x.shape[0]
+    with torch.no_grad():
+        if hasattr(m, "lstm"):
+            if actions is not None:
+                x = torch.cat([x, actions.double().reshape(B, 1, 1).expand(-1, x.shape[1], 1)], dim=2)
+            H = m.lstm.hidden_size
+            h, c, zs = x.new_zeros((B, H)), x.new_zeros((B, H)), []
+            for t in range(x.shape[1]):
+                z = x[:, t] @ m.lstm.weight_ih_l0.t() + m.lstm.bias_ih_l0 + h @ m.lstm.weight_hh_l0.t() + m.lstm.bias_hh_l0
+                i, f, g, o = z.chunk(4, dim=1)
+                c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+                h = torch.sigmoid(o) * torch.tanh(c)
+                zs.append(z)
+            assert float((h - m.lstm(x)[0][:, -1]).abs().max()) < 1e-9  # the recurrence written out is nn.LSTM's
+            z = torch.stack(zs, dim=1)
+            if hasattr(m, "mu_layer"):
+                hid = m.last_layer(h)
+                p = m.mu_layer(hid) + eps.double() * torch.nn.functional.softplus(m.std_layer(hid))
+            else:
+                p = m.last_layer[0](h)
+        else:
+            x = x.reshape(B, -1)
+            if actions is not None:
+                x = torch.cat([x, actions.double().reshape(B, 1)], dim=1)
+            z = m.network[0](x)
+            p = m.network[:-1](x)
+    return z, p
+
+
+def hot_shares(z, p, lstm, tanh_output):
+    """The saturated shares of ``hot_preactivations``' result, asserted against the conditions a hot case rests on
+    (conditions on the f64 reference, not measurements); returns them as a dict."""
+    def share(mask):
+        return float(mask.double().mean())
+
+    s = {"z>17": share(z.abs() > 17), "z>60": share(z.abs() > 60), "z<2": share(z.abs() < 2)}
+    assert s["z>17"] >= 0.10 and s["z<2"] >= 0.03, s
+    if lstm:
+        assert s["z>60"] >= 0.01, s  # the clamp of the exponential's argument
+    if tanh_output:
+        a = p.abs()
+        s.update({"p<2": share(a < 2), "p4-9": share((a > 4) & (a < 9)), "p>9.1": share(a > 9.1)})
+        assert s["p<2"] >= 0.20 and s["p4-9"] >= 0.20 and s["p>9.1"] >= 0.05, s
+    return s
