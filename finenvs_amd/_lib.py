@@ -360,6 +360,34 @@ MLP_CRITIC_SIGNATURES = {
     "fe_twin_mlpq_backward": (C.c_int, [_vp, _vp, _qw, _qw, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _qg, _qg, _vp, _vp]),
 }
 
+# include/finenvs_amd_mlp_sac.h: the SAC MLP actor with the folded head (finenvs_amd/mlp_sac.py)
+MLP_SAC_GRAD_CHUNK_PAIRS = 512  # FE_MLP_SAC_GRAD_CHUNK_PAIRS
+MLP_SAC_GRAD_MAX_GROUPS = 256  # FE_MLP_SAC_GRAD_MAX_GROUPS
+MLP_SAC_MAX_WINDOW = {32: 304, 64: 144, 128: 72}  # FE_MLP_SAC_MAX_WINDOW_H*: the largest window admitted with one asset
+
+
+class FeMlpSacWeights(C.Structure):
+    """struct fe_mlp_sac_weights of include/finenvs_amd_mlp_sac.h."""
+
+    _fields_ = [("w1t", _vp), ("wpos", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("wmu", _vp), ("bmu", _vp), ("wstd", _vp),
+                ("bstd", _vp), ("vmu", _vp), ("vstd", _vp), ("cfold", _vp)]
+
+
+class FeMlpSacGrads(C.Structure):
+    """struct fe_mlp_sac_grads of include/finenvs_amd_mlp_sac.h."""
+
+    _fields_ = [("w1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp), ("w_mu", _vp), ("b_mu", _vp), ("w_std", _vp), ("b_std", _vp)]
+
+
+_sw, _sg = C.POINTER(FeMlpSacWeights), C.POINTER(FeMlpSacGrads)
+MLP_SAC_SIGNATURES = {
+    "fe_mlp_sac_pack": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_env_rollout_mlp_sac": (C.c_int, [_vp, _vp, _sw, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_mlp_sac_forward": (C.c_int, [_vp, _vp, _sw, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fe_mlp_sac_grad_workspace_floats": (_i64, [_i32, _i32, _i64]),
+    "fe_mlp_sac_backward": (C.c_int, [_vp, _vp, _sw, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sg, _vp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -389,7 +417,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
                          **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES,
-                         **MLP_CRITIC_SIGNATURES}.items():
+                         **MLP_CRITIC_SIGNATURES, **MLP_SAC_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -206,8 +206,8 @@ class _FusedTwin:
     depend on the network -- the checks of devices, vectors and indices, the ring's descriptors, the NaN rule for an index
     outside ``[0, size)``, ``ReplayDraw`` handling, the critic loss and the target launches' argument lists.  A family
     provides ``forward``, ``q``, ``_weights()`` (the two ctypes weight structs), ``_shape_args()`` (what its C entries
-    take between the weights and the descriptors: ``H``, or ``H`` and the activation), ``_target_entry(cursor)`` and
-    ``_check_target_actor``."""
+    take between the weights and the descriptors: ``H``, or ``H`` and the activation), ``_target_entry(cursor)``,
+    ``_check_target_actor`` and ``_check_sac_actor``."""
 
     def _check_devices(self) -> None:
         dev = torch.device(self.env._dev)
@@ -309,6 +309,33 @@ class _FusedTwin:
         noise = self._vector(noise, B, "noise")
         return self._targets(buffer, idx, actions, noise, policy_std, policy_clip, None, None, gamma, reward_scale, draw)
 
+    def sac_targets(self, buffer, indices: Optional[torch.Tensor], actor_roll, noise: Optional[torch.Tensor] = None,
+                    gamma: float = 0.99, log_alpha: Optional[torch.Tensor] = None, reward_scale: float = 1.0,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+        """``SACAgent.compute_targets`` (SAC_agent.py:200-227) for the transitions ``indices`` (logical, (B,)) of
+        ``buffer``: the actor half in ``actor_roll.forward`` (``FusedTwinCritic``: a ``FusedSACRollout``,
+        ``FusedTwinMLPCritic``: a ``FusedMLPSACRollout`` of its env) on the sampled next descriptors with
+        ``noise`` (B, 1) standard normals -- by default ``torch.randn``, the draw ``rsample`` makes -- then both target
+        critics and ``y = r + gamma * (1 - d) * (min(q1, q2) - alpha * log_prob)`` with ``alpha = log_alpha.exp()``,
+        ``r`` the stored reward times ``reward_scale``.  (B, 1) float32.  ``indices=None`` draws ``batch_size`` of them as
+        ``get_mini_batch`` does; ``self.last`` keeps the indices, next actions, log-probabilities and values.
+        ``indices`` may be a ``ReplayDraw`` of a ``cursor=True`` buffer: its gathered next descriptors are used and the
+        ring's head and size are read from the cursor (``fe_twin_q_target_c``), so the call is capturable."""
+        draw = as_draw(buffer, indices, "sac_targets")
+        self._check_sac_actor(actor_roll)
+        if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.device != torch.device(self.env._dev):
+            raise ValueError(f"log_alpha must be a one-element tensor on {self.env._dev}")
+        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
+        B = int(idx.numel())
+        if noise is None:
+            noise = torch.randn((B, 1), device=self.env._dev)
+        src, pos = self._next_descriptors(buffer, idx, draw)
+        actions, log_probs, _, _ = actor_roll.forward(src, pos, noise=noise.reshape(B, 1))
+        alpha = log_alpha.detach().exp().float().reshape(1).contiguous()
+        y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale, draw)
+        self.last.update(log_probs=log_probs, alpha=alpha)
+        return y
+
 
 class FusedTwinCritic(_FusedTwin):
     """Two LSTM critics of the same H evaluated together on the device (C ABI of include/finenvs_amd_critic.h).
@@ -369,6 +396,12 @@ class FusedTwinCritic(_FusedTwin):
         if not isinstance(target_actor, FusedLSTMRollout) or target_actor.out_act != 0:
             raise ValueError('target_actor must be a FusedLSTMRollout with output_activation="tanh"')
 
+    def _check_sac_actor(self, actor_roll) -> None:
+        from .sac import FusedSACRollout
+
+        if not isinstance(actor_roll, FusedSACRollout):
+            raise ValueError("actor_roll must be a FusedSACRollout (the SAC actor's head)")
+
     def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
         """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
         descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
@@ -406,35 +439,6 @@ class FusedTwinCritic(_FusedTwin):
             raise ValueError("the fused critic's gradient needs float32 parameters")
         q1, q2 = _TwinQ.apply(self, src, pos, actions, *params)
         return q1, q2
-
-    def sac_targets(self, buffer, indices: Optional[torch.Tensor], actor_roll, noise: Optional[torch.Tensor] = None,
-                    gamma: float = 0.99, log_alpha: Optional[torch.Tensor] = None, reward_scale: float = 1.0,
-                    batch_size: Optional[int] = None) -> torch.Tensor:
-        """``SACAgent.compute_targets`` (SAC_agent.py:200-227) for the transitions ``indices`` (logical, (B,)) of
-        ``buffer``: the actor half in ``actor_roll.forward`` (a ``FusedSACRollout``) on the sampled next descriptors with
-        ``noise`` (B, 1) standard normals -- by default ``torch.randn``, the draw ``rsample`` makes -- then both target
-        critics and ``y = r + gamma * (1 - d) * (min(q1, q2) - alpha * log_prob)`` with ``alpha = log_alpha.exp()``,
-        ``r`` the stored reward times ``reward_scale``.  (B, 1) float32.  ``indices=None`` draws ``batch_size`` of them as
-        ``get_mini_batch`` does; ``self.last`` keeps the indices, next actions, log-probabilities and values.
-        ``indices`` may be a ``ReplayDraw`` of a ``cursor=True`` buffer: its gathered next descriptors are used and the
-        ring's head and size are read from the cursor (``fe_twin_q_target_c``), so the call is capturable."""
-        from .sac import FusedSACRollout
-
-        draw = as_draw(buffer, indices, "sac_targets")
-        if not isinstance(actor_roll, FusedSACRollout):
-            raise ValueError("actor_roll must be a FusedSACRollout (the SAC actor's head)")
-        if not isinstance(log_alpha, torch.Tensor) or log_alpha.numel() != 1 or log_alpha.device != torch.device(self.env._dev):
-            raise ValueError(f"log_alpha must be a one-element tensor on {self.env._dev}")
-        idx = self._indices(buffer, indices if draw is None else draw.indices, batch_size)
-        B = int(idx.numel())
-        if noise is None:
-            noise = torch.randn((B, 1), device=self.env._dev)
-        src, pos = self._next_descriptors(buffer, idx, draw)
-        actions, log_probs, _, _ = actor_roll.forward(src, pos, noise=noise.reshape(B, 1))
-        alpha = log_alpha.detach().exp().float().reshape(1).contiguous()
-        y = self._targets(buffer, idx, actions, None, 0.0, 0.0, log_probs, alpha, gamma, reward_scale, draw)
-        self.last.update(log_probs=log_probs, alpha=alpha)
-        return y
 
 
 # ---------------------------------------------------------------- the torch restatements (host or device)

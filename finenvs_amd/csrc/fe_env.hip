@@ -2806,7 +2806,7 @@ int fe_ppo_value_loss(const float *values, const float *returns, int64_t count, 
 
 }  // extern "C"
 
-// ---- what the library's second translation unit (fe_mlp_critic.hip) needs of this one: hidden visibility, as
+// ---- what the library's other translation units (fe_mlp_critic.hip, fe_mlp_sac.hip) need of this one: hidden visibility, as
 // fe_set_error is shared with fe_csv.cpp.  Host code only: this unit's device code object is what it was. ----
 // An env's window, asset count and device.
 extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(const fe_env *env, int32_t *W, int32_t *A, int *device) {
@@ -2819,4 +2819,16 @@ extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(cons
 extern "C" __attribute__((visibility("hidden"))) int fe_prepare_big_lds_internal(int device, const void *kern, size_t lds,
                                                                                  const char *who) {
     return prepare_big_lds(device, kern, lds, who);
+}
+
+// What a K-step MLP rollout of the third unit (fe_mlp_sac.hip) takes from the env, as rollout_mlp_sampled_impl does: the
+// state is bound, a copy of the parameter block with the rollout's tile set (128 pairs per workgroup), and the grid.
+extern "C" __attribute__((visibility("hidden"))) int fe_env_mlp_rollout_internal(const fe_env *env, const char *who, void *params_out,
+                                                                                 size_t params_bytes, int64_t *grid_out) {
+    if (int rc = require_bound(env, who)) return rc;
+    if (params_bytes != sizeof(Params)) return fail(FE_ERR_STATE, "%s: the units disagree about the parameter block", who);
+    Params p = env->p;
+    *grid_out = rollout_geometry(env, p, mlp_tile_envs(p), /*replace=*/true);
+    memcpy(params_out, &p, sizeof(p));
+    return FE_OK;
 }

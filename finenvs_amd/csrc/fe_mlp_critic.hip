@@ -24,6 +24,7 @@
 
 #define FE_ERROR_BUFFER_ELSEWHERE 1
 #include "fe_mlp_critic_kernels.h"
+#include "fe_host_common.h"
 
 extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(const fe_env *env, int32_t *W, int32_t *A, int *device);
 extern "C" __attribute__((visibility("hidden"))) int fe_prepare_big_lds_internal(int device, const void *kern, size_t lds,
@@ -31,50 +32,7 @@ extern "C" __attribute__((visibility("hidden"))) int fe_prepare_big_lds_internal
 
 namespace {
 
-// The launch helpers of fe_env.hip this unit needs, restated (they are a few lines each; the kernels do not move).
-constexpr int64_t kMaxGrid = 8 * 256;
-constexpr size_t kMaxLds = 160 * 1024;
-
-[[maybe_unused]] const auto kHostFastDiv = &make_fastdiv;  // fe_device_common.h's host helper; no kernel here divides
-
-int64_t capped_grid(int64_t tiles) { return tiles < kMaxGrid ? tiles : kMaxGrid; }
-
-int grid_for(int64_t work_items) {
-    const int64_t g = (work_items + kBlock - 1) / kBlock;
-    return (int)(g < 1 ? 1 : capped_grid(g));
-}
-
-// "<who>: <what> launch: <HIP error>"
-int launched(const char *who, const char *what, hipError_t he) {
-    return he == hipSuccess ? FE_OK : fail(FE_ERR_HIP, "%s: %s launch: %s", who, what, hipGetErrorString(he));
-}
-
-// Makes the env's device current for the duration of a call (fe_env.hip's DeviceGuard).
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) {
-            err = hipSetDevice(device);
-            switched = err == hipSuccess;
-        }
-    }
-    ~DeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-    int status() const { return err == hipSuccess ? FE_OK : hip_fail(err, "hipSetDevice"); }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
-// f(std::integral_constant<int, NT>) for NT = H / 32 at H = 32 / 64 / 128 (the caller has refused every other H)
-template <class F>
-auto with_nt(int32_t H, F &&f) {
-    return H == 32 ? f(std::integral_constant<int, 1>{}) : (H == 64 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 4>{}));
-}
-
+// (the launch helpers of fe_env.hip this unit needs are restated once for the small units, in fe_host_common.h)
 bool weights_ok(const fe_mlpq_weights *w) { return w && w->w1t && w->wpos && w->wact && w->b1 && w->w2 && w->b2 && w->w3 && w->b3; }
 bool grads_ok(const fe_mlpq_grads *g) { return g && g->w1 && g->b1 && g->w2 && g->b2 && g->w3 && g->b3; }
 

@@ -10,9 +10,10 @@ targets with ``hidden_dims=(128, 128)``.  Its submodule names are the reference'
 ``FusedTwinMLPCritic`` is ``FusedTwinCritic``'s front end (finenvs_amd/critic.py) for two such critics: values on
 observation descriptors (C ABI ``fe_twin_mlpq_forward``, include/finenvs_amd_mlp_critic.h), ``q`` as a differentiable
 function of the actions and both critics' parameters (``fe_twin_mlpq_backward``), ``critic_loss`` on replayed
-transitions and ``td3_targets`` straight from the replay ring (``fe_twin_mlpq_target``), the target actor a
-``FusedMLP2Rollout``.  Nothing is rendered.  Scope: one asset, two hidden layers of the same width H in {32, 64, 128} and
-the same activation, a window the two-layer head admits (``MLP2_MAX_WINDOW``).
+transitions, ``td3_targets`` straight from the replay ring (``fe_twin_mlpq_target``), the target actor a
+``FusedMLP2Rollout``, and ``sac_targets`` with a ``FusedMLPSACRollout`` (finenvs_amd/mlp_sac.py) as the actor.  Nothing is
+rendered.  Scope: one asset, two hidden layers of the same width H in {32, 64, 128} and the same activation, a window the
+two-layer head admits (``MLP2_MAX_WINDOW``).
 """
 from __future__ import annotations
 
@@ -218,6 +219,12 @@ class FusedTwinMLPCritic(_FusedTwin):
         if not isinstance(target_actor, FusedMLP2Rollout) or target_actor.out_act != 0 or target_actor.env is not self.env:
             raise ValueError('target_actor must be a FusedMLP2Rollout of this env with output_activation="tanh" (e.g. '
                              "FusedMLP2Head(...).rollout)")
+
+    def _check_sac_actor(self, actor_roll) -> None:
+        from .mlp_sac import FusedMLPSACRollout
+
+        if not isinstance(actor_roll, FusedMLPSACRollout) or actor_roll.env is not self.env:
+            raise ValueError("actor_roll must be a FusedMLPSACRollout of this env (the SAC MLP actor)")
 
     def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
         """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
