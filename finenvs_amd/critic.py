@@ -139,9 +139,9 @@ def torch_grads_to_packed(g: Dict[str, torch.Tensor], H: int) -> Dict[str, torch
 
 
 class _TwinQ(torch.autograd.Function):
-    """(q1, q2) of ``FusedTwinCritic`` as a differentiable function of the actions and the twelve parameters: the
-    forward is ``fe_twin_q_forward``, the backward ``fe_twin_q_backward`` (the same activations, recomputed); at
-    H > 128 their ``_streamed`` namesakes, whose gradients arrive in torch's row order."""
+    """(q1, q2) of a ``_FusedTwin`` as a differentiable function of the actions and the twelve parameters: the forward
+    is the family's forward entry, the backward its backward entry on the weights the forward packed (the activations
+    recomputed)."""
 
     @staticmethod
     def forward(ctx, fused, src, pos, actions, *params):
@@ -159,55 +159,64 @@ class _TwinQ(torch.autograd.Function):
             fused.weights.check_version(ctx.version)
         src, pos, act = ctx.saved_tensors
         env, H, B = fused.env, fused.H, int(src.numel())
+        W, dev = int(env.num_intervals), env._dev
         need = ctx.needs_input_grad
+        n = (len(need) - 4) // 2  # parameters per critic
         need_a = need[3]
-        need_w = (any(need[4:10]), any(need[10:16]))
+        need_w = (any(need[4:4 + n]), any(need[4 + n:]))
         dq = [g if g is not None and (need_w[c] or need_a) else None for c, g in enumerate((g1, g2))]
-        out = [None] * 16
+        out = [None] * len(need)
         if dq[0] is None and dq[1] is None:
             return tuple(out)
-        dev = env._dev
         dq = [None if g is None else g.reshape(B).float().contiguous() for g in dq]
-        grads = [empty_packed_grads(H, dev) if dq[c] is not None and need_w[c] else None for c in range(2)]
+        grads = [fused._empty_grads() if dq[c] is not None and need_w[c] else None for c in range(2)]
         da = torch.empty((B,), dtype=torch.float32, device=dev) if need_a else None
-        streamed = H > 128
-        floats = env._lib.fe_twin_q_streamed_grad_workspace_floats if streamed else env._lib.fe_twin_q_grad_workspace_floats
-        ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
-        cg = [None if g is None else _lib.FeCriticGrads(*(g[k].data_ptr() for k in GRAD_KEYS)) for g in grads]
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
-        backward = env._lib.fe_twin_q_backward_streamed if streamed else env._lib.fe_twin_q_backward
         if B == 0:  # nothing to launch (an empty tensor has no address to pass): the sums over an empty batch are zeros
             for g in grads:
                 if g is not None:
-                    for t in g.values():
+                    for t in g:
                         t.zero_()
         else:
-            cw = [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
-                  for x in ctx.packed]
-            _lib.check(backward(
-                env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), H, src.data_ptr(), pos.data_ptr(),
-                act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
+            ws = torch.empty((int(fused._entry("workspace")(H, W, B)),), dtype=torch.float32, device=dev)
+            cw = [fused._struct(x) for x in ctx.packed]
+            cg = [None if g is None else fused.GRADS(*(t.data_ptr() for t in g)) for g in grads]
+            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+            ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
+            _lib.check(fused._entry("backward")(
+                env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), *fused._shape_args(), src.data_ptr(),
+                pos.data_ptr(), act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
                 env._stream()), env._lib)
         if need_a:
             out[3] = da.reshape(ctx.action_shape)
         for c in range(2):
             if grads[c] is None:
                 continue
-            t = grads[c] if streamed else packed_grads_to_torch(grads[c], H)
-            for k, key in enumerate(GRAD_KEYS):
-                if need[4 + 6 * c + k]:
-                    out[4 + 6 * c + k] = t[key]
+            for k, g in enumerate(fused._grads_to_torch(grads[c])):
+                if need[4 + n * c + k]:
+                    out[4 + n * c + k] = g
         return tuple(out)
 
 
 class _FusedTwin:
     """What ``FusedTwinCritic`` and ``FusedTwinMLPCritic`` (finenvs_amd/mlp_critic.py) share: everything that does not
-    depend on the network -- the checks of devices, vectors and indices, the ring's descriptors, the NaN rule for an index
-    outside ``[0, size)``, ``ReplayDraw`` handling, the critic loss and the target launches' argument lists.  A family
-    provides ``forward``, ``q``, ``_weights()`` (the two ctypes weight structs), ``_shape_args()`` (what its C entries
-    take between the weights and the descriptors: ``H``, or ``H`` and the activation), ``_target_entry(cursor)``,
-    ``_check_target_actor`` and ``_check_sac_actor``."""
+    depend on the network -- the checks of devices, vectors and indices, ``forward`` and ``q`` with its autograd function,
+    the ring's descriptors, the NaN rule for an index outside ``[0, size)``, ``ReplayDraw`` handling, the critic loss and
+    the target launches' argument lists.  A family provides ``_weights()`` (packs both critics into ``self._packed`` and
+    returns their two ctypes weight structs), ``_struct(x)`` (that struct of one packed critic), ``_shape_args()`` (what
+    its C entries take between the weights and the descriptors: ``H``, or ``H`` and the activation), ``ENTRIES`` or
+    ``_entry(kind)`` (the ``"forward"``, ``"backward"`` and ``"workspace"`` entries), ``_target_entry(cursor)``,
+    ``_parameters(critic)`` (one critic's parameter tuple) and ``_DTYPE_ERROR``, ``_empty_grads()`` and ``GRADS`` (one
+    critic's gradient buffers as its backward writes them, in the parameters' order, and their ctypes struct),
+    ``_grads_to_torch(grads)`` (those in torch's layout), ``_check_target_actor`` and ``_check_sac_actor``.  ``weights``
+    (a ``FusedAdam``) is the LSTM's alone."""
+
+    weights = None
+
+    def _entry(self, kind: str):
+        return getattr(self.env._lib, self.ENTRIES[kind])
+
+    def _grads_to_torch(self, grads):
+        return grads
 
     def _check_devices(self) -> None:
         dev = torch.device(self.env._dev)
@@ -220,6 +229,42 @@ class _FusedTwin:
             raise ValueError(f"{name} must be a {dtype} tensor of {B} elements ((B,) or (B, 1)) on {self.env._dev}, got "
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}")
         return t.reshape(B).contiguous()
+
+    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
+        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
+        env = self.env
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        act = self._vector(actions, B, "actions")
+        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
+        if B:
+            c1, c2 = self._weights()
+            _lib.check(self._entry("forward")(
+                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), *self._shape_args(), src.data_ptr(),
+                pos.data_ptr(), act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
+        return q1, q2
+
+    __call__ = forward
+
+    # ---------------------------------------------------------------- the gradient half
+    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
+        """``forward`` as a differentiable function (C ABI ``fe_twin_q_backward``, include/finenvs_amd_critic_grad.h;
+        the MLP critics': ``fe_twin_mlpq_backward``): ``(q1, q2)`` (B, 1) float32, the same values bit for bit.
+        ``backward()`` accumulates into the ``.grad`` of both critics' parameters and of ``actions`` (float32, (B, 1) or
+        (B,)) as the torch modules would: the critic loss of SAC/critic.py:30-45 / TD3/critic.py:31-46, ``dQ/da`` for
+        TD3/actor.py ``compute_loss`` and the SAC actor loss.  A critic whose output gets no gradient does not run; one
+        whose parameters are frozen has no weight reduction."""
+        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
+        src = self._vector(obs_src, B, "obs_src", torch.int64)
+        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
+        self._vector(actions, B, "actions")
+        params = self._parameters(self.critic_1) + self._parameters(self.critic_2)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError(self._DTYPE_ERROR)
+        return _TwinQ.apply(self, src, pos, actions, *params)
 
     def critic_loss(self, buffer, indices: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """``MSE(q1, y) + MSE(q2, y)`` of both critics (SAC/critic.py:30-45 compute_loss, once per critic) on the
@@ -371,6 +416,10 @@ class FusedTwinCritic(_FusedTwin):
         self._lr32 = log_return_f32(env)
         self.last: Dict[str, torch.Tensor] = {}
 
+    GRADS = _lib.FeCriticGrads
+    _parameters = staticmethod(critic_parameters)
+    _DTYPE_ERROR = "the fused critic's gradient needs float32 parameters"
+
     def _weights(self):
         self._check_devices()
         if self.weights is not None:
@@ -378,8 +427,26 @@ class FusedTwinCritic(_FusedTwin):
         else:
             w = [pack_critic_weights(c) for c in (self.critic_1, self.critic_2)]
         self._packed = w  # kept alive until the launch has been queued
-        return [_lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
-                for x in w]
+        return [self._struct(x) for x in w]
+
+    @staticmethod
+    def _struct(x) -> "_lib.FeCriticWeights":
+        return _lib.FeCriticWeights(x["whh"].data_ptr(), x["wx"].data_ptr(), x["wout"].data_ptr(), x["bout"].data_ptr())
+
+    def _entry(self, kind: str):
+        lib = self.env._lib
+        if kind == "workspace":
+            return lib.fe_twin_q_streamed_grad_workspace_floats if self.streamed else lib.fe_twin_q_grad_workspace_floats
+        return getattr(lib, f"fe_twin_q_{kind}" + ("_streamed" if self.streamed else ""))
+
+    def _empty_grads(self):
+        return list(empty_packed_grads(self.H, self.env._dev).values())
+
+    def _grads_to_torch(self, grads):
+        """fe_twin_q_backward_streamed writes torch's row order and layout; the resident kernel the packed one."""
+        if self.streamed:
+            return grads
+        return list(packed_grads_to_torch(dict(zip(GRAD_KEYS, grads)), self.H).values())
 
     def _shape_args(self):
         return (self.H,)
@@ -401,44 +468,6 @@ class FusedTwinCritic(_FusedTwin):
 
         if not isinstance(actor_roll, FusedSACRollout):
             raise ValueError("actor_roll must be a FusedSACRollout (the SAC actor's head)")
-
-    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
-        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
-        env = self.env
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        act = self._vector(actions, B, "actions")
-        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        if B:
-            c1, c2 = self._weights()
-            entry = env._lib.fe_twin_q_forward_streamed if self.streamed else env._lib.fe_twin_q_forward
-            _lib.check(entry(
-                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, src.data_ptr(), pos.data_ptr(),
-                act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
-        return q1, q2
-
-    __call__ = forward
-
-    # ---------------------------------------------------------------- the gradient half
-    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """``forward`` as a differentiable function (C ABI ``fe_twin_q_backward``, include/finenvs_amd_critic_grad.h):
-        ``(q1, q2)`` (B, 1) float32, the same values bit for bit.  ``backward()`` accumulates into the ``.grad`` of both
-        critics' parameters and of ``actions`` (float32, (B, 1) or (B,)) as the torch modules would: the critic loss of
-        SAC/critic.py:30-45 / TD3/critic.py:31-46, ``dQ/da`` for TD3/actor.py ``compute_loss`` and the SAC actor loss.
-        A critic whose output gets no gradient does not run; one whose parameters are frozen has no weight
-        reduction."""
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        self._vector(actions, B, "actions")
-        params = critic_parameters(self.critic_1) + critic_parameters(self.critic_2)
-        if any(p.dtype is not torch.float32 for p in params):
-            raise ValueError("the fused critic's gradient needs float32 parameters")
-        q1, q2 = _TwinQ.apply(self, src, pos, actions, *params)
-        return q1, q2
 
 
 # ---------------------------------------------------------------- the torch restatements (host or device)

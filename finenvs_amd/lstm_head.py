@@ -98,55 +98,83 @@ def head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
 
 
 class _HeadValue(torch.autograd.Function):
-    """``FusedLSTMRollout.forward`` as a differentiable function of the head's six parameters: the forward is
-    ``fe_lstm_forward``, the backward ``fe_lstm_backward`` (the same activations, recomputed)."""
+    """``head.rollout.forward`` as a differentiable function of the head's parameters: the forward is the rollout's
+    forward entry, the backward the head's ``_backward`` launch (the same activations, recomputed)."""
 
     @staticmethod
     def forward(ctx, head, src, pos, *params):
         roll = head.rollout
         out = roll.forward(src, pos)
         ctx.set_materialize_grads(False)
-        # the packed weights forward() ran with: backward packs nothing again and makes no copy to the host
-        ctx.head, ctx.packed = head, (roll.whh, roll.wx, roll.wout)
+        # the weight buffers forward() ran with: backward packs nothing again and makes no copy to the host
+        ctx.head, ctx.packed = head, tuple(getattr(roll, name) for name in head.PACKED)
         ctx.version = None if head.weights is None else head.weights.version
         ctx.save_for_backward(src, pos, out)
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        out = [None] * 9
-        if g_out is None or not any(ctx.needs_input_grad[3:]):
+        head, need = ctx.head, ctx.needs_input_grad
+        out = [None] * len(need)
+        if g_out is None or not any(need[3:]):
             return tuple(out)
-        head = ctx.head
         src, pos, values = ctx.saved_tensors
         env, H, B = head.env, head.H, int(src.numel())
-        dev = env._dev
-        shapes = {"w_ih": (4 * H, 5), "w_hh": (4 * H, H), "b_ih": (4 * H,), "b_hh": (4 * H,), "w_out": (1, H), "b_out": (1,)}
-        grads = [torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in LSTM_GRAD_KEYS]
+        W, dev = int(env.num_intervals), env._dev
+        grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in head.grad_shapes(H, W)]
         if B:
             g_out = g_out.reshape(B).float().contiguous()
-            streamed = H > 128
-            floats = env._lib.fe_lstm_streamed_grad_workspace_floats if streamed else env._lib.fe_lstm_grad_workspace_floats
-            ws = torch.empty((int(floats(H, int(env.num_intervals), B)),), dtype=torch.float32, device=dev)
-            whh, wx, wout = ctx.packed
+            ws = torch.empty((int(getattr(env._lib, head.WORKSPACE)(H, W, B)),), dtype=torch.float32, device=dev)
             if head.weights is not None:
                 head.weights.check_version(ctx.version)
-            lg = _lib.FeLstmGrads(*(g.data_ptr() for g in grads))
-            backward = env._lib.fe_lstm_backward_streamed if streamed else env._lib.fe_lstm_backward
-            _lib.check(backward(
-                env._handle, head.rollout._lr32.data_ptr(), whh.data_ptr(), wx.data_ptr(), wout.data_ptr(), H,
-                head.rollout.out_act, src.data_ptr(), pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(),
-                ws.data_ptr(), C.byref(lg), env._stream()), env._lib)
+            sg = head.GRADS(*(g.data_ptr() for g in grads))
+            head._backward(ctx.packed, src, pos, B, values, g_out, ws, sg)
         else:
             for g in grads:
                 g.zero_()
-        for k in range(6):
-            if ctx.needs_input_grad[3 + k]:
-                out[3 + k] = grads[k]
+        for k, g in enumerate(grads):
+            if need[3 + k]:
+                out[3 + k] = g
         return tuple(out)
 
 
-class FusedLSTMHead:
+class _FusedHead:
+    """What ``FusedLSTMHead``, ``FusedMLPHead`` and ``FusedMLP2Head`` (finenvs_amd/mlp_head.py, mlp2_head.py) share: the
+    checks of the descriptors and of the module's parameters, and the call with its autograd function.  A family
+    provides ``env``, ``module``, ``H`` and ``rollout``; ``_parameters`` (of the module) with ``_DTYPE_ERROR``;
+    ``refresh``; ``PACKED`` (the rollout's attributes a forward ran with, which its backward reads); ``grad_shapes(H, W)``
+    and ``GRADS`` (the gradients in the parameters' order, and their ctypes struct); ``WORKSPACE`` (the sizing entry) and
+    ``_backward(packed, src, pos, B, values, g_out, ws, grads)`` (the backward launch: its argument list is the
+    family's).  ``weights`` (a ``FusedAdam``) is the LSTM's alone."""
+
+    weights = None
+
+    def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
+        params = self._parameters(self.module)
+        if any(p.dtype is not torch.float32 for p in params):
+            raise ValueError(self._DTYPE_ERROR)
+        if any(p.device != torch.device(self.env._dev) for p in params):
+            raise ValueError(f"the head's parameters must live on the env's device {self.env._dev}")
+        return params
+
+    def __call__(self, obs_src: torch.Tensor, obs_pos: torch.Tensor) -> torch.Tensor:
+        """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B,)`` or ``(B, 1)`` float64):
+        (B, 1) float32, ``self.rollout.forward``'s values bit for bit."""
+        env = self.env
+        if not isinstance(obs_src, torch.Tensor) or not isinstance(obs_pos, torch.Tensor):
+            raise ValueError("obs_src / obs_pos must be tensors of observation descriptors")
+        B = int(obs_src.numel())
+        if obs_pos.numel() != B:
+            raise ValueError(f"obs_pos must hold one position per descriptor ({B}), got {tuple(obs_pos.shape)}")
+        params = self._check_parameters()
+        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
+        pos = obs_pos.reshape(B, 1).to(device=env._dev, dtype=torch.float64).contiguous()
+        if B:  # an empty batch packs nothing and launches nothing, in either direction
+            self.refresh()
+        return _HeadValue.apply(self, src, pos, *params)
+
+
+class FusedLSTMHead(_FusedHead):
     """An ``LSTMHead`` (or the reference's network of that shape) trained on observation descriptors.
 
     ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_lstm_forward`` --
@@ -170,12 +198,18 @@ class FusedLSTMHead:
     version check for the same mistake); and ``self.rollout.set_weights(...)`` takes the rollout off the optimizer's
     buffers, output bias included, until a new head is built."""
 
+    GRADS, PACKED = _lib.FeLstmGrads, ("whh", "wx", "wout")
+    _parameters = staticmethod(head_parameters)
+    _DTYPE_ERROR = "the fused LSTM head's gradient needs float32 parameters"
+
     def __init__(self, env, module: nn.Module, streamed: bool = False, weights=None):
         self.H, self.output_activation = check_head(module, streamed)
         if int(env.num_assets) != 1:
             raise ValueError(f"the fused LSTM head trains one asset (the env has {env.num_assets}), as the fused twin "
                              "critic does")
         self.env, self.module = env, module
+        # which entries run: a function of H alone
+        self.WORKSPACE = "fe_lstm_streamed_grad_workspace_floats" if self.H > 128 else "fe_lstm_grad_workspace_floats"
         self._check_parameters()
         self.weights = weights
         packed = weights.packed(module) if weights is not None else None  # ValueError if the module is not registered
@@ -184,13 +218,9 @@ class FusedLSTMHead:
             roll = self.rollout
             roll.whh, roll.wx, roll.wout, roll.bout_dev = packed["whh"], packed["wx"], packed["wout"], packed["bout"]
 
-    def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
-        params = head_parameters(self.module)
-        if any(p.dtype is not torch.float32 for p in params):
-            raise ValueError("the fused LSTM head's gradient needs float32 parameters")
-        if any(p.device != torch.device(self.env._dev) for p in params):
-            raise ValueError(f"the head's parameters must live on the env's device {self.env._dev}")
-        return params
+    @staticmethod
+    def grad_shapes(H: int, W: int):
+        return (4 * H, 5), (4 * H, H), (4 * H,), (4 * H,), (1, H), (1,)
 
     def refresh(self) -> None:
         """The module's current parameters into ``self.rollout``, packed on the device (``lstm_pack``).  One 4-byte copy
@@ -206,21 +236,14 @@ class FusedLSTMHead:
         roll.wout = w_out.detach().reshape(self.H).clone()
         roll.bout = float(b_out.detach())
 
-    def __call__(self, obs_src: torch.Tensor, obs_pos: torch.Tensor) -> torch.Tensor:
-        """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B,)`` or ``(B, 1)`` float64):
-        (B, 1) float32, ``self.rollout.forward``'s values bit for bit."""
-        env = self.env
-        if not isinstance(obs_src, torch.Tensor) or not isinstance(obs_pos, torch.Tensor):
-            raise ValueError("obs_src / obs_pos must be tensors of observation descriptors")
-        B = int(obs_src.numel())
-        if obs_pos.numel() != B:
-            raise ValueError(f"obs_pos must hold one position per descriptor ({B}), got {tuple(obs_pos.shape)}")
-        params = self._check_parameters()
-        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
-        pos = obs_pos.reshape(B, 1).to(device=env._dev, dtype=torch.float64).contiguous()
-        if B:  # an empty batch packs nothing and launches nothing, in either direction
-            self.refresh()
-        return _HeadValue.apply(self, src, pos, *params)
+    def _backward(self, packed, src, pos, B, values, g_out, ws, grads) -> None:
+        env, roll = self.env, self.rollout
+        whh, wx, wout = packed
+        backward = env._lib.fe_lstm_backward_streamed if self.H > 128 else env._lib.fe_lstm_backward
+        _lib.check(backward(
+            env._handle, roll._lr32.data_ptr(), whh.data_ptr(), wx.data_ptr(), wout.data_ptr(), self.H, roll.out_act,
+            src.data_ptr(), pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(), ws.data_ptr(), C.byref(grads),
+            env._stream()), env._lib)
 
 
 # ---------------------------------------------------------------- the reference's losses, plain torch on the output

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .mlp_head import _FusedHead, _MLPModule, check_head
+from .mlp_head import _FusedMLPDepth, _MLPModule, check_head
 from .rollout import FusedMLP2Rollout
 
 MLP2_GRAD_KEYS = ("w1", "b1", "w2", "b2", "w3", "b3")  # fe_mlp2_grads' fields, in mlp2_head_parameters' order
@@ -52,7 +52,7 @@ def mlp2_head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
     return net[0].weight, net[0].bias, net[2].weight, net[2].bias, net[4].weight, net[4].bias
 
 
-class FusedMLP2Head(_FusedHead):
+class FusedMLP2Head(_FusedMLPDepth):
     """An ``MLP2Head`` (or the reference's network of that shape) trained on observation descriptors.
 
     ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_mlp2_forward`` --

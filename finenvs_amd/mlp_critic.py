@@ -17,7 +17,6 @@ two-layer head admits (``MLP2_MAX_WINDOW``).
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Tuple
 
 import torch
@@ -117,61 +116,6 @@ def mlpq_grad_shapes(H: int, W: int):
     return (H, 5 * W + 1), (H,), (H, H), (H,), (1, H), (1,)
 
 
-class _TwinMLPQ(torch.autograd.Function):
-    """(q1, q2) of ``FusedTwinMLPCritic`` as a differentiable function of the actions and the twelve parameters: the
-    forward is ``fe_twin_mlpq_forward``, the backward ``fe_twin_mlpq_backward`` (the hidden layers recomputed)."""
-
-    @staticmethod
-    def forward(ctx, fused, src, pos, actions, *params):
-        q1, q2 = fused.forward(src, pos, actions.detach())
-        ctx.set_materialize_grads(False)  # an output nobody used gets None, not zeros: its critic does not run
-        ctx.fused, ctx.packed, ctx.action_shape = fused, getattr(fused, "_packed", None), actions.shape  # (none yet: B = 0)
-        ctx.save_for_backward(src, pos, actions.detach().reshape(-1).contiguous())
-        return q1, q2
-
-    @staticmethod
-    def backward(ctx, g1, g2):
-        fused = ctx.fused
-        src, pos, act = ctx.saved_tensors
-        env, H, B = fused.env, fused.H, int(src.numel())
-        W, dev = int(env.num_intervals), env._dev
-        need = ctx.needs_input_grad
-        need_a = need[3]
-        need_w = (any(need[4:10]), any(need[10:16]))
-        dq = [g if g is not None and (need_w[c] or need_a) else None for c, g in enumerate((g1, g2))]
-        out = [None] * 16
-        if dq[0] is None and dq[1] is None:
-            return tuple(out)
-        dq = [None if g is None else g.reshape(B).float().contiguous() for g in dq]
-        grads = [[torch.empty(shape, dtype=torch.float32, device=dev) for shape in mlpq_grad_shapes(H, W)]
-                 if dq[c] is not None and need_w[c] else None for c in range(2)]
-        da = torch.empty((B,), dtype=torch.float32, device=dev) if need_a else None
-        if B == 0:  # nothing to launch (an empty tensor has no address to pass): the sums over an empty batch are zeros
-            for g in grads:
-                if g is not None:
-                    for t in g:
-                        t.zero_()
-        else:
-            ws = torch.empty((int(env._lib.fe_twin_mlpq_grad_workspace_floats(H, W, B)),), dtype=torch.float32, device=dev)
-            cw = [_weights_struct(x) for x in ctx.packed]
-            cg = [None if g is None else _lib.FeMlpqGrads(*(t.data_ptr() for t in g)) for g in grads]
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
-            _lib.check(env._lib.fe_twin_mlpq_backward(
-                env._handle, fused._lr32.data_ptr(), C.byref(cw[0]), C.byref(cw[1]), H, fused.act, src.data_ptr(),
-                pos.data_ptr(), act.data_ptr(), B, ptr(dq[0]), ptr(dq[1]), ws.data_ptr(), ref(cg[0]), ref(cg[1]), ptr(da),
-                env._stream()), env._lib)
-        if need_a:
-            out[3] = da.reshape(ctx.action_shape)
-        for c in range(2):
-            if grads[c] is None:
-                continue
-            for k, g in enumerate(grads[c]):
-                if need[4 + 6 * c + k]:
-                    out[4 + 6 * c + k] = g
-        return tuple(out)
-
-
 class FusedTwinMLPCritic(_FusedTwin):
     """Two MLP critics of the same H and activation evaluated together on the device (C ABI of
     include/finenvs_amd_mlp_critic.h): ``FusedTwinCritic``'s front end -- ``forward`` / ``__call__``, ``q``,
@@ -204,10 +148,20 @@ class FusedTwinMLPCritic(_FusedTwin):
         self._lr32 = log_return_f32(env)
         self.last: Dict[str, torch.Tensor] = {}
 
+    ENTRIES = {"forward": "fe_twin_mlpq_forward", "backward": "fe_twin_mlpq_backward",
+               "workspace": "fe_twin_mlpq_grad_workspace_floats"}
+    GRADS = _lib.FeMlpqGrads
+    _parameters, _struct = staticmethod(mlp_critic_parameters), staticmethod(_weights_struct)
+    _DTYPE_ERROR = "the fused MLP critic's gradient needs float32 parameters"
+
     def _weights(self):
         self._check_devices()
         self._packed = [pack_mlp_critic_weights(self.env, c) for c in (self.critic_1, self.critic_2)]  # alive until queued
         return [_weights_struct(x) for x in self._packed]
+
+    def _empty_grads(self):
+        shapes = mlpq_grad_shapes(self.H, int(self.env.num_intervals))
+        return [torch.empty(shape, dtype=torch.float32, device=self.env._dev) for shape in shapes]
 
     def _shape_args(self):
         return (self.H, self.act)
@@ -225,40 +179,6 @@ class FusedTwinMLPCritic(_FusedTwin):
 
         if not isinstance(actor_roll, FusedMLPSACRollout) or actor_roll.env is not self.env:
             raise ValueError("actor_roll must be a FusedMLPSACRollout of this env (the SAC MLP actor)")
-
-    def forward(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """Both critics on B (state, action) pairs: ``obs_src (B,)`` int64 / ``obs_pos (B, 1)`` float64 observation
-        descriptors and ``actions (B, 1)`` float32 -> ``(q1, q2)``, each (B, 1) float32."""
-        env = self.env
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        act = self._vector(actions, B, "actions")
-        q1 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        q2 = torch.empty((B, 1), dtype=torch.float32, device=env._dev)
-        if B:
-            c1, c2 = self._weights()
-            _lib.check(env._lib.fe_twin_mlpq_forward(
-                env._handle, self._lr32.data_ptr(), C.byref(c1), C.byref(c2), self.H, self.act, src.data_ptr(),
-                pos.data_ptr(), act.data_ptr(), B, q1.data_ptr(), q2.data_ptr(), env._stream()), env._lib)
-        return q1, q2
-
-    __call__ = forward
-
-    def q(self, obs_src: torch.Tensor, obs_pos: torch.Tensor, actions: torch.Tensor):
-        """``forward`` as a differentiable function (C ABI ``fe_twin_mlpq_backward``): ``(q1, q2)`` (B, 1) float32, the
-        same values bit for bit.  ``backward()`` accumulates into the ``.grad`` of both critics' parameters and of
-        ``actions`` (float32, (B, 1) or (B,)) as the torch modules would: the critic loss of TD3/critic.py:31-46,
-        ``dQ/da`` for TD3/actor.py ``compute_loss`` and a SAC actor loss.  A critic whose output gets no gradient does not
-        run; one whose parameters are frozen has no weight reduction."""
-        B = int(obs_src.numel()) if isinstance(obs_src, torch.Tensor) else -1
-        src = self._vector(obs_src, B, "obs_src", torch.int64)
-        pos = self._vector(obs_pos, B, "obs_pos", torch.float64)
-        self._vector(actions, B, "actions")
-        params = mlp_critic_parameters(self.critic_1) + mlp_critic_parameters(self.critic_2)
-        if any(p.dtype is not torch.float32 for p in params):
-            raise ValueError("the fused MLP critic's gradient needs float32 parameters")
-        return _TwinMLPQ.apply(self, src, pos, actions, *params)
 
 
 # ---------------------------------------------------------------- the torch restatements (host or device)

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .lstm_head import _FusedHead
 from .rollout import FusedMLPRollout
 
 MLP_HEAD_HIDDEN_SIZES = FusedMLPRollout.HIDDEN_SIZES
@@ -122,53 +123,14 @@ def mlp_head_parameters(module: nn.Module) -> Tuple[torch.Tensor, ...]:
     return first.weight, first.bias, last.weight, last.bias
 
 
-class _MLPHeadValue(torch.autograd.Function):
-    """``head.rollout.forward`` as a differentiable function of the head's parameters: the forward is ``fe_mlp_forward``
-    or ``fe_mlp2_forward``, the backward the head's ``BACKWARD`` entry (the hidden layers recomputed)."""
-
-    @staticmethod
-    def forward(ctx, head, src, pos, *params):
-        roll = head.rollout
-        out = roll.forward(src, pos)
-        ctx.set_materialize_grads(False)
-        # the weight buffers forward() ran with: backward packs nothing again and makes no copy to the host
-        ctx.head, ctx.packed = head, tuple(getattr(roll, name) for name in head.PACKED)
-        ctx.save_for_backward(src, pos, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, g_out):
-        head = ctx.head
-        out = [None] * (3 + len(head.GRAD_KEYS))
-        if g_out is None or not any(ctx.needs_input_grad[3:]):
-            return tuple(out)
-        src, pos, values = ctx.saved_tensors
-        env, H, B = head.env, head.H, int(src.numel())
-        W, dev = int(env.num_intervals), env._dev
-        grads = [torch.empty(shape, dtype=torch.float32, device=dev) for shape in head.grad_shapes(H, W)]
-        if B:
-            g_out = g_out.reshape(B).float().contiguous()
-            ws = torch.empty((int(getattr(env._lib, head.WORKSPACE)(H, W, B)),), dtype=torch.float32, device=dev)
-            weights = head.WEIGHTS(*(t.data_ptr() for t in ctx.packed))
-            mg = head.GRADS(*(g.data_ptr() for g in grads))
-            roll = head.rollout
-            _lib.check(getattr(env._lib, head.BACKWARD)(
-                env._handle, roll._lr32.data_ptr(), C.byref(weights), H, roll.act, roll.out_act, src.data_ptr(),
-                pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(), ws.data_ptr(), C.byref(mg), env._stream()), env._lib)
-        else:
-            for g in grads:
-                g.zero_()
-        for k, g in enumerate(grads):
-            if ctx.needs_input_grad[3 + k]:
-                out[3 + k] = g
-        return tuple(out)
-
-
-class _FusedHead:
-    """What ``FusedMLPHead`` and ``FusedMLP2Head`` share.  A depth names: ``GRAD_KEYS`` and ``grad_shapes(H, W)`` (the
+class _FusedMLPDepth(_FusedHead):
+    """What ``FusedMLPHead`` and ``FusedMLP2Head`` share on top of ``_FusedHead`` (finenvs_amd/lstm_head.py): the
+    constructor, ``refresh`` and the backward launch.  A depth names: ``GRAD_KEYS`` and ``grad_shapes(H, W)`` (the
     gradients, in its parameters' order), ``WEIGHTS`` / ``GRADS`` (the ctypes structs), ``WORKSPACE`` / ``BACKWARD`` (the C
     entries), ``PACKED`` (the rollout's attributes that fill ``WEIGHTS``: ``w1t``, ``wpos``, then one per parameter after
     the first), ``_check`` / ``_parameters`` (of the module) and ``_make_rollout``."""
+
+    _DTYPE_ERROR = "the fused MLP head's gradient needs float32 parameters"
 
     def __init__(self, env, module: nn.Module):
         self.H, W, self.activation, self.output_activation = self._check(module)
@@ -179,14 +141,6 @@ class _FusedHead:
         self.env, self.module = env, module
         self.rollout = self._make_rollout(self._check_parameters())
         self.refresh()
-
-    def _check_parameters(self) -> Tuple[torch.Tensor, ...]:
-        params = self._parameters(self.module)
-        if any(p.dtype is not torch.float32 for p in params):
-            raise ValueError("the fused MLP head's gradient needs float32 parameters")
-        if any(p.device != torch.device(self.env._dev) for p in params):
-            raise ValueError(f"the head's parameters must live on the env's device {self.env._dev}")
-        return params
 
     def refresh(self) -> None:
         """The module's current parameters into ``self.rollout``, on the device into fresh buffers (``fe_mlp_pack`` for
@@ -203,24 +157,15 @@ class _FusedHead:
         for name, p in zip(self.PACKED[2:], params[1:]):  # a (1, H) output weight is kept as (H)
             setattr(roll, name, p.detach().reshape(p.shape[-1:] if p.shape[0] == 1 else p.shape).clone())
 
-    def __call__(self, obs_src: torch.Tensor, obs_pos: torch.Tensor) -> torch.Tensor:
-        """The head on B observation descriptors (``obs_src (B,)`` int64, ``obs_pos (B,)`` or ``(B, 1)`` float64):
-        (B, 1) float32, ``self.rollout.forward``'s values bit for bit."""
-        env = self.env
-        if not isinstance(obs_src, torch.Tensor) or not isinstance(obs_pos, torch.Tensor):
-            raise ValueError("obs_src / obs_pos must be tensors of observation descriptors")
-        B = int(obs_src.numel())
-        if obs_pos.numel() != B:
-            raise ValueError(f"obs_pos must hold one position per descriptor ({B}), got {tuple(obs_pos.shape)}")
-        params = self._check_parameters()
-        src = obs_src.reshape(B).to(device=env._dev, dtype=torch.int64).contiguous()
-        pos = obs_pos.reshape(B, 1).to(device=env._dev, dtype=torch.float64).contiguous()
-        if B:  # an empty batch packs nothing and launches nothing, in either direction
-            self.refresh()
-        return _MLPHeadValue.apply(self, src, pos, *params)
+    def _backward(self, packed, src, pos, B, values, g_out, ws, grads) -> None:
+        env, roll = self.env, self.rollout
+        weights = self.WEIGHTS(*(t.data_ptr() for t in packed))
+        _lib.check(getattr(env._lib, self.BACKWARD)(
+            env._handle, roll._lr32.data_ptr(), C.byref(weights), self.H, roll.act, roll.out_act, src.data_ptr(),
+            pos.data_ptr(), B, values.data_ptr(), g_out.data_ptr(), ws.data_ptr(), C.byref(grads), env._stream()), env._lib)
 
 
-class FusedMLPHead(_FusedHead):
+class FusedMLPHead(_FusedMLPDepth):
     """An ``MLPHead`` (or the reference's network of that shape) trained on observation descriptors.
 
     ``head(obs_src, obs_pos)`` is ``module(env.render(obs_src, obs_pos).float())`` computed by ``fe_mlp_forward`` --

@@ -299,3 +299,28 @@ def test_example_runs_to_finite_losses():
 
     history = sac_time_series.main(num_envs=256, iterations=6, chunk=4, batch=128, quiet=True)
     assert history and all(np.isfinite([h["critic_loss"], h["actor_loss"], h["alpha_loss"]]).all() for h in history)
+
+
+def test_evaluate_returns_equals_chunked_runs_that_record_actions(fe, fo):
+    """``FusedSACRollout.evaluate_returns`` (the reference's evaluation loop, as ``FusedLSTMRollout.evaluate_returns``)
+    steps with ``run(chunk, record_actions=False)``: the null ``actions_out`` of ``fe_env_rollout_sac``.  Its per-env
+    episode returns equal, bit for bit, those of a second identical env stepped with ``run(16)`` chunks that record
+    their actions until every env has finished."""
+    from finenvs_amd.sac import FusedSACRollout
+
+    N, A, W, H = 8, 1, 4, 32
+    actor = _actor(H, W, seed=7)
+    _, env = _make(fe, fo, N, A, W, 6, 40, 0.1, True, seed=5)
+    got = FusedSACRollout(env, actor).evaluate_returns(chunk=16)
+    assert got.shape == (N,) and bool(torch.isfinite(got).all())
+    _, twin_env = _make(fe, fo, N, A, W, 6, 40, 0.1, True, seed=5)
+    roll = FusedSACRollout(twin_env, actor)
+    for _ in range(64):
+        actions, _, _ = roll.run(16)
+        assert actions.shape == (16, N, A)
+        if int(twin_env._counters[0].item()) == N:
+            break
+    else:
+        raise AssertionError("episodes did not all terminate")
+    assert_bits(t2n(got), t2n(twin_env.episode_returns), "episode returns")
+    assert bool((got != 0).any())  # the envs traded
