@@ -106,6 +106,13 @@ EVO_SIGNATURES = {
     "fe_evo_noise": (C.c_int, [C.c_uint64, C.c_uint32, _vp, _i64, _i64, _vp, _vp]),
 }
 
+# include/finenvs_amd_evo2.h: the same population with two hidden layers (FeEvoPopulation again)
+EVO2_SIGNATURES = {
+    "fe_evo2_rollout": EVO_SIGNATURES["fe_evo_rollout"],
+    "fe_evo2_num_params": (_i64, [_i32, _i32]),
+    "fe_evo2_lds_bytes": (_i64, [_i32, _i32, _i32]),
+}
+
 
 # include/finenvs_amd_replay.h: the off-policy replay ring (finenvs_amd/replay.py; same library)
 class FeReplayRing(C.Structure):
@@ -417,7 +424,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
                          **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES,
-                         **MLP_CRITIC_SIGNATURES, **MLP_SAC_SIGNATURES}.items():
+                         **MLP_CRITIC_SIGNATURES, **MLP_SAC_SIGNATURES, **EVO2_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

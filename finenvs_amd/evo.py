@@ -2,8 +2,9 @@
 finenvs/agents/networks/parallel_mlp.py) with the per-env networks never materialised.
 
 ``FusedPopulationMLPRollout`` runs K env steps of the whole population per launch (C ABI ``fe_evo_rollout``,
-include/finenvs_amd_evo.h): every training env acts with ``theta + s * sigma * z`` of its mirrored pair, the noise ``z``
-generated inside the kernel; finished episodes land in per-env slots on the device, so ``agent.store``'s per-step
+include/finenvs_amd_evo.h; ``FusedPopulationMLP2Rollout`` is the same with the reference's default two hidden layers,
+``fe_evo2_rollout``, include/finenvs_amd_evo2.h): every training env acts with ``theta + s * sigma * z`` of its mirrored
+pair, the noise ``z`` generated inside the kernel; finished episodes land in per-env slots on the device, so ``agent.store``'s per-step
 ``nonzero()`` / ``.item()`` host syncs are gone.  ``FusedEvoAgent`` is the EvoAgent loop on top of it.  The rank transform,
 fitness, gradient and Adam step are small torch functions below (pinned against the reference by
 tests/test_evo_host.py)."""
@@ -64,11 +65,15 @@ def adam_step(theta: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch
     return theta + alpha_t * torch.div(m, torch.sqrt(v) + 10 ** -8), m, v
 
 
-def init_parameters(num_observations: int, hidden_dim: int, generator: torch.Generator) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
-    """ParallelMLP's initialisation (parallel_mlp.py:45-65) for (5W, H, 1): every layer's weight (in, out) and bias (1, out)
-    ~ N(0, sqrt(2 / in)), drawn in the order W1, b1, W2, b2."""
+def init_parameters(num_observations: int, hidden_dim: int, generator: torch.Generator,
+                    hidden_layers: int = 1) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """ParallelMLP's initialisation (parallel_mlp.py:45-65) for (5W, H, 1), or (5W, H, H, 1) with ``hidden_layers=2``: every
+    layer's weight (in, out) and bias (1, out) ~ N(0, sqrt(2 / in)), drawn in the order W1, b1, W2, b2[, W3, b3]."""
+    if hidden_layers not in (1, 2):
+        raise ValueError("hidden_layers must be 1 or 2")
+    dims = (num_observations,) + (hidden_dim,) * hidden_layers + (1,)
     weights, biases = [], []
-    for fan_in, fan_out in ((num_observations, hidden_dim), (hidden_dim, 1)):
+    for fan_in, fan_out in zip(dims[:-1], dims[1:]):
         std = float(np.sqrt(2 / fan_in))
         weights.append(torch.normal(0.0, std, (fan_in, fan_out), generator=generator))
         biases.append(torch.normal(0.0, std, (1, fan_out), generator=generator))
@@ -83,6 +88,14 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
     Needs a training-mode env with ``redraw="device"``."""
 
     HIDDEN = (32, 64)
+    _ENTRY = "fe_evo_rollout"  # the C ABI's rollout of this network shape
+
+    @staticmethod
+    def _count_params(num_observations: int, H: int) -> int:
+        return num_observations * H + 2 * H + 1
+
+    def _hidden_message(self) -> str:
+        return f"hidden_dim must be one of {self.HIDDEN} (two hidden layers are out of scope)"
 
     def __init__(self, env, num_eval_envs: int, hidden_dim: int, noise_std_dev: float, seed: int,
                  action_noise_std: float = 0.01, max_episodes: int = 8):
@@ -94,7 +107,7 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
         if env.redraw != "device":
             raise ValueError('the ES population needs redraw="device": no host in the loop')
         if int(hidden_dim) not in self.HIDDEN:
-            raise ValueError(f"hidden_dim must be one of {self.HIDDEN} (two hidden layers are out of scope)")
+            raise ValueError(self._hidden_message())
         N = env.num_envs
         n_train = N - int(num_eval_envs)
         if num_eval_envs < 0 or n_train <= 0 or n_train % 2:
@@ -107,7 +120,7 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
         self.max_episodes = int(max_episodes)
         W, A, dev = env.num_intervals, env.num_assets, env._dev
         self.num_observations = 5 * W
-        self.num_params = 5 * W * self.H + 2 * self.H + 1
+        self.num_params = self._count_params(5 * W, self.H)
         self.obs_src = torch.empty((N,), dtype=torch.int64, device=dev)
         self.obs_pos = torch.empty((N, A), dtype=torch.float64, device=dev)
         self._lr32 = log_return_f32(env)
@@ -175,8 +188,8 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
                         ("scratch_rewards", self._scratch_rew), ("scratch_dones", self._scratch_done)):
             setattr(pop, name, t.data_ptr())
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        _lib.check(env._lib.fe_evo_rollout(env._handle, C.byref(pop), K, ptr(actions), ptr(means), ptr(rewards), ptr(dones),
-                                           env._stream()))
+        _lib.check(getattr(env._lib, self._ENTRY)(env._handle, C.byref(pop), K, ptr(actions), ptr(means), ptr(rewards),
+                                                  ptr(dones), env._stream()))
         self._end_run()
         self.step += K
         self.means = means
@@ -240,22 +253,101 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
         return out
 
 
+def evo2_layout(num_observations: int, H: int) -> Dict[str, Tuple[int, Tuple[int, int]]]:
+    """The flat layout of the two-hidden-layer theta (include/finenvs_amd_evo2.h): name -> (offset, ParallelMLP shape), in the
+    reference's layer order.  Every offset is a multiple of 4 (H is), so the noise stream's definition carries over."""
+    O = int(num_observations)
+    out, off = {}, 0
+    for name, shape in (("W1", (O, H)), ("b1", (1, H)), ("W2", (H, H)), ("b2", (1, H)), ("W3", (H, 1)), ("b3", (1, 1))):
+        out[name] = (off, shape)
+        off += shape[0] * shape[1]
+    return out
+
+
+def evo2_flatten(weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor], num_observations: int,
+                 H: int) -> torch.Tensor:
+    """ParallelMLP's lists of three weight and three bias layers as one f32 theta in ``evo2_layout``'s order; refuses wrong
+    shapes and non-finite entries."""
+    if len(weight_layers) != 3 or len(bias_layers) != 3:
+        raise ValueError("expected two hidden layers: three weight and three bias layers")
+    lay = evo2_layout(num_observations, H)
+    flat = [weight_layers[0], bias_layers[0], weight_layers[1], bias_layers[1], weight_layers[2], bias_layers[2]]
+    for t, (_, shp) in zip(flat, lay.values()):
+        if tuple(t.shape) != shp:
+            raise ValueError(f"layer of shape {tuple(t.shape)}, expected {shp}")
+    theta = torch.cat([t.detach().reshape(-1).to(dtype=torch.float32) for t in flat])
+    if not bool(torch.isfinite(theta).all()):
+        raise ValueError("parameters have non-finite entries")
+    return theta.contiguous()
+
+
+def evo2_views(theta: torch.Tensor, num_observations: int, H: int) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
+    v = {k: theta[off:off + s[0] * s[1]].view(*s) for k, (off, s) in evo2_layout(num_observations, H).items()}
+    return [v["W1"], v["W2"], v["W3"]], [v["b1"], v["b2"], v["b3"]]
+
+
+class FusedPopulationMLP2Rollout(FusedPopulationMLPRollout):
+    """``FusedPopulationMLPRollout`` with the reference's default two hidden layers (H, H): the network is
+    ``tanh(W3^T tanh(W2^T tanh(W1^T x + b1) + b2) + b3)`` (include/finenvs_amd_evo2.h, ``fe_evo2_rollout``); members, noise
+    streams, episode state, ``noise`` and ``gradient`` are the one-layer class's, at ``num_params = 5WH + H^2 + 3H + 1``.
+    theta lives in the LDS: H <= 128, and a window that cannot fit is refused here, before any launch."""
+
+    HIDDEN = (32, 64, 128)
+    LDS_BYTES = 160 * 1024
+    _ENTRY = "fe_evo2_rollout"
+
+    @staticmethod
+    def _count_params(num_observations: int, H: int) -> int:
+        return num_observations * H + H * H + 3 * H + 1
+
+    def _hidden_message(self) -> str:
+        return (f"hidden_dim must be one of {self.HIDDEN} (theta lives in the 160 KiB LDS: the middle layer of the reference's "
+                "256 alone is 256 KiB)")
+
+    def __init__(self, env, num_eval_envs: int, hidden_dim: int, noise_std_dev: float, seed: int,
+                 action_noise_std: float = 0.01, max_episodes: int = 8):
+        super().__init__(env, num_eval_envs, hidden_dim, noise_std_dev, seed, action_noise_std=action_noise_std,
+                         max_episodes=max_episodes)
+        W, A = env.num_intervals, env.num_assets
+        if A > 128:
+            raise ValueError(f"the ES population runs at most 128 assets per env (got {A})")
+        need = int(env._lib.fe_evo2_lds_bytes(W, A, self.H))
+        assert self.num_params == int(env._lib.fe_evo2_num_params(W, self.H))
+        if need > self.LDS_BYTES:
+            raise ValueError(f"theta ({self.num_params} floats at window {W}, H = {self.H}) does not fit the 160 KiB LDS "
+                             f"({need} bytes needed with {A} asset(s))")
+
+    def set_parameters(self, weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor]) -> None:
+        """ParallelMLP's lists: ``weight_layers = [W1 (5W, H), W2 (H, H), W3 (H, 1)]``, ``bias_layers = [b1 (1, H), b2 (1, H),
+        b3 (1, 1)]``."""
+        self.theta = evo2_flatten(weight_layers, bias_layers, self.num_observations, self.H).to(self.env._dev)
+
+    def parameters(self) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+        """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
+        return evo2_views(self.theta, self.num_observations, self.H)
+
+
 # ---------------------------------------------------------------- the agent
 class FusedEvoAgent:
     """EvoAgent (evo_agent.py) on a TimeSeriesEnv with the fused population: ``collect`` replaces the loop
     agent.step -> env.step -> agent.store, ``train`` the update, ``log_progress`` the progress record."""
 
-    def __init__(self, env, hidden_dim: int = 64, learning_rate: float = 0.01, noise_std_dev: float = 0.02,
+    def __init__(self, env, hidden_dim: int = 64, hidden_layers: int = 1, learning_rate: float = 0.01, noise_std_dev: float = 0.02,
                  l2_coefficient: float = 0.005, num_eval_envs: Optional[int] = None, seed: int = 0,
                  action_noise_std: float = 0.01, max_episodes: int = 8):
         if num_eval_envs is None:
             num_eval_envs = 2 if env.num_envs % 2 == 0 else 1
         self.env = env
         self.learning_rate, self.l2_coefficient = float(learning_rate), float(l2_coefficient)
-        self.population = FusedPopulationMLPRollout(env, num_eval_envs, hidden_dim, noise_std_dev, seed,
-                                                    action_noise_std=action_noise_std, max_episodes=max_episodes)
+        if hidden_layers not in (1, 2):
+            raise ValueError("hidden_layers must be 1 or 2")
+        population = FusedPopulationMLPRollout if hidden_layers == 1 else FusedPopulationMLP2Rollout
+        self.hidden_layers = int(hidden_layers)
+        self.population = population(env, num_eval_envs, hidden_dim, noise_std_dev, seed,
+                                     action_noise_std=action_noise_std, max_episodes=max_episodes)
         pop = self.population
-        w, b = init_parameters(pop.num_observations, pop.H, torch.Generator().manual_seed(int(seed)))
+        w, b = init_parameters(pop.num_observations, pop.H, torch.Generator().manual_seed(int(seed)), self.hidden_layers)
         pop.set_parameters(w, b)
         self.first_moment = torch.zeros_like(pop.theta)
         self.second_moment = torch.zeros_like(pop.theta)

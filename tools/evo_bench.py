@@ -4,6 +4,10 @@ batched matmul (parallel_mlp.py:84-156) + env.step, with and without EvoAgent.st
 (evo_agent.py:96-112).
 
     timeout -k 10 600 python tools/evo_bench.py [--envs 16384] [--window 16] [--hidden 64] [--steps 32] [--assets 1]
+                                                [--hidden-layers 2]
+
+``--hidden-layers 2``: the two-hidden-layer population (fe_evo2_rollout) against a three-layer ParallelMLP restated in
+torch, and against the one-layer kernel at the same H where that exists (H = 32 / 64).
 
 Prints one line per arm and a final JSON line.
 """
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--assets", type=int, default=1)
     ap.add_argument("--eval-envs", type=int, default=2)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--hidden-layers", type=int, default=1, choices=(1, 2))
     a = ap.parse_args()
     N, W, H, K, A, E = a.envs, a.window, a.hidden, a.steps, a.assets, a.eval_envs
     prices, day_id, _ = make_series(A)
@@ -49,10 +54,20 @@ def main():
         return finenvs_amd.TimeSeriesEnv(prices=prices, day_id=day_id, num_intervals=W, num_envs=N, redraw="device",
                                          obs_buffers=2)
 
+    L = a.hidden_layers
     out = {"envs": N, "window": W, "hidden": H, "steps_per_launch": K, "assets": A}
+    if L == 2:
+        out["hidden_layers"] = 2
+        if H in (32, 64):  # the one-layer kernel at the same H, in the same process
+            env = make_env()
+            one = FusedEvoAgent(env, hidden_dim=H, num_eval_envs=E, max_episodes=64).population
+            out["one_layer_us_per_step"] = 1e3 * timed(lambda: one.run(K), a.reps) / K
+            print(f"one-layer population : {out['one_layer_us_per_step']:9.1f} us/step")
+            del one, env
+            torch.cuda.empty_cache()
     # ---- fused
     env = make_env()
-    agent = FusedEvoAgent(env, hidden_dim=H, num_eval_envs=E, max_episodes=64)
+    agent = FusedEvoAgent(env, hidden_dim=H, hidden_layers=L, num_eval_envs=E, max_episodes=64)
     pop = agent.population
     fused_ms = timed(lambda: pop.run(K), a.reps) / K
     out["fused_us_per_step"] = 1e3 * fused_ms
@@ -69,7 +84,7 @@ def main():
     dev = env._dev
     n_train, half = N - E, (N - E) // 2
     torch.manual_seed(0)
-    shapes = [(5 * W, H), (H, 1)]
+    shapes = [(5 * W, H), (H, 1)] if L == 1 else [(5 * W, H), (H, H), (H, 1)]
     layers = [(torch.randn(s, device=dev) * (2 / s[0]) ** 0.5, torch.randn((1, s[1]), device=dev) * (2 / s[0]) ** 0.5) for s in shapes]
 
     def perturb():
@@ -119,6 +134,8 @@ def main():
     print(f"torch perturb (once per generation): {out['perturb_ms']:.3f} ms")
     out["speedup_vs_torch"] = t_ms / fused_ms
     out["speedup_vs_torch_store"] = ts_ms / fused_ms
+    if "one_layer_us_per_step" in out:
+        out["ratio_to_one_layer"] = out["fused_us_per_step"] / out["one_layer_us_per_step"]
     print(json.dumps(out))
 
 
