@@ -13,9 +13,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["fe_env.hip", "fe_mlp_critic.hip", "fe_mlp_sac.hip", "fe_evo2.hip", "fe_csv.cpp"]
-HEADERS = ["fe_device_common.h", "fe_store_policy.h", "fe_step_kernel.h", "fe_activations.h", "fe_rollout_kernels.h", "fe_mlp_head_kernels.h", "fe_mlp2_head_kernels.h", "fe_lstm_kernel.h", "fe_lstm_rollout_body.h", "fe_lstm_big_rollout_body.h", "fe_lstm_stream_tile.h", "fe_lstm_stream_sgrad_body.h", "fe_aux_kernels.h", "fe_evo_kernels.h", "fe_replay_kernels.h", "fe_ring_draw_kernels.h", "fe_ppo_kernels.h", "fe_critic_kernels.h", "fe_bptt_tile.h", "fe_critic_grad_kernels.h", "fe_sac_grad_kernels.h", "fe_lstm_grad_kernels.h", "fe_lstm_grad_streamed_kernels.h", "fe_critic_streamed_kernels.h", "fe_sac_streamed_kernels.h", "fe_optim_kernels.h",
-           "fe_mlp_critic_kernels.h", "fe_mlp_sac_kernels.h", "fe_evo2_kernels.h", "fe_host_common.h"]  # included by fe_env.hip; the last four by fe_mlp_critic.hip / fe_mlp_sac.hip / fe_evo2.hip, with the MLP and ES headers
+SOURCES = ["fe_env.hip", "fe_mlp_critic.hip", "fe_mlp_sac.hip", "fe_evo.hip", "fe_csv.cpp"]
+HEADERS = ["fe_device_common.h", "fe_store_policy.h", "fe_step_kernel.h", "fe_activations.h", "fe_rollout_kernels.h", "fe_mlp_head_kernels.h", "fe_mlp2_head_kernels.h", "fe_lstm_kernel.h", "fe_lstm_rollout_body.h", "fe_lstm_big_rollout_body.h", "fe_lstm_stream_tile.h", "fe_lstm_stream_sgrad_body.h", "fe_aux_kernels.h", "fe_replay_kernels.h", "fe_ring_draw_kernels.h", "fe_ppo_kernels.h", "fe_critic_kernels.h", "fe_bptt_tile.h", "fe_critic_grad_kernels.h", "fe_sac_grad_kernels.h", "fe_lstm_grad_kernels.h", "fe_lstm_grad_streamed_kernels.h", "fe_critic_streamed_kernels.h", "fe_sac_streamed_kernels.h", "fe_optim_kernels.h",
+           "fe_mlp_critic_kernels.h", "fe_mlp_sac_kernels.h", "fe_evo_kernels.h", "fe_host_common.h"]  # included by fe_env.hip; the last four by fe_mlp_critic.hip / fe_mlp_sac.hip / fe_evo.hip, the first two of them with the MLP headers
 LIB = os.path.join(HERE, "libfinenvs_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [

@@ -63,8 +63,9 @@ thread_local char g_err[512] = "";
 // Records the message fe_last_error returns and passes `code` through.  fe_csv.cpp calls it by this name: hidden
 // visibility keeps it internal to the library, not an exported symbol.
 #ifdef FE_ERROR_BUFFER_ELSEWHERE
-// A second translation unit of the library (fe_mlp_critic.hip) defines FE_ERROR_BUFFER_ELSEWHERE before it includes this
-// header: the one error buffer and fe_set_error's definition stay in fe_env.hip, this unit only calls it.
+// The smaller translation units of the library (fe_mlp_critic.hip, fe_mlp_sac.hip, fe_evo.hip) define
+// FE_ERROR_BUFFER_ELSEWHERE before they include this header: the one error buffer and fe_set_error's definition stay in
+// fe_env.hip, those units only call it.
 extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...);
 #else
 extern "C" __attribute__((visibility("hidden"))) int fe_set_error(int code, const char *fmt, ...) {

@@ -39,7 +39,6 @@
 //                           rollout kernel and by fe_lstm_stream_sgrad_body.h
 //   fe_lstm_stream_sgrad_body.h  the tile loop of the streamed head's and the streamed critics' recurrence kernels
 //   fe_aux_kernels.h      descriptor / render kernels, init kernels (log-returns, day tables), trajectory kernels
-//   fe_evo_kernels.h      evolution-strategies population rollout (per-env perturbed MLP), ES gradient, noise render
 //   fe_replay_kernels.h   off-policy replay ring of observation descriptors: append, fused minibatch sample
 //   fe_ring_draw_kernels.h  a mini-batch drawn and gathered from the ring's device cursor (capturable updates)
 //   fe_ppo_kernels.h     PPO's mini-batch drawn from a keyed permutation and gathered, and its two losses with gradients
@@ -72,7 +71,6 @@
 
 #include "finenvs_amd.h"
 #include "finenvs_amd_ext.h"
-#include "finenvs_amd_evo.h"
 #include "finenvs_amd_replay.h"
 #include "finenvs_amd_sac.h"
 #include "finenvs_amd_critic.h"
@@ -96,7 +94,6 @@
 #include "fe_mlp2_head_kernels.h"
 #include "fe_lstm_kernel.h"
 #include "fe_aux_kernels.h"
-#include "fe_evo_kernels.h"
 #include "fe_replay_kernels.h"
 #include "fe_ring_draw_kernels.h"
 #include "fe_ppo_kernels.h"
@@ -113,7 +110,7 @@ namespace {
 
 // Largest grid of the grid-strided element-wise launches and of the tile-looping rollouts.
 constexpr int64_t kMaxGrid = 8 * 256;
-// Dynamic LDS a workgroup can have: the MLP, evo and split-LSTM launches refuse more, each with its own message.
+// Dynamic LDS a workgroup can have: the MLP and split-LSTM launches refuse more, each with its own message.
 constexpr size_t kMaxLds = 160 * 1024;
 
 int64_t capped_grid(int64_t tiles) { return tiles < kMaxGrid ? tiles : kMaxGrid; }
@@ -297,7 +294,7 @@ static hipError_t prepare_kernel(int device, const void *kern, int block, size_t
     return he;
 }
 
-// The big-LDS path of the MLP, evo and split-LSTM rollouts (the caller has refused lds > kMaxLds in its own words):
+// The big-LDS path of the MLP and split-LSTM rollouts (the caller has refused lds > kMaxLds in its own words):
 // prepare_kernel for a kBlock-thread launch, its failure reported as "<who>: hipFuncSetAttribute: <HIP error>" ...
 static int prepare_big_lds(int device, const void *kern, size_t lds, const char *who) {
     const hipError_t he = prepare_kernel(device, kern, kBlock, lds, nullptr);
@@ -1598,91 +1595,6 @@ int fe_traj_returns(const double *rewards, const int32_t *dones, const float *va
     return launched("fe_traj_returns");
 }
 
-// ---- include/finenvs_amd_evo.h: the evolution-strategies population ----
-
-int fe_evo_rollout(fe_env *env, const fe_evo_population *pop, int32_t K, float *actions_out, float *means_out,
-                   double *rewards_out, int32_t *dones_out, void *stream) {
-    if (!env || !pop || K < 1 || !pop->logret_f32 || !pop->theta || !pop->obs_src || !pop->obs_pos || !pop->returns ||
-        !pop->timesteps || !pop->episode_returns || !pop->episode_counts || !pop->counters || !pop->scratch_rewards ||
-        !pop->scratch_dones)
-        return fail(FE_ERR_ARG, "fe_evo_rollout: bad argument");
-    if (!env->bound) return fail(FE_ERR_ARG, "fe_evo_rollout: env state not bound");
-    const int32_t H = pop->hidden;
-    if (H != 32 && H != 64) return fail(FE_ERR_ARG, "fe_evo_rollout: H must be 32 or 64 (got %d)", (int)H);
-    Params p = env->p;
-    const int64_t nt = pop->num_train;
-    if (nt <= 0 || nt % 2 != 0 || nt > p.N)
-        return fail(FE_ERR_ARG, "fe_evo_rollout: the %lld training envs must be positive, even and at most N = %lld "
-                    "(mirrored sampling, parallel_mlp.py:24-27)", (long long)nt, (long long)p.N);
-    if (pop->max_episodes < 1) return fail(FE_ERR_ARG, "fe_evo_rollout: max_episodes must be >= 1");
-    if (p.evaluate) return fail(FE_ERR_ARG, "fe_evo_rollout: the population needs a training-mode env (evaluate = 0)");
-    if (p.redraw_mode != 1) return fail(FE_ERR_ARG, "fe_evo_rollout: the population needs redraw mode 1 (device redraws)");
-    if (p.A > 128) return fail(FE_ERR_ARG, "fe_evo_rollout: at most 128 assets per env (got %d)", (int)p.A);
-    DeviceGuard guard(env->device);
-    if (int rc = guard.status()) return rc;
-    // a tile = PB mirrored pairs (2 PB envs): each wavefront evaluates whole pairs, every z element serves both signs
-    int PB = 128 / p.A;
-    if (PB > 8) PB = 8;
-    if (PB < 1) PB = 1;
-    const int64_t half = nt / 2;
-    const int EB = 2 * PB;
-    const int64_t pair_tiles = (half + PB - 1) / PB;
-    const int64_t eval_tiles = (p.N - nt + EB - 1) / EB;
-    p.EB = EB;
-    p.num_tiles = pair_tiles + eval_tiles;
-    const int64_t P = evo_num_params(p.W, H);
-    const size_t lds = evo_lds_bytes(EB, p.A, P);
-    if (lds > kMaxLds)
-        return fail(FE_ERR_ARG, "fe_evo_rollout: theta (%lld floats) does not fit the 160 KiB LDS (%zu bytes needed)",
-                    (long long)P, lds);
-    EvoArgs r;
-    r.lr32 = pop->logret_f32; r.theta = pop->theta; r.obs_src = pop->obs_src; r.obs_pos = pop->obs_pos;
-    r.ret = pop->returns; r.ts = pop->timesteps; r.ep_ret = pop->episode_returns; r.ep_cnt = pop->episode_counts;
-    r.counters = reinterpret_cast<unsigned long long *>(pop->counters);
-    r.actions_out = actions_out; r.means_out = means_out; r.rew_out = rewards_out; r.done_out = dones_out;
-    r.rew_scratch = pop->scratch_rewards; r.done_scratch = pop->scratch_dones;
-    r.n_train = nt; r.half = half; r.K = K; r.max_ep = pop->max_episodes; r.PB = PB; r.pair_tiles = (int32_t)pair_tiles;
-    r.sigma = pop->noise_std; r.nu = pop->action_noise_std; r.seed = pop->seed; r.g = pop->generation; r.step0 = pop->step;
-    const void *kern = with_nt(p.A == 1, H, [](auto S, auto NT) {  // H = 32 or 64 here, and the kernel takes H itself
-        return (const void *)fe_evo_rollout_kernel<decltype(S)::value, decltype(NT)::value == 1 ? 32 : 64>;
-    });
-    // one workgroup per tile (capped); the tile is fixed by the pair layout above, without fe_env_set_launch's override
-    return launch_big_lds(env->device, kern, capped_grid(p.num_tiles), lds, p, r, stream, "fe_evo_rollout");
-}
-
-int64_t fe_evo_gradient_workspace_doubles(int64_t num_pairs, int64_t num_params) {
-    if (num_pairs < 1 || num_params < 1) return 0;
-    return (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs * num_params;
-}
-
-int fe_evo_gradient(uint64_t seed, uint32_t generation, int64_t num_pairs, int64_t num_params, const float *diffed,
-                    double *workspace, double *out, void *stream) {
-    if (!diffed || !workspace || !out || num_pairs < 1 || num_params < 1 || num_pairs > 0xffffffffll ||
-        num_params > 4 * 0xffffffffll)
-        return fail(FE_ERR_ARG, "fe_evo_gradient: bad argument");
-    DeviceGuard guard(device_of(out));
-    if (int rc = guard.status("fe_evo_gradient: out is not device memory")) return rc;
-    const int64_t blocks = (num_pairs + kEvoGradPairs - 1) / kEvoGradPairs;
-    const int64_t threads = blocks * ((num_params + 3) / 4);
-    hipLaunchKernelGGL(fe_evo_gradient_partial_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, seed, generation, num_pairs, num_params, diffed, workspace);
-    hipLaunchKernelGGL(fe_evo_gradient_reduce_kernel, dim3((unsigned)((num_params + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, blocks, num_params, (const double *)workspace, out);
-    return launched("fe_evo_gradient");
-}
-
-int fe_evo_noise(uint64_t seed, uint32_t generation, const int64_t *pairs, int64_t count, int64_t num_params, float *out,
-                 void *stream) {
-    if (!pairs || !out || count < 1 || num_params < 1 || num_params > 4 * 0xffffffffll)
-        return fail(FE_ERR_ARG, "fe_evo_noise: bad argument");
-    DeviceGuard guard(device_of(out));
-    if (int rc = guard.status("fe_evo_noise: out is not device memory")) return rc;
-    const int64_t threads = count * ((num_params + 3) / 4);
-    hipLaunchKernelGGL(fe_evo_noise_kernel, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       (hipStream_t)stream, seed, generation, pairs, count, num_params, out);
-    return launched("fe_evo_noise");
-}
-
 // ---- include/finenvs_amd_replay.h: the off-policy replay ring ----
 
 static bool replay_ring_ok(const fe_replay_ring *ring) {
@@ -2806,7 +2718,7 @@ int fe_ppo_value_loss(const float *values, const float *returns, int64_t count, 
 
 }  // extern "C"
 
-// ---- what the library's other translation units (fe_mlp_critic.hip, fe_mlp_sac.hip) need of this one: hidden visibility, as
+// ---- what the library's other translation units (fe_mlp_critic.hip, fe_mlp_sac.hip, fe_evo.hip) need of this one: hidden visibility, as
 // fe_set_error is shared with fe_csv.cpp.  Host code only: this unit's device code object is what it was. ----
 // An env's window, asset count and device.
 extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(const fe_env *env, int32_t *W, int32_t *A, int *device) {
@@ -2815,13 +2727,16 @@ extern "C" __attribute__((visibility("hidden"))) void fe_env_shape_internal(cons
     *device = env->device;
 }
 
+// Whether fe_env_bind_state has been called: fe_evo_rollout refuses an unbound env in words of its own.
+extern "C" __attribute__((visibility("hidden"))) int fe_env_bound_internal(const fe_env *env) { return env->bound; }
+
 // prepare_big_lds for a kernel of the other unit: one cache of (device, kernel) attributes for the whole library.
 extern "C" __attribute__((visibility("hidden"))) int fe_prepare_big_lds_internal(int device, const void *kern, size_t lds,
                                                                                  const char *who) {
     return prepare_big_lds(device, kern, lds, who);
 }
 
-// What a K-step MLP rollout of the third unit (fe_mlp_sac.hip) takes from the env, as rollout_mlp_sampled_impl does: the
+// What a K-step rollout of the third and fourth units (fe_mlp_sac.hip, fe_evo.hip) takes from the env, as rollout_mlp_sampled_impl does: the
 // state is bound, a copy of the parameter block with the rollout's tile set (128 pairs per workgroup), and the grid.
 extern "C" __attribute__((visibility("hidden"))) int fe_env_mlp_rollout_internal(const fe_env *env, const char *who, void *params_out,
                                                                                  size_t params_bytes, int64_t *grid_out) {

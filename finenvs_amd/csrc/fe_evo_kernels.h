@@ -1,7 +1,17 @@
-// fe_evo_kernels.h -- part of fe_env.hip (one translation unit; see the overview there): the evolution-strategies
-// population -- a K-step rollout in which every env acts with ITS OWN perturbed one-hidden-layer perceptron, generated
+// fe_evo_kernels.h -- part of fe_evo.hip (one translation unit of the library): the evolution-strategies population -- a
+// K-step rollout in which every env acts with ITS OWN perturbed perceptron of one hidden layer (H) or two (H, H), generated
 // inside the kernel from a counter-based normal stream -- plus the gradient and noise-render kernels of the ES update
-// (finenvs/agents/ES/evo_agent.py, finenvs/agents/networks/parallel_mlp.py; C ABI: include/finenvs_amd_evo.h).
+// (finenvs/agents/ES/evo_agent.py, finenvs/agents/networks/parallel_mlp.py; C ABI: include/finenvs_amd_evo.h and
+// include/finenvs_amd_evo2.h).
+//
+// theta, each segment row-major (in, out): W1 (5W, H), b1 (H), [W2 (H, H), b2 (H),] Wo (H), bo.  Every segment starts at a
+// multiple of 4 (H is one), so z_{g,p,j} is word j % 4 of the counter (j / 4, p, g, 0x45565a00) at either depth.
+//
+// Summation order (fixed: two launches give the same bits, and run(32); run(32) equals run(64)).  Lane l owns the outputs
+// 4q..4q+3 (q = l % G, G = H / 4) of the rows rg, rg + R, ... (rg = l / G, R = 64 / G) of a hidden layer's weight, in
+// ascending order with fmaf from +0; then a butterfly over the row groups (xor G, 2G, ..., 32) completes the sums; then the
+// bias is added as (acc + (b + e)).  The output layer: four fmaf per lane in ascending i from +0, a butterfly over q (xor 1,
+// 2, ..., G / 2), + bo.
 #pragma once
 #include "fe_device_common.h"
 #include "fe_rollout_kernels.h"
@@ -82,124 +92,201 @@ struct EvoArgs {
     uint32_t g, step0;
 };
 
-__host__ __device__ inline int64_t evo_num_params(int W, int H) { return (int64_t)5 * W * H + 2 * (int64_t)H + 1; }
-
-__host__ __device__ inline size_t evo_lds_bytes(int EB, int A, int64_t P) {
-    size_t S = (size_t)EB * A;
-    size_t b = (size_t)EB * 8 + S * 8 + S * 8 + S * 4 + S * 4 + (size_t)EB * 4;  // TileLds
-    b = (b + 7) & ~(size_t)7;
-    b += (size_t)EB * 8;  // redrawn day per env
-    b += S * 4;           // actions
-    b = (b + 15) & ~(size_t)15;
-    b += (size_t)P * 4;   // theta
-    return (b + 15) & ~(size_t)15;
+// Floats of theta with `layers` hidden layers: 5W*H + 2H + 1, and H*H + H more for the middle layer.
+__host__ __device__ inline int64_t evo_num_params(int layers, int W, int H) {
+    return (int64_t)5 * W * H + (layers - 1) * ((int64_t)H * H + H) + 2 * (int64_t)H + 1;
 }
 
-// The policy of one unit = two env slots of the tile, by one wavefront.  Pair tiles: slot u is env p (sign +1), slot PB + u
-// env p + n_train/2 (sign -1) of the same pair p, so every z element is generated once and serves both signs.  Eval tiles:
-// slots 2u, 2u + 1, both unperturbed.  Lane l owns hidden units 4q..4q+3 (q = l % G, G = H / 4: one Philox call per row)
-// for the rows r = rg, rg + R, ... (rg = l / G, R = 64 / G) of W1; a butterfly over the row groups completes the first
-// layer, one over q the second.  Assets are evaluated one after the other with the env's weights (z regenerated per asset).
-template <bool SINGLE, int H>
-__device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &r, const TileLds &l, float *s_act,
-                                                const float *s_theta, bool pair_tile, int64_t base, int u, int k,
-                                                int lane) {
-    constexpr int G = H / 4, R = 64 / G;
-    const int A = SINGLE ? 1 : p.A;
-    const int R5 = 5 * p.W;
-    const int PB = r.PB;
-    int eA, eB;
-    int64_t nA, nB, pair = 0;
+// Byte offsets of a tile's dynamic LDS behind TileLds (carve_lds, at 0) and their total: the redrawn day per env, the
+// actions, theta (P floats) and, with two hidden layers only, the middle layer's exchange buffer: 2 H floats (members A
+// and B) for each of the workgroup's wavefronts.  The kernel and the host's byte count both read this.
+struct EvoLds {
+    size_t idx, act, theta, xchg, total;
+};
+
+__host__ __device__ inline EvoLds evo_lds(int layers, int EB, int A, int64_t P, int H) {
+    const size_t S = (size_t)EB * A;
+    EvoLds o;
+    o.idx = (size_t)EB * 8 + S * 8 + S * 8 + S * 4 + S * 4 + (size_t)EB * 4;  // TileLds
+    o.idx = (o.idx + 7) & ~(size_t)7;
+    o.act = o.idx + (size_t)EB * 8;
+    o.theta = (o.act + S * 4 + 15) & ~(size_t)15;
+    o.xchg = (o.theta + (size_t)P * 4 + 15) & ~(size_t)15;
+    o.total = o.xchg + (layers == 2 ? (size_t)(kBlock / 64) * 2 * H * 4 : 0);
+    return o;
+}
+
+// Compiler-level ordering of one wavefront's LDS traffic: a wave issues its DS instructions in order and they complete in
+// order, so what is needed is only that the compiler moves no LDS access across this point.  NOT a workgroup barrier: the
+// waves of a tile run different trip counts of the unit loop when PB is 7 or 1.
+__device__ __forceinline__ void evo_wave_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The two members of unit u of a tile.  Pair tiles: slot u is env p (sign +1), slot PB + u env p + n_train/2 (sign -1) of
+// the same pair p = base + u, so every z element is generated once and serves both signs.  Eval tiles: slots 2u, 2u + 1,
+// both unperturbed; a last odd env is computed twice (eB = eA) and stored once (vB is false).
+struct EvoMembers {
+    int eA, eB;      // env slots of the tile
+    int64_t nA, nB;  // env indices
+    int64_t pair;
     bool vA, vB;
+};
+
+__device__ __forceinline__ EvoMembers evo_members(const Params &p, const EvoArgs &r, bool pair_tile, int64_t base, int u) {
+    EvoMembers m;
+    m.pair = 0;
     if (pair_tile) {
-        pair = base + u;
-        eA = u; eB = PB + u;
-        nA = pair; nB = r.half + pair;
-        vA = vB = pair < r.half;
+        m.pair = base + u;
+        m.eA = u; m.eB = r.PB + u;
+        m.nA = m.pair; m.nB = r.half + m.pair;
+        m.vA = m.vB = m.pair < r.half;
     } else {
-        eA = 2 * u; eB = 2 * u + 1;
-        nA = base + eA; nB = base + eB;
-        vA = nA < p.N; vB = nB < p.N;
+        m.eA = 2 * u; m.eB = 2 * u + 1;
+        m.nA = base + m.eA; m.nB = base + m.eB;
+        m.vA = m.nA < p.N; m.vB = m.nB < p.N;
     }
-    if (!vA) return;          // wave-uniform
-    if (!vB) eB = eA;         // (an eval tile's last odd env: computed twice, stored once)
+    if (!m.vB) m.eB = m.eA;
+    return m;
+}
+
+// One hidden layer's sums for both members: acc[i] = sum over the lane's rows rg, rg + R, ... of x(row) * w[row][4q + i],
+// the weight perturbed by +- sigma z on pair tiles (Philox counter q0 + row * G + q, q0 the segment's offset / 4), then
+// the butterfly over the row groups.  x(row, xA, xB) gives the row's input of either member.
+template <int H, class X>
+__device__ __forceinline__ void evo_layer(const EvoArgs &r, bool pair_tile, int64_t pair, const float *w, uint32_t q0,
+                                          int rows, int lane, X x, float (&accA)[4], float (&accB)[4]) {
+    constexpr int G = H / 4, R = 64 / G;
     const int q = lane % G, rg = lane / G;
-    const float sigma = r.sigma;
-    const int64_t rstride = 4 * (int64_t)A;
-    const int64_t NA = p.N * A;
-    const uint32_t qb = (uint32_t)R5 * G;  // Philox counter of b1[0..3]
-    for (int a = 0; a < A; ++a) {
-        const float *xa = r.lr32 + l.src[eA] + 4 * a;
-        const float *xb = r.lr32 + l.src[eB] + 4 * a;
-        const float posA = (float)l.pos[eA * A + a], posB = (float)l.pos[eB * A + a];
-        float accA[4] = {0.0f, 0.0f, 0.0f, 0.0f}, accB[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int row = rg; row < R5; row += R) {
-            const int jw = row / 5, c = row - 5 * jw;
-            const float xA = c < 4 ? xa[jw * rstride + c] : posA;
-            const float xB = c < 4 ? xb[jw * rstride + c] : posB;
-            const float4 th = *reinterpret_cast<const float4 *>(s_theta + (size_t)row * H + 4 * q);
-            if (pair_tile) {
-                const float4 z = evo_z4(r.seed, r.g, pair, (uint32_t)row * G + q);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float e = sigma * f4get(z, i);
-                    accA[i] = fmaf(xA, f4get(th, i) + e, accA[i]);
-                    accB[i] = fmaf(xB, f4get(th, i) - e, accB[i]);
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    accA[i] = fmaf(xA, f4get(th, i), accA[i]);
-                    accB[i] = fmaf(xB, f4get(th, i), accB[i]);
-                }
-            }
-        }
-#pragma unroll
-        for (int m = G; m < 64; m <<= 1)
+    for (int i = 0; i < 4; ++i) accA[i] = accB[i] = 0.0f;
+    for (int row = rg; row < rows; row += R) {
+        float xA, xB;
+        x(row, xA, xB);
+        const float4 th = *reinterpret_cast<const float4 *>(w + (size_t)row * H + 4 * q);
+        if (pair_tile) {
+            const float4 z = evo_z4(r.seed, r.g, pair, q0 + (uint32_t)row * G + q);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                accA[i] = accA[i] + __shfl_xor(accA[i], m, 64);
-                accB[i] = accB[i] + __shfl_xor(accB[i], m, 64);
+                const float e = r.sigma * f4get(z, i);
+                accA[i] = fmaf(xA, f4get(th, i) + e, accA[i]);
+                accB[i] = fmaf(xB, f4get(th, i) - e, accB[i]);
             }
-        const float *tb = s_theta + (size_t)R5 * H;
-        const float4 b1 = *reinterpret_cast<const float4 *>(tb + 4 * q);
-        const float4 w2 = *reinterpret_cast<const float4 *>(tb + H + 4 * q);
-        float b2A = tb[2 * H], b2B = b2A;
-        float4 zb = make_float4(0.0f, 0.0f, 0.0f, 0.0f), zw = zb;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                accA[i] = fmaf(xA, f4get(th, i), accA[i]);
+                accB[i] = fmaf(xB, f4get(th, i), accB[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int m = G; m < 64; m <<= 1)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            accA[i] = accA[i] + __shfl_xor(accA[i], m, 64);
+            accB[i] = accB[i] + __shfl_xor(accB[i], m, 64);
+        }
+}
+
+// h = tanh(acc + (b +- sigma z)) for the lane's four hidden units; qb is the Philox counter of b[0..3].
+__device__ __forceinline__ void evo_hidden(const EvoArgs &r, bool pair_tile, int64_t pair, const float *b, uint32_t qb, int q,
+                                           const float (&accA)[4], const float (&accB)[4], float (&hA)[4], float (&hB)[4]) {
+    const float4 bq = *reinterpret_cast<const float4 *>(b + 4 * q);
+    float4 zb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (pair_tile) zb = evo_z4(r.seed, r.g, pair, qb + q);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float eb = r.sigma * f4get(zb, i);
+        hA[i] = lstm_tanh(accA[i] + (f4get(bq, i) + eb));
+        hB[i] = lstm_tanh(accB[i] + (f4get(bq, i) - eb));
+    }
+}
+
+// The policy of one unit = two env slots of the tile (evo_members), by one wavefront.  Every row group holds the same
+// hidden values after a layer's butterfly.  Row i of the middle layer needs h1[i] in every lane: the lanes of row group 0
+// write h1 to the wave's LDS buffer s_h (A at [0, H), B at [H, 2H); null with one hidden layer) and every lane reads the
+// rows it owns.  Assets are evaluated one after the other with the env's weights (z regenerated per asset).
+template <bool SINGLE, int H, int LAYERS>
+__device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &r, const TileLds &l, float *s_act,
+                                                const float *s_theta, float *s_h, bool pair_tile, int64_t base, int u,
+                                                int k, int lane) {
+    constexpr int G = H / 4;
+    const int A = SINGLE ? 1 : p.A;
+    const int R5 = 5 * p.W;
+    const EvoMembers m = evo_members(p, r, pair_tile, base, u);
+    if (!m.vA) return;  // wave-uniform
+    const int q = lane % G;
+    const int64_t rstride = 4 * (int64_t)A;
+    const int64_t NA = p.N * A;
+    for (int a = 0; a < A; ++a) {
+        const float *xa = r.lr32 + l.src[m.eA] + 4 * a;
+        const float *xb = r.lr32 + l.src[m.eB] + 4 * a;
+        const float posA = (float)l.pos[m.eA * A + a], posB = (float)l.pos[m.eB * A + a];
+        // the segment being read and the Philox counter of its first four floats advance together
+        const float *t = s_theta;
+        uint32_t qc = 0;
+        float accA[4], accB[4], hA[4], hB[4];
+        evo_layer<H>(r, pair_tile, m.pair, t, qc, R5, lane, [&](int row, float &xA, float &xB) {
+            const int jw = row / 5, c = row - 5 * jw;
+            xA = c < 4 ? xa[jw * rstride + c] : posA;
+            xB = c < 4 ? xb[jw * rstride + c] : posB;
+        }, accA, accB);
+        t += (size_t)R5 * H; qc += (uint32_t)R5 * G;
+        evo_hidden(r, pair_tile, m.pair, t, qc, q, accA, accB, hA, hB);
+        t += H; qc += G;
+        if constexpr (LAYERS == 2) {
+            evo_wave_fence();  // the previous asset's (step's, unit's) reads of s_h are done
+            if (lane < G) {    // row group 0
+                *reinterpret_cast<float4 *>(s_h + 4 * q) = make_float4(hA[0], hA[1], hA[2], hA[3]);
+                *reinterpret_cast<float4 *>(s_h + H + 4 * q) = make_float4(hB[0], hB[1], hB[2], hB[3]);
+            }
+            evo_wave_fence();  // h1 is in s_h before any lane reads it
+            evo_layer<H>(r, pair_tile, m.pair, t, qc, H, lane, [&](int row, float &xA, float &xB) {
+                xA = s_h[row];
+                xB = s_h[H + row];
+            }, accA, accB);
+            t += (size_t)H * H; qc += (uint32_t)H * G;
+            evo_hidden(r, pair_tile, m.pair, t, qc, q, accA, accB, hA, hB);
+            t += H; qc += G;
+        }
+        // the output layer: t = Wo (H) with bo behind it, their counters qc + q and qc + G (word .x)
+        const float4 wo = *reinterpret_cast<const float4 *>(t + 4 * q);
+        float boA = t[H], boB = boA;
+        float4 zw = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (pair_tile) {
-            zb = evo_z4(r.seed, r.g, pair, qb + q);
-            zw = evo_z4(r.seed, r.g, pair, qb + G + q);
-            const float e = sigma * evo_z4(r.seed, r.g, pair, qb + 2 * G).x;
-            b2A = b2A + e;
-            b2B = b2B - e;
+            zw = evo_z4(r.seed, r.g, m.pair, qc + q);
+            const float e = r.sigma * evo_z4(r.seed, r.g, m.pair, qc + G).x;
+            boA = boA + e;
+            boB = boB - e;
         }
         float partA = 0.0f, partB = 0.0f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const float eb = sigma * f4get(zb, i), ew = sigma * f4get(zw, i);
-            const float hA = lstm_tanh(accA[i] + (f4get(b1, i) + eb));
-            const float hB = lstm_tanh(accB[i] + (f4get(b1, i) - eb));
-            partA = fmaf(f4get(w2, i) + ew, hA, partA);
-            partB = fmaf(f4get(w2, i) - ew, hB, partB);
+            const float ew = r.sigma * f4get(zw, i);
+            partA = fmaf(f4get(wo, i) + ew, hA[i], partA);
+            partB = fmaf(f4get(wo, i) - ew, hB[i], partB);
         }
 #pragma unroll
-        for (int m = 1; m < G; m <<= 1) {
-            partA = partA + __shfl_xor(partA, m, 64);
-            partB = partB + __shfl_xor(partB, m, 64);
+        for (int s = 1; s < G; s <<= 1) {
+            partA = partA + __shfl_xor(partA, s, 64);
+            partB = partB + __shfl_xor(partB, s, 64);
         }
-        const float outA = lstm_tanh(partA + b2A), outB = lstm_tanh(partB + b2B);
+        const float outA = lstm_tanh(partA + boA), outB = lstm_tanh(partB + boB);
         float actA = outA, actB = outB;
         if (pair_tile && r.nu != 0.0f) {  // parallel_mlp.py:95,106-110: training members only
             const uint32_t step = r.step0 + (uint32_t)k;
-            actA = outA + r.nu * evo_action_noise(r.seed, r.g, step, nA, a);
-            actB = outB + r.nu * evo_action_noise(r.seed, r.g, step, nB, a);
+            actA = outA + r.nu * evo_action_noise(r.seed, r.g, step, m.nA, a);
+            actB = outB + r.nu * evo_action_noise(r.seed, r.g, step, m.nB, a);
         }
         if (lane == 0) {
-            s_act[eA * A + a] = actA;
-            if (r.means_out) r.means_out[(int64_t)k * NA + nA * A + a] = outA;
-            if (vB) {
-                s_act[eB * A + a] = actB;
-                if (r.means_out) r.means_out[(int64_t)k * NA + nB * A + a] = outB;
+            s_act[m.eA * A + a] = actA;
+            if (r.means_out) r.means_out[(int64_t)k * NA + m.nA * A + a] = outA;
+            if (m.vB) {
+                s_act[m.eB * A + a] = actB;
+                if (r.means_out) r.means_out[(int64_t)k * NA + m.nB * A + a] = outB;
             }
         }
     }
@@ -208,26 +295,26 @@ __device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &
 // K steps of the whole population per launch: the loop of fe_rollout_mlp_kernel (account state in registers, descriptors
 // in LDS, account_keep), with the per-env policy above and EvoAgent.store's bookkeeping (evo_agent.py:96-112) where the
 // done flag is known.  Tiles: pair tiles [0, pair_tiles) hold PB mirrored pairs (2 PB envs), the rest EB = 2 PB
-// consecutive eval envs.
-template <bool SINGLE, int H>
-__global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params p, const EvoArgs r) {
+// consecutive eval envs.  At two layers and H = 128 theta is above half the LDS from W = 5 on, so one workgroup per CU
+// is resident there whatever the registers allow.
+template <bool SINGLE, int H, int LAYERS>
+__device__ __forceinline__ void evo_rollout_body(const Params &p, const EvoArgs &r) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int A = SINGLE ? 1 : p.A;
     const int EB = p.EB;
     const int S = EB * A;
+    const int64_t P = evo_num_params(LAYERS, p.W, H);
     const TileLds l = carve_lds(smem, EB, S);
-    size_t off = (size_t)EB * 8 + (size_t)S * 8 + (size_t)S * 8 + (size_t)S * 4 + (size_t)S * 4 + (size_t)EB * 4;
-    off = (off + 7) & ~(size_t)7;
-    int64_t *l_idx = reinterpret_cast<int64_t *>(smem + off);
-    off += (size_t)EB * 8;
-    float *s_act = reinterpret_cast<float *>(smem + off);
-    off = (off + (size_t)S * 4 + 15) & ~(size_t)15;
-    float *s_theta = reinterpret_cast<float *>(smem + off);
-    const int64_t P = evo_num_params(p.W, H);
+    const EvoLds o = evo_lds(LAYERS, EB, A, P, H);
+    int64_t *l_idx = reinterpret_cast<int64_t *>(smem + o.idx);
+    float *s_act = reinterpret_cast<float *>(smem + o.act);
+    float *s_theta = reinterpret_cast<float *>(smem + o.theta);
     const int tid = threadIdx.x;
     const int e = SINGLE ? tid : (int)fdiv((uint32_t)tid, p.div_A);
     const int a = SINGLE ? 0 : tid - e * A;
     const int lane = tid & 63, wave = tid >> 6;
+    float *s_h = nullptr;
+    if constexpr (LAYERS == 2) s_h = reinterpret_cast<float *>(smem + o.xchg) + (size_t)wave * 2 * H;
     const int64_t NA = p.N * A;
     const int PB = r.PB;
     for (int64_t i = tid; i < P; i += kBlock) s_theta[i] = r.theta[i];
@@ -262,7 +349,7 @@ __global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params 
         __syncthreads();  // also covers theta on the first tile
         for (int k = 0; k < r.K; ++k) {
             for (int u = wave; u < PB; u += kBlock / 64)
-                evo_policy_unit<SINGLE, H>(p, r, l, s_act, s_theta, pair_tile, base, u, k, lane);
+                evo_policy_unit<SINGLE, H, LAYERS>(p, r, l, s_act, s_theta, s_h, pair_tile, base, u, k, lane);
             lds_barrier();
             const float act = active ? s_act[e * A + a] : 0.0f;
             if (active && r.actions_out) r.actions_out[(int64_t)k * NA + sl] = act;
@@ -298,6 +385,17 @@ __global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params 
         }
         __syncthreads();
     }
+}
+
+// The entry points: one hidden layer (fe_evo_rollout, H = 32 / 64) and two (fe_evo2_rollout, H = 32 / 64 / 128).
+template <bool SINGLE, int H>
+__global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params p, const EvoArgs r) {
+    evo_rollout_body<SINGLE, H, 1>(p, r);
+}
+
+template <bool SINGLE, int H>
+__global__ __launch_bounds__(kBlock, 2) void fe_evo2_rollout_kernel(const Params p, const EvoArgs r) {
+    evo_rollout_body<SINGLE, H, 2>(p, r);
 }
 
 // First pass of the gradient: partial[b][j] = sum over the pairs of block b (ascending) of diffed[p] * z_{g,p,j}, in f64.

@@ -80,6 +80,62 @@ def init_parameters(num_observations: int, hidden_dim: int, generator: torch.Gen
     return weights, biases
 
 
+# ---------------------------------------------------------------- theta's layout
+def evo_layout(num_observations: int, H: int, hidden_layers: int) -> Dict[str, Tuple[int, Tuple[int, int]]]:
+    """The flat layout of theta with one or two hidden layers (include/finenvs_amd_evo.h, finenvs_amd_evo2.h): name ->
+    (offset, ParallelMLP shape), W1, b1, W2, b2[, W3, b3] in the reference's layer order.  Every offset is a multiple of 4
+    (H is), so the noise stream's definition is the same at either depth."""
+    dims = (int(num_observations),) + (H,) * hidden_layers + (1,)
+    out, off = {}, 0
+    for i, (fan_in, fan_out) in enumerate(zip(dims[:-1], dims[1:]), start=1):
+        for name, shape in ((f"W{i}", (fan_in, fan_out)), (f"b{i}", (1, fan_out))):
+            out[name] = (off, shape)
+            off += shape[0] * shape[1]
+    return out
+
+
+_LAYER_LISTS = {1: "expected one hidden layer: two weight and two bias layers",
+                2: "expected two hidden layers: three weight and three bias layers"}
+
+
+def evo_flatten(weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor], num_observations: int, H: int,
+                hidden_layers: int, device=None) -> torch.Tensor:
+    """ParallelMLP's lists of weight and bias layers as one f32 theta in ``evo_layout``'s order (each layer moved to
+    ``device`` first, if one is given); refuses wrong shapes and non-finite entries."""
+    if len(weight_layers) != hidden_layers + 1 or len(bias_layers) != hidden_layers + 1:
+        raise ValueError(_LAYER_LISTS[hidden_layers])
+    flat = [t for pair in zip(weight_layers, bias_layers) for t in pair]
+    for t, (_, shp) in zip(flat, evo_layout(num_observations, H, hidden_layers).values()):
+        if tuple(t.shape) != shp:
+            raise ValueError(f"layer of shape {tuple(t.shape)}, expected {shp}")
+    theta = torch.cat([t.detach().reshape(-1).to(device=device, dtype=torch.float32) for t in flat])
+    if not bool(torch.isfinite(theta).all()):
+        raise ValueError("parameters have non-finite entries")
+    return theta.contiguous()
+
+
+def evo_views(theta: torch.Tensor, num_observations: int, H: int, hidden_layers: int) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
+    v = {k: theta[off:off + s[0] * s[1]].view(*s) for k, (off, s) in evo_layout(num_observations, H, hidden_layers).items()}
+    return [v[f"W{i}"] for i in range(1, hidden_layers + 2)], [v[f"b{i}"] for i in range(1, hidden_layers + 2)]
+
+
+def evo2_layout(num_observations: int, H: int) -> Dict[str, Tuple[int, Tuple[int, int]]]:
+    """``evo_layout`` of the two-hidden-layer theta."""
+    return evo_layout(num_observations, H, 2)
+
+
+def evo2_flatten(weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor], num_observations: int,
+                 H: int) -> torch.Tensor:
+    """``evo_flatten`` of three weight and three bias layers, on the device they are on."""
+    return evo_flatten(weight_layers, bias_layers, num_observations, H, 2)
+
+
+def evo2_views(theta: torch.Tensor, num_observations: int, H: int) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
+    """``evo_views`` of the two-hidden-layer theta."""
+    return evo_views(theta, num_observations, H, 2)
+
+
 # ---------------------------------------------------------------- the population rollout
 class FusedPopulationMLPRollout(_FusedEvaluation):
     """K steps of an ES population per launch.  Env ``i < n_train/2`` acts with ``theta + sigma z_p`` (p = i), ``n_train/2 <= i
@@ -88,11 +144,12 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
     Needs a training-mode env with ``redraw="device"``."""
 
     HIDDEN = (32, 64)
+    LAYERS = 1  # hidden layers
     _ENTRY = "fe_evo_rollout"  # the C ABI's rollout of this network shape
 
-    @staticmethod
-    def _count_params(num_observations: int, H: int) -> int:
-        return num_observations * H + 2 * H + 1
+    @classmethod
+    def _count_params(cls, num_observations: int, H: int) -> int:
+        return sum(rows * cols for _, (rows, cols) in evo_layout(num_observations, H, cls.LAYERS).values())
 
     def _hidden_message(self) -> str:
         return f"hidden_dim must be one of {self.HIDDEN} (two hidden layers are out of scope)"
@@ -140,26 +197,13 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
 
     # -- parameters
     def set_parameters(self, weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor]) -> None:
-        """ParallelMLP's lists: ``weight_layers = [W1 (5W, H), W2 (H, 1)]``, ``bias_layers = [b1 (1, H), b2 (1, 1)]``."""
-        H, O = self.H, self.num_observations
-        want_w, want_b = [(O, H), (H, 1)], [(1, H), (1, 1)]
-        if len(weight_layers) != 2 or len(bias_layers) != 2:
-            raise ValueError("expected one hidden layer: two weight and two bias layers")
-        for t, shp in zip(list(weight_layers) + list(bias_layers), want_w + want_b):
-            if tuple(t.shape) != shp:
-                raise ValueError(f"layer of shape {tuple(t.shape)}, expected {shp}")
-        flat = [weight_layers[0], bias_layers[0], weight_layers[1], bias_layers[1]]
-        theta = torch.cat([t.detach().reshape(-1).to(device=self.env._dev, dtype=torch.float32) for t in flat])
-        if not bool(torch.isfinite(theta).all()):
-            raise ValueError("parameters have non-finite entries")
-        self.theta = theta.contiguous()
+        """ParallelMLP's lists: ``weight_layers = [W1 (5W, H), W2 (H, 1)]``, ``bias_layers = [b1 (1, H), b2 (1, 1)]``; with two
+        hidden layers ``[W1 (5W, H), W2 (H, H), W3 (H, 1)]`` and ``[b1 (1, H), b2 (1, H), b3 (1, 1)]``."""
+        self.theta = evo_flatten(weight_layers, bias_layers, self.num_observations, self.H, self.LAYERS, device=self.env._dev)
 
     def parameters(self) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
         """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
-        H, O, t = self.H, self.num_observations, self.theta
-        W1, b1 = t[:O * H].view(O, H), t[O * H:O * H + H].view(1, H)
-        W2, b2 = t[O * H + H:O * H + 2 * H].view(H, 1), t[O * H + 2 * H:].view(1, 1)
-        return [W1, W2], [b1, b2]
+        return evo_views(self.theta, self.num_observations, self.H, self.LAYERS)
 
     # -- rollout
     def run(self, num_steps: int, record: bool = False):
@@ -253,40 +297,6 @@ class FusedPopulationMLPRollout(_FusedEvaluation):
         return out
 
 
-def evo2_layout(num_observations: int, H: int) -> Dict[str, Tuple[int, Tuple[int, int]]]:
-    """The flat layout of the two-hidden-layer theta (include/finenvs_amd_evo2.h): name -> (offset, ParallelMLP shape), in the
-    reference's layer order.  Every offset is a multiple of 4 (H is), so the noise stream's definition carries over."""
-    O = int(num_observations)
-    out, off = {}, 0
-    for name, shape in (("W1", (O, H)), ("b1", (1, H)), ("W2", (H, H)), ("b2", (1, H)), ("W3", (H, 1)), ("b3", (1, 1))):
-        out[name] = (off, shape)
-        off += shape[0] * shape[1]
-    return out
-
-
-def evo2_flatten(weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor], num_observations: int,
-                 H: int) -> torch.Tensor:
-    """ParallelMLP's lists of three weight and three bias layers as one f32 theta in ``evo2_layout``'s order; refuses wrong
-    shapes and non-finite entries."""
-    if len(weight_layers) != 3 or len(bias_layers) != 3:
-        raise ValueError("expected two hidden layers: three weight and three bias layers")
-    lay = evo2_layout(num_observations, H)
-    flat = [weight_layers[0], bias_layers[0], weight_layers[1], bias_layers[1], weight_layers[2], bias_layers[2]]
-    for t, (_, shp) in zip(flat, lay.values()):
-        if tuple(t.shape) != shp:
-            raise ValueError(f"layer of shape {tuple(t.shape)}, expected {shp}")
-    theta = torch.cat([t.detach().reshape(-1).to(dtype=torch.float32) for t in flat])
-    if not bool(torch.isfinite(theta).all()):
-        raise ValueError("parameters have non-finite entries")
-    return theta.contiguous()
-
-
-def evo2_views(theta: torch.Tensor, num_observations: int, H: int) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
-    """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
-    v = {k: theta[off:off + s[0] * s[1]].view(*s) for k, (off, s) in evo2_layout(num_observations, H).items()}
-    return [v["W1"], v["W2"], v["W3"]], [v["b1"], v["b2"], v["b3"]]
-
-
 class FusedPopulationMLP2Rollout(FusedPopulationMLPRollout):
     """``FusedPopulationMLPRollout`` with the reference's default two hidden layers (H, H): the network is
     ``tanh(W3^T tanh(W2^T tanh(W1^T x + b1) + b2) + b3)`` (include/finenvs_amd_evo2.h, ``fe_evo2_rollout``); members, noise
@@ -294,12 +304,9 @@ class FusedPopulationMLP2Rollout(FusedPopulationMLPRollout):
     theta lives in the LDS: H <= 128, and a window that cannot fit is refused here, before any launch."""
 
     HIDDEN = (32, 64, 128)
+    LAYERS = 2
     LDS_BYTES = 160 * 1024
     _ENTRY = "fe_evo2_rollout"
-
-    @staticmethod
-    def _count_params(num_observations: int, H: int) -> int:
-        return num_observations * H + H * H + 3 * H + 1
 
     def _hidden_message(self) -> str:
         return (f"hidden_dim must be one of {self.HIDDEN} (theta lives in the 160 KiB LDS: the middle layer of the reference's "
@@ -317,15 +324,6 @@ class FusedPopulationMLP2Rollout(FusedPopulationMLPRollout):
         if need > self.LDS_BYTES:
             raise ValueError(f"theta ({self.num_params} floats at window {W}, H = {self.H}) does not fit the 160 KiB LDS "
                              f"({need} bytes needed with {A} asset(s))")
-
-    def set_parameters(self, weight_layers: Sequence[torch.Tensor], bias_layers: Sequence[torch.Tensor]) -> None:
-        """ParallelMLP's lists: ``weight_layers = [W1 (5W, H), W2 (H, H), W3 (H, 1)]``, ``bias_layers = [b1 (1, H), b2 (1, H),
-        b3 (1, 1)]``."""
-        self.theta = evo2_flatten(weight_layers, bias_layers, self.num_observations, self.H).to(self.env._dev)
-
-    def parameters(self) -> Tuple[List[torch.Tensor], List[torch.Tensor]]:
-        """(weight_layers, bias_layers) in ParallelMLP's shapes, views of ``theta``."""
-        return evo2_views(self.theta, self.num_observations, self.H)
 
 
 # ---------------------------------------------------------------- the agent

@@ -206,4 +206,4 @@ def test_entry_points_reject_bad_arguments_without_a_gpu_and_the_header_declares
     assert sorted(set(re.findall(r"\b(fe_[a-z0-9_]+)\s*\(", text))) == sorted(_lib.EVO2_SIGNATURES)
     from finenvs_amd.csrc import build
 
-    assert "fe_evo2.hip" in build.SOURCES and "fe_evo2_kernels.h" in build.HEADERS
+    assert "fe_evo.hip" in build.SOURCES and "fe_evo_kernels.h" in build.HEADERS

@@ -1,4 +1,4 @@
-"""GPU: the ES population with two hidden layers (csrc/fe_evo2_kernels.h, ``fe_evo2_rollout``,
+"""GPU: the ES population with two hidden layers (csrc/fe_evo_kernels.h, ``fe_evo2_rollout``,
 ``finenvs_amd.evo.FusedPopulationMLP2Rollout``).
 
 * lock-step parity with the oracle env (no action noise): member weights rebuilt from ``pop.noise``; the device's actions

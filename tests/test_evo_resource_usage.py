@@ -1,4 +1,5 @@
-"""CPU (cross-compile only): the fe_evo_* kernels have no scratch memory and no VGPR spills (tools/resource_usage.py)."""
+"""CPU (cross-compile only): the fe_evo_* kernels of finenvs_amd/csrc/fe_evo.hip have no scratch memory and no VGPR spills
+(tools/resource_usage.py).  The unit's whole kernel set and its committed table are tests/test_evo2_resource_usage.py's."""
 import os
 import sys
 
@@ -16,7 +17,7 @@ def table():
 
     if not os.path.exists(hip_build.HIPCC):
         pytest.skip("hipcc not available")
-    return resource_usage.kernel_table()
+    return resource_usage.kernel_table(source="fe_evo.hip")
 
 
 def test_evo_kernels_use_no_scratch(table):

@@ -228,7 +228,7 @@ def _lockstep_case(fe, fo, N, A, W, H, num_eval, days, bars):
 
 
 def _evo_lds_bytes(EB, A, P):
-    """``evo_lds_bytes`` of csrc/fe_evo_kernels.h restated: the tile's account state, the redrawn days, the actions, theta."""
+    """``evo_lds`` of csrc/fe_evo_kernels.h restated: the tile's account state, the redrawn days, the actions, theta."""
     S = EB * A
     b = EB * 8 + S * 8 + S * 8 + S * 4 + S * 4 + EB * 4
     b = (b + 7) & ~7
