@@ -3,8 +3,16 @@ regimes that the automatic geometry reaches only at full size -- several tiles p
 ragged and single-env tiles, grids that are not multiples of 8 or exceed the tile count, the U = 1 returns scan -- and
 compares bit for bit with the C oracle (oracle/fe_oracle.c), as the rest of the suite does at the automatic geometry.
 The override runs must also equal the automatic run exactly.  Tolerances are those of the existing tests of the same
-kernel: MLP ELU actions 2e-6, evo actions 1e-5.
+kernel: MLP ELU actions 2e-6, evo actions 1e-5, evo2 actions ``ACTION_TOL`` of tests/test_evo2_rollout_gpu.py.
+
+The rollouts that SAMPLE (section 2b: fe_rollout_mlp_sampled_kernel, fe_rollout_mlp2_sampled_kernel,
+fe_rollout_mlp_sac_kernel, fe_rollout_sac_kernel, fe_rollout_sac_big_kernel) take a (K, N, A) noise tensor indexed by
+``(k, n0 + ee, aa)`` and compare ``n0 + ee`` with the evaluation env: their override runs equal the automatic run and the
+oracle env bit for bit, ``forward`` on the trajectory's rows returns what ``run`` recorded, only the evaluation env acts on
+its mean, and the recorded means meet the f64 torch forward within ``2e-5 max|x64| + 4 max|x32_torch - x64|``
+(tests/test_mlp_sac_gpu.py::_bound).  fe_evo2_rollout_kernel walks a second tile at N = 40 000 and, with A = 17, at 28 663.
 """
+import copy
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -184,17 +192,24 @@ def test_step_kernel_results_do_not_depend_on_tile_or_grid(fe, fo, cid, N, A, W,
 
 
 # ----------------------------------------------------------------------------- 2. fused rollouts in the tile loop
-def _rollout_envs(fe, fo, N, A, W, tiles, seed, days=6, bars=14):
-    """Oracle, automatic-geometry env and one env per rollout_tile_envs override, all on the same tables and days."""
-    P, LR = _tables(fo, days, A, bars, W, seed=seed, drop=0.05)
+def _rollout_envs(fe, fo, N, A, W, tiles, seed, days=6, bars=14, evaluate=False, stagger=False):
+    """Oracle, automatic-geometry env and one env per rollout_tile_envs override, all on the same tables and days.
+    ``stagger`` (full days, no dropped bars): env n starts at the row of its day from which 1 + 7 n mod 12 steps are left
+    (tests/test_evo2_rollout_gpu.py::_stagger), so that a run of a few steps crosses episode ends in most envs."""
+    P, LR = _tables(fo, days, A, bars, W, seed=seed, drop=0.0 if stagger else 0.05)
     D = P.shape[0]
     idx = (np.arange(N) * 7 + 1) % D
-    kw = dict(num_intervals=W, evaluate=False, starting_balance=2000)
+    kw = dict(num_intervals=W, evaluate=evaluate, starting_balance=2000)
     ref = fo.OracleEnv(P, LR, env_indices=idx, redraw_mode=1, seed=9, auto_emit=False, nthreads=8, **kw)
     ref.redraw_counter[0] = 1
+    first = bars - (1 + (7 * np.arange(N)) % min(bars, 12))
+    if stagger:
+        ref.spot0[:] = first
     envs = []
     for tile in (0,) + tuple(tiles):
         env = fe.TimeSeriesEnv(tables=(P, LR), env_indices=idx, redraw="device", seed=9, obs_buffers=0, **kw)
+        if stagger:
+            env.env_spots = torch.as_tensor(first).unsqueeze(1) + torch.arange(W)
         if tile:
             step_geometry = env.launch_info()
             assert env.set_launch(rollout_tile_envs=tile) == step_geometry, "the step kernel's geometry stays automatic"
@@ -413,6 +428,266 @@ def test_evo_rollout_tile_loop_equals_oracle(fe, fo):
         assert_bits(t2n(pop.observation()), obs, f"launch {rep} observation()")
         assert_bits(t2n(pop.returns), ret, f"launch {rep} running returns")
     assert ndone > 0
+
+
+def _evo2_tile_loop(fe, fo, N, A, W, H, num_eval, days, bars, chunks):
+    """``_Lockstep`` of tests/test_evo2_rollout_gpu.py (member weights rebuilt from ``pop.noise``, ``_forward2`` in f64,
+    ``ACTION_TOL``; rewards, dones, state, running returns, counters and episode slots bit for bit) at a tile count above
+    kMaxGrid.  Returns the run and the tile count of fe_evo.hip's geometry."""
+    from tests import test_evo2_rollout_gpu as te2
+
+    run, _ = te2._case(fe, fo, N, A, W, H, num_eval, days, bars, stagger=True)
+    pop = run.pop
+    PB = max(1, min(8, 128 // A))
+    tiles = _cdiv(pop.num_pairs, PB) + _cdiv(num_eval, 2 * PB)
+    w = te2._member_weights(pop)
+    for rep, K in enumerate(chunks):
+        run.run(K, w, f"chunk {rep}")
+    assert pop.num_finished() > 0 and run.total > 0
+    run.report(f"evo2 tile loop (N, A, W, H) = ({N}, {A}, {W}, {H}), {tiles} tiles")
+    return run, tiles, PB
+
+
+def test_evo2_rollout_tile_loop_equals_oracle(fe, fo):
+    """fe_evo2_rollout_kernel at N = 40 000 (A = 1, W = 8, H = 32), the shape of the one-layer case above: 2 501 tiles of
+    16 envs for kMaxGrid workgroups, so 453 workgroups walk a second tile with theta loaded once and the per-wave exchange
+    buffer of the second layer reused."""
+    _, tiles, PB = _evo2_tile_loop(fe, fo, 40000, 1, 8, 32, 4, 5, 20, (3, 9))
+    assert PB == 8 and tiles > 2048
+
+
+def test_evo2_rollout_tile_loop_with_uneven_unit_counts(fe, fo):
+    """A = 17: PB = 7 pairs, 14-env tiles, the waves of a tile run 2, 2, 2 and 1 units.  N = 28 663 is the smallest N with
+    three evaluation envs whose tile count exceeds kMaxGrid (14 330 pairs = 2 047 full tiles + 1 of one pair, and one
+    evaluation tile: 2 049), so one workgroup walks a second tile."""
+    N, num_eval = 28663, 3
+    _, tiles, PB = _evo2_tile_loop(fe, fo, N, 17, 4, 32, num_eval, 4, 11, (2, 5))
+    assert PB == 7 and tiles == 2049
+    assert _cdiv((N - 2 - num_eval) // 2, PB) + 1 <= 2048  # one pair fewer: no second tile
+
+
+# ----------------------------------------------------------------------------- 2b. sampling rollouts in the tile loop
+STATE = ("cash", "margin", "long_shares", "env_indices", "env_spots")
+
+
+class _SampledMLP:
+    """``FusedMLPRollout`` / ``FusedMLP2Rollout`` with a tanh output, ``run(noise=, std=, trajectory=)``."""
+    outputs, std = ("actions", "means", "rewards", "dones"), 0.7
+
+    def __init__(self, depth, H, W, activation, seed):
+        from tests import test_mlp2_head_gpu as t2
+        from tests import test_mlp_head_gpu as th
+
+        self.t = th if depth == 1 else t2
+        self.module = self.t._module(H, W, seed, activation, "tanh")
+
+    def roll(self, env):
+        return self.t._rollout(env, self.module, "tanh")
+
+    def run(self, roll, K, noise, traj):
+        a, r, d = roll.run(K, noise=noise, std=self.std, record_means=True, trajectory=traj)
+        return dict(actions=a, means=roll.means, rewards=r, dones=d)
+
+    def forward(self, roll, src, pos, noise):
+        return dict(means=roll.forward(src, pos))
+
+    def sampled(self, means, noise):  # fe_rollout_mlp_sampled_kernel's statement, exact in f32
+        return (means + torch.tensor(self.std, dtype=torch.float32, device=means.device) * noise).clamp(-1.0, 1.0)
+
+    def torch_means(self, pairs, dtype):
+        with torch.no_grad():
+            return copy.deepcopy(self.module).to(dtype)(pairs.to(dtype))
+
+
+class _SacActor:
+    """``FusedMLPSACRollout`` / ``FusedSACRollout`` (resident or streamed)."""
+    outputs = ("actions", "means", "stds", "rewards", "dones")
+
+    def __init__(self, lstm, H, W, activation, seed):
+        from tests import test_mlp_sac_gpu as tms
+        from tests import test_sac_rollout_gpu as tsr
+
+        self.lstm, self.streamed = lstm, H > 128
+        self.actor = tsr._actor(H, W, seed) if lstm else tms._rollout_actor(H, W, seed, activation)
+
+    def roll(self, env):
+        from finenvs_amd.mlp_sac import FusedMLPSACRollout
+        from finenvs_amd.sac import FusedSACRollout
+
+        if not self.lstm:
+            return FusedMLPSACRollout(env, self.actor)
+        roll = FusedSACRollout(env, self.actor, streamed=self.streamed)
+        assert roll.streamed == self.streamed
+        return roll
+
+    def run(self, roll, K, noise, traj):
+        a, r, d = roll.run(K, noise=noise, trajectory=traj, record_means=True, record_stds=True)
+        return dict(actions=a, means=roll.means, stds=roll.stds, rewards=r, dones=d)
+
+    def forward(self, roll, src, pos, noise):
+        a, _, mu, sd = roll.forward(src, pos, noise)
+        return dict(actions=a, means=mu, stds=sd)
+
+    sampled = None
+
+    def torch_means(self, pairs, dtype):
+        with torch.no_grad():
+            return copy.deepcopy(self.actor).to(dtype).get_distribution(pairs.to(dtype)).loc
+
+
+def _sampled_tile_loop(fe, fo, fam, N, A, W, tiles, K, reps, seed, evaluate=False, stagger=False, what=""):
+    """A rollout that takes a ``(K, N, A)`` noise tensor, on one oracle env, one automatic-geometry env and one env per
+    ``rollout_tile_envs`` override.  Per launch, bit for bit: every override run equals the automatic one in every output,
+    both trajectory descriptor arrays (K + 1 rows) and the env's state; ``forward`` on the last override run's trajectory
+    rows returns what ``run`` recorded; the evaluation env (the last of a training-mode env) acts on its mean and every
+    other env's action differs from its mean; the oracle env stepped with the device's actions gives the device's
+    rewards, dones and state.  The means of the first step of the last launch against the f64 torch forward on the
+    rendered trajectory state, within the family's yardstick."""
+    from finenvs_amd.sac import pair_states
+    from finenvs_amd.trajectory import TrajectoryBuffer
+    from tests.test_mlp_sac_gpu import _bound
+
+    _, _, ref, envs = _rollout_envs(fe, fo, N, A, W, tiles, seed=seed, evaluate=evaluate, stagger=stagger)
+    assert all(int(e._eval_env) == (-1 if evaluate else N - 1) for e in envs)
+    rolls = [fam.roll(e) for e in envs]
+    obs = ref.reset().copy()
+    for roll in rolls:
+        assert_bits(t2n(roll.observation()), obs, what + " initial obs")
+    gen = torch.Generator(device="cuda").manual_seed(seed)
+    ndone = 0
+    for rep in range(reps):
+        noise = torch.randn((K, N, A), generator=gen, device="cuda")
+        res = []
+        for roll in rolls:
+            traj = TrajectoryBuffer(K, N, A, states=True)
+            out = fam.run(roll, K, noise, traj)
+            out.update(src=traj.obs_src, pos=traj.obs_pos)
+            assert tuple(traj.obs_src.shape) == (K + 1, N) and tuple(traj.obs_pos.shape) == (K + 1, N, A)
+            res.append((out, traj))
+        for j in range(1, len(rolls)):
+            w = f"{what} launch {rep}: tile {tiles[j - 1]} against the automatic geometry:"
+            for name in fam.outputs + ("src", "pos"):
+                assert_bits(t2n(res[j][0][name]), t2n(res[0][0][name]), f"{w} {name}")
+            for name in STATE:
+                assert_bits(t2n(getattr(envs[j], name)), t2n(getattr(envs[0], name)), f"{w} {name}")
+            assert_bits(t2n(rolls[j].observation()), t2n(rolls[0].observation()), f"{w} observation()")
+        (out, traj), env, roll = res[-1], envs[-1], rolls[-1]
+        acts, means = out["actions"], out["means"]
+        w = f"{what} launch {rep}:"
+        # forward on the trajectory's rows returns what run recorded
+        fwd = fam.forward(roll, out["src"][:K].reshape(-1), out["pos"][:K].reshape(-1, A), noise.reshape(-1, A))
+        assert_bits(t2n(fwd["means"].reshape(K, N, A)), t2n(means), f"{w} forward means == run means")
+        if "stds" in fwd:
+            assert_bits(t2n(fwd["stds"].reshape(K, N, A)), t2n(out["stds"]), f"{w} forward stds == run stds")
+        sampled = fwd["actions"].reshape(K, N, A) if "actions" in fwd else fam.sampled(means, noise)
+        # the evaluation env acts on its mean, every other env samples
+        differ = acts != means
+        if not evaluate:
+            assert_bits(t2n(acts[:, -1]), t2n(means[:, -1]), f"{w} the evaluation env acts on its mean")
+            assert_bits(t2n(acts[:, :-1]), t2n(sampled[:, :-1]), f"{w} the other envs' actions are the samples")
+            differ = differ[:, :-1]
+        else:
+            assert_bits(t2n(acts), t2n(sampled), f"{w} every env's action is the sample")
+        # The sample's own statement can return the mean (a draw that is exactly 0.0, a mean that tanh rounded to +-1.0
+        # and a clamp): decided from the recorded means and the noise alone, and rare -- at most one element in 10 000.
+        same = sampled == means
+        same = same if evaluate else same[:, :-1]
+        print(f"{w} {int((~differ).sum())} of {differ.numel()} sampled actions equal their means; the statement gives the "
+              f"mean for {int(same.sum())} (noise there: {noise[:, :N if evaluate else N - 1][same].tolist()[:4]})")
+        assert int(same.sum()) <= 1e-4 * same.numel(), f"{w} {int(same.sum())} samples equal their means by their statement"
+        assert bool((differ | same).all()), f"{w} a sampled action equals its mean"
+        if rep == reps - 1:  # a consistent but wrong policy: the f64 torch forward on the rendered trajectory state
+            pairs = pair_states(traj.states(env, 0), A)
+            x32, x64 = fam.torch_means(pairs.float(), torch.float32), fam.torch_means(pairs, torch.float64)
+            assert float(x64.std()) > 1e-3, "the head must depend on the observation"
+            _bound(means[0].reshape(-1, 1), x32, x64, f"{w} means of step 0 against f64 torch")  # 2e-5 max|x64| + 4 max|x32 - x64|
+        # the oracle env stepped with the device's actions
+        for k in range(K):
+            assert_bits(t2n(traj.states(env, k)), obs, f"{w} step {k} trajectory state")
+            obs, r_ref, d_ref, _ = ref.step(t2n(acts[k]))
+            obs = obs.copy()
+            ndone += int(d_ref.sum())
+            assert_bits(t2n(out["rewards"][k]), r_ref, f"{w} step {k} rewards")
+            assert_bits(t2n(out["dones"][k]), d_ref, f"{w} step {k} dones")
+        assert_bits(t2n(traj.states(env, K)), obs, f"{w} last trajectory state")
+        assert_bits(t2n(roll.observation()), obs, f"{w} observation()")
+        assert_bits(t2n(env.cash), ref.cash, f"{w} cash")
+        assert_bits(t2n(env.margin), ref.margin, f"{w} margin")
+        assert_bits(t2n(env.long_shares), ref.long, f"{w} long")
+        assert_bits(t2n(env.env_indices), ref.env_idx, f"{w} env_idx")
+        assert_bits(t2n(env.env_spots[:, 0]), ref.spot0, f"{w} spot0")
+        if evaluate and int(ref.n_terminated[0]) == N:  # as tests/test_sac_rollout_gpu.py: every env has finished
+            for e in envs:
+                e.reset_evaluation_metrics()
+            ref.terminated[:] = 0
+            ref.episode_returns[:] = 0
+            ref.n_terminated[0] = 0
+    assert ndone > 0, "the run must cross episode ends"
+
+
+# kMaxGrid = 2048 (fe_env.hip): at rollout_tile_envs = 1 every case below has more tiles than workgroups.  A tile holds at
+# most kBlock / A = 256 / A envs; the policy phase walks ``blk = wave; blk < nblk; blk += 4`` over blocks of 32 pairs, so a
+# tile of more than 128 pairs (256 at A = 1, 85 at A = 3) gives every wavefront a second block.
+SAMPLED_MLP_CASES = [
+    # depth, H, A, N, W, tiles, activation, evaluate
+    (1, 32, 1, 3000, 8, (1, 33, 256), "elu", False),   # > 2048 tiles; ragged tile; 8 column blocks, so each wave takes 2
+    (1, 64, 3, 2100, 5, (1, 85), "tanh", False),       # 3 pairs per tile; 255 pairs per tile
+    (1, 64, 3, 2100, 5, (1,), "relu", True),           # an evaluate-mode env: every env samples
+    (2, 64, 1, 3000, 8, (1, 256), "elu", False),
+    (2, 128, 3, 2100, 5, (1, 7), "tanh", False),       # the one-workgroup-per-CU instantiation
+    (2, 64, 1, 3000, 8, (1,), "relu", True),
+]
+
+
+@pytest.mark.parametrize("depth,H,A,N,W,tiles,activation,evaluate", SAMPLED_MLP_CASES)
+def test_sampled_mlp_rollout_tile_loop(fe, fo, depth, H, A, N, W, tiles, activation, evaluate):
+    """fe_rollout_mlp_sampled_kernel / fe_rollout_mlp2_sampled_kernel under set_launch(rollout_tile_envs=): three launches
+    of five steps on 14-bar days."""
+    assert _cdiv(N, 1) > 2048
+    fam = _SampledMLP(depth, H, W, activation, seed=N + H + depth)
+    _sampled_tile_loop(fe, fo, fam, N, A, W, tiles, 5, 3, seed=3 * N + W + H + depth, evaluate=evaluate,
+                       what=f"mlp{depth} sampled H={H} A={A}")
+
+
+SAC_MLP_CASES = [
+    # H, A, N, W, tiles, activation, evaluate
+    (32, 1, 3000, 8, (1, 33, 256), "elu", False),
+    (64, 3, 2100, 5, (1, 85), "tanh", False),
+    (128, 1, 3000, 4, (1, 7), "relu", False),
+    (64, 3, 2100, 5, (1,), "elu", True),
+]
+
+
+@pytest.mark.parametrize("H,A,N,W,tiles,activation,evaluate", SAC_MLP_CASES)
+def test_sac_mlp_rollout_tile_loop(fe, fo, H, A, N, W, tiles, activation, evaluate):
+    """fe_rollout_mlp_sac_kernel under set_launch(rollout_tile_envs=): mu, s and the action leave from inside the policy
+    phase, indexed by ``(k, n0 + ee, aa)``; three launches of five steps on 14-bar days."""
+    assert _cdiv(N, 1) > 2048
+    fam = _SacActor(False, H, W, activation, seed=H + A)
+    _sampled_tile_loop(fe, fo, fam, N, A, W, tiles, 5, 3, seed=3 * N + W + H, evaluate=evaluate, what=f"sac mlp H={H} A={A}")
+
+
+SAC_LSTM_CASES = [
+    # H, A, N, W, tiles, K, reps, evaluate -- K and reps of test_lstm_rollout_tile_loop_equals_oracle
+    (32, 1, 4500, 4, (1, 7), 4, 3, False),     # shrink-only override, as the LSTM case
+    (128, 3, 4500, 4, (1,), 3, 2, False),
+    (256, 1, 3000, 2, (1, 3), 2, 2, False),    # streamed
+    (32, 1, 4500, 4, (1,), 4, 3, True),
+]
+
+
+@pytest.mark.parametrize("H,A,N,W,tiles,K,reps,evaluate", SAC_LSTM_CASES)
+def test_sac_lstm_rollout_tile_loop(fe, fo, H, A, N, W, tiles, K, reps, evaluate):
+    """fe_rollout_sac_kernel / fe_rollout_sac_big_kernel (``streamed=True``, H = 256) with the tile shrunk to one env: more
+    tiles than the resident grid, so workgroups loop over tiles with h / c, the descriptors and the noise index reloaded
+    per tile.  The runs are a few steps long, so the envs start staggered near their days' ends."""
+    if H <= 128:
+        assert _cdiv(N, 1) > 16 * _num_cus()
+    else:  # a workgroup has 512 threads, so at most 2048 / 512 = 4 are resident per CU: twice as many tiles as workgroups
+        assert _cdiv(N, 1) >= 2 * 4 * _num_cus()
+    fam = _SacActor(True, H, W, None, seed=W + H)
+    _sampled_tile_loop(fe, fo, fam, N, A, W, tiles, K, reps, seed=N + H + A, evaluate=evaluate, stagger=True,
+                       what=f"sac lstm H={H} A={A}")
 
 
 # ----------------------------------------------------------------------------- 3. replay sampling in the tile loop

@@ -879,11 +879,12 @@ def _bound(label, got, t32, r64, rows=None):
     return err / tol
 
 
-@pytest.mark.parametrize("H", [32, 128, 256])
-def test_sac_head_forward_contract(H):
+def _sac_forward_contract(roll, actor, src, pos, states, noise, title):
+    """The forward contract of a SAC head (the LSTM actor's or, tests/test_mlp_sac_contract_gpu.py, the MLP actor's): means
+    and stds (relative) against the f64 copy within the yardstick, then actions and log_probs head-locally, from the
+    kernel's own f32 means and stds.  Returns what ``roll.forward`` returned."""
     from torch.distributions import Normal
 
-    env, roll, actor, src, pos, states, noise, _ = _sac_setup(H)
     actions, log_probs, means, stds = roll.forward(src, pos, noise)
     ref = {}
     for dtype in (F32, F64):
@@ -917,19 +918,58 @@ def test_sac_head_forward_contract(H):
     squash = log_probs.double()[S] - n64
     allow = 4 * 2.0 ** -20 + 2e-5 * float(n64.abs().max()) + 4 * float((n32 - n64).abs().max())
     assert float((squash + np.log(EPS7)).abs().max()) <= allow, (float((squash + np.log(EPS7)).abs().max()), allow)
-    print(f"MEASURED sac forward H = {H}: {({k: round(v, 3) for k, v in worst.items()})} rows at +-1.0: {int(S.sum())}")
+    print(f"MEASURED {title}: {({k: round(v, 3) for k, v in worst.items()})} rows at +-1.0: {int(S.sum())}")
+    return actions, log_probs, means, stds
+
+
+@pytest.mark.parametrize("H", [32, 128, 256])
+def test_sac_head_forward_contract(H):
+    env, roll, actor, src, pos, states, noise, _ = _sac_setup(H)
+    _sac_forward_contract(roll, actor, src, pos, states, noise, f"sac forward H = {H}")
 
 
 GRID_ACTIONS = [0.0] + [s * v for v in (0.5, 0.999, 1 - 2.0 ** -12, 1 - 2.0 ** -23, 1 - 2.0 ** -24, 1.0) for s in (1, -1)]
 GRID_STDS = [1e-6, 1e-3, 0.3, 5.0, 25.0]
 
 
-def _surrogate_grads(actor, states, du, ds, dtype):
+def _surrogate_grads(actor, states, du, ds, dtype, params=tsac._params):
     a = copy.deepcopy(actor).to(dtype)
     tl._zero(a)
     hid = a(states.to(dtype))
     (du.detach() * a.mu_layer(hid) + ds.detach() * torch.nn.functional.softplus(a.std_layer(hid))).sum().backward()
-    return [p.grad for p in tsac._params(a)]
+    return [p.grad for p in params(a)]
+
+
+def _sac_grid(gen, count=SAC_COUNT):
+    """Crafted ``actions`` x ``stds`` (``GRID_ACTIONS`` x ``GRID_STDS``, the rest drawn from the grid) and the upstream
+    gradients ``ga``, ``gl`` with zeros sprinkled in, each (count, 1) f32 on the device."""
+    grid = [(a, s) for a in GRID_ACTIONS for s in GRID_STDS]
+    grid += [grid[i] for i in torch.randint(0, len(grid), (count - len(grid),), generator=gen).tolist()]
+    actions = torch.tensor([g[0] for g in grid], dtype=F64).float().reshape(-1, 1).cuda()
+    stds = torch.tensor([g[1] for g in grid], dtype=F64).float().reshape(-1, 1).cuda()
+    assert int((actions.abs() == 1.0).sum()) >= 10 and float(actions.abs().max()) == 1.0
+    ga, gl = (torch.randn((count, 1), generator=gen) for _ in range(2))
+    ga[5::11] = 0.0
+    gl[7::13] = 0.0
+    return actions, stds, ga.cuda(), gl.cuda()
+
+
+def _sac_contract_grads(actor, states, noise, actions, stds, da, dl, params=tsac._params):
+    """``{dtype: gradients}`` of the surrogate ``sum(du mu(theta) + ds softplus(q(theta)))`` with the contract's ``du``, ``ds``
+    (include/finenvs_amd_sac_grad.h, include/finenvs_amd_mlp_sac.h) in f32 and f64; ``da`` / ``dl`` None: no upstream."""
+    per = {}
+    for dtype in (F32, F64):
+        a, s, e = actions.to(dtype), stds.to(dtype), noise.to(dtype)
+        xa = torch.zeros_like(a) if da is None else da.to(dtype)
+        xl = torch.zeros_like(a) if dl is None else dl.to(dtype)
+        om = 1 - a * a
+        du = xa * om + xl * (2 * a * om / (om + (EPS7 if dtype is F64 else 1e-7)))
+        ds = du * e - xl / s
+        per[dtype] = _surrogate_grads(actor, states, du, ds, dtype, params)
+    return per
+
+
+UPSTREAMS = ("both", "d_actions only", "d_log_probs only")
 
 
 @pytest.mark.parametrize("H", [32, 128, 256])
@@ -943,22 +983,14 @@ def test_sac_head_backward_contract_on_crafted_forward_outputs(H):
     W = 4
     env, roll, actor, src, pos, states, noise, gen = _sac_setup(H, W)
     roll.forward(src, pos, noise)  # packs the weights the backward reads
-    grid = [(a, s) for a in GRID_ACTIONS for s in GRID_STDS]
-    grid += [grid[i] for i in torch.randint(0, len(grid), (SAC_COUNT - len(grid),), generator=gen).tolist()]
-    actions = torch.tensor([g[0] for g in grid], dtype=F64).float().reshape(-1, 1).cuda()
-    stds = torch.tensor([g[1] for g in grid], dtype=F64).float().reshape(-1, 1).cuda()
-    assert int((actions.abs() == 1.0).sum()) >= 10 and float(actions.abs().max()) == 1.0
-    ga, gl = (torch.randn((SAC_COUNT, 1), generator=gen) for _ in range(2))
-    ga[5::11] = 0.0
-    gl[7::13] = 0.0
-    ga, gl = ga.cuda(), gl.cuda()
+    actions, stds, ga, gl = _sac_grid(gen)
     params = tsac._params(actor)
     lib = env._lib
     floats = lib.fe_sac_streamed_grad_workspace_floats if roll.streamed else lib.fe_sac_grad_workspace_floats
     backward = lib.fe_sac_backward_streamed if roll.streamed else lib.fe_sac_backward
     w, (bmu, bstd) = roll._packed, roll._biases
     worst = {}
-    for label, da, dl in (("both", ga, gl), ("d_actions only", ga, None), ("d_log_probs only", None, gl)):
+    for label, da, dl in zip(UPSTREAMS, (ga, ga, None), (gl, None, gl)):
         ws = torch.full((int(floats(H, W, SAC_COUNT)),), float("nan"), dtype=F32, device="cuda")
         g = [torch.full(p.shape, float("nan"), dtype=F32, device="cuda") for p in params]
         sg = _lib.FeSacGrads(*(x.data_ptr() for x in g))
@@ -968,15 +1000,7 @@ def test_sac_head_backward_contract_on_crafted_forward_outputs(H):
             SAC_COUNT, noise.data_ptr(), actions.data_ptr(), stds.data_ptr(), None if da is None else da.data_ptr(),
             None if dl is None else dl.data_ptr(), ws.data_ptr(), C.byref(sg), env._stream()), lib)
         torch.cuda.synchronize()
-        per = {}
-        for dtype in (F32, F64):
-            a, s, e = actions.to(dtype), stds.to(dtype), noise.to(dtype)
-            xa = torch.zeros_like(a) if da is None else da.to(dtype)
-            xl = torch.zeros_like(a) if dl is None else dl.to(dtype)
-            om = 1 - a * a
-            du = xa * om + xl * (2 * a * om / (om + (EPS7 if dtype is F64 else 1e-7)))
-            ds = du * e - xl / s
-            per[dtype] = _surrogate_grads(actor, states, du, ds, dtype)
+        per = _sac_contract_grads(actor, states, noise, actions, stds, da, dl)
         tally = [0.0]
         for name, gf, gd in zip(SAC_GRAD_KEYS, g, per[F64]):
             assert bool(torch.isfinite(gf).all()), (label, name)
