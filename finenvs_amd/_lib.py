@@ -113,6 +113,13 @@ EVO2_SIGNATURES = {
     "fe_evo2_lds_bytes": (_i64, [_i32, _i32, _i32]),
 }
 
+# include/finenvs_amd_evo2_streamed.h: the two-hidden-layer population with theta read through L2 (H up to 256)
+EVO2_STREAMED_SIGNATURES = {
+    "fe_evo2_rollout_streamed": EVO_SIGNATURES["fe_evo_rollout"],
+    "fe_evo2_streamed_num_params": (_i64, [_i32, _i32]),
+    "fe_evo2_streamed_lds_bytes": (_i64, [_i32, _i32, _i32]),
+}
+
 
 # include/finenvs_amd_replay.h: the off-policy replay ring (finenvs_amd/replay.py; same library)
 class FeReplayRing(C.Structure):
@@ -424,7 +431,7 @@ def load(path: Optional[str] = None) -> C.CDLL:
                          **LSTM_GRAD_SIGNATURES, **LSTM_STREAMED_GRAD_SIGNATURES, **CRITIC_STREAMED_SIGNATURES,
                          **OPTIM_SIGNATURES, **SAC_STREAMED_SIGNATURES,
                          **REPLAY_CURSOR_SIGNATURES, **PPO_SIGNATURES, **MLP_HEAD_SIGNATURES, **MLP2_HEAD_SIGNATURES,
-                         **MLP_CRITIC_SIGNATURES, **MLP_SAC_SIGNATURES, **EVO2_SIGNATURES}.items():
+                         **MLP_CRITIC_SIGNATURES, **MLP_SAC_SIGNATURES, **EVO2_SIGNATURES, **EVO2_STREAMED_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError here means the .so is stale
         fn.restype = res
         fn.argtypes = args

@@ -13,9 +13,9 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["fe_env.hip", "fe_mlp_critic.hip", "fe_mlp_sac.hip", "fe_evo.hip", "fe_csv.cpp"]
+SOURCES = ["fe_env.hip", "fe_mlp_critic.hip", "fe_mlp_sac.hip", "fe_evo.hip", "fe_evo_streamed.hip", "fe_csv.cpp"]
 HEADERS = ["fe_device_common.h", "fe_store_policy.h", "fe_step_kernel.h", "fe_activations.h", "fe_rollout_kernels.h", "fe_mlp_head_kernels.h", "fe_mlp2_head_kernels.h", "fe_lstm_kernel.h", "fe_lstm_rollout_body.h", "fe_lstm_big_rollout_body.h", "fe_lstm_stream_tile.h", "fe_lstm_stream_sgrad_body.h", "fe_aux_kernels.h", "fe_replay_kernels.h", "fe_ring_draw_kernels.h", "fe_ppo_kernels.h", "fe_critic_kernels.h", "fe_bptt_tile.h", "fe_critic_grad_kernels.h", "fe_sac_grad_kernels.h", "fe_lstm_grad_kernels.h", "fe_lstm_grad_streamed_kernels.h", "fe_critic_streamed_kernels.h", "fe_sac_streamed_kernels.h", "fe_optim_kernels.h",
-           "fe_mlp_critic_kernels.h", "fe_mlp_sac_kernels.h", "fe_evo_kernels.h", "fe_host_common.h"]  # included by fe_env.hip; the last four by fe_mlp_critic.hip / fe_mlp_sac.hip / fe_evo.hip, the first two of them with the MLP headers
+           "fe_mlp_critic_kernels.h", "fe_mlp_sac_kernels.h", "fe_evo_kernels.h", "fe_host_common.h", "fe_evo_host.h"]  # included by fe_env.hip; the last five by fe_mlp_critic.hip / fe_mlp_sac.hip / fe_evo.hip / fe_evo_streamed.hip, the first two of them with the MLP headers
 LIB = os.path.join(HERE, "libfinenvs_amd.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
@@ -29,7 +29,7 @@ def needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, h) for h in HEADERS] + [os.path.join(REPO, "include", h) for h in ("finenvs_amd.h", "finenvs_amd_ext.h", "finenvs_amd_evo.h", "finenvs_amd_replay.h", "finenvs_amd_sac.h", "finenvs_amd_critic.h", "finenvs_amd_critic_grad.h", "finenvs_amd_sac_grad.h", "finenvs_amd_lstm_grad.h", "finenvs_amd_lstm_grad_streamed.h", "finenvs_amd_critic_streamed.h", "finenvs_amd_sac_streamed.h", "finenvs_amd_optim.h", "finenvs_amd_replay_cursor.h", "finenvs_amd_ppo.h", "finenvs_amd_mlp_head.h", "finenvs_amd_mlp2_head.h", "finenvs_amd_mlp_critic.h", "finenvs_amd_mlp_sac.h", "finenvs_amd_evo2.h")]
+    deps = [os.path.join(HERE, s) for s in SOURCES] + [os.path.join(HERE, h) for h in HEADERS] + [os.path.join(REPO, "include", h) for h in ("finenvs_amd.h", "finenvs_amd_ext.h", "finenvs_amd_evo.h", "finenvs_amd_replay.h", "finenvs_amd_sac.h", "finenvs_amd_critic.h", "finenvs_amd_critic_grad.h", "finenvs_amd_sac_grad.h", "finenvs_amd_lstm_grad.h", "finenvs_amd_lstm_grad_streamed.h", "finenvs_amd_critic_streamed.h", "finenvs_amd_sac_streamed.h", "finenvs_amd_optim.h", "finenvs_amd_replay_cursor.h", "finenvs_amd_ppo.h", "finenvs_amd_mlp_head.h", "finenvs_amd_mlp2_head.h", "finenvs_amd_mlp_critic.h", "finenvs_amd_mlp_sac.h", "finenvs_amd_evo2.h", "finenvs_amd_evo2_streamed.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,4 +1,5 @@
-// fe_evo_kernels.h -- part of fe_evo.hip (one translation unit of the library): the evolution-strategies population -- a
+// fe_evo_kernels.h -- part of fe_evo.hip and fe_evo_streamed.hip (two translation units of the library, the second with
+// theta read through L2, include/finenvs_amd_evo2_streamed.h): the evolution-strategies population -- a
 // K-step rollout in which every env acts with ITS OWN perturbed perceptron of one hidden layer (H) or two (H, H), generated
 // inside the kernel from a counter-based normal stream -- plus the gradient and noise-render kernels of the ES update
 // (finenvs/agents/ES/evo_agent.py, finenvs/agents/networks/parallel_mlp.py; C ABI: include/finenvs_amd_evo.h and
@@ -209,6 +210,7 @@ __device__ __forceinline__ void evo_hidden(const EvoArgs &r, bool pair_tile, int
 // hidden values after a layer's butterfly.  Row i of the middle layer needs h1[i] in every lane: the lanes of row group 0
 // write h1 to the wave's LDS buffer s_h (A at [0, H), B at [H, 2H); null with one hidden layer) and every lane reads the
 // rows it owns.  Assets are evaluated one after the other with the env's weights (z regenerated per asset).
+// theta is read where it lives: the workgroup's LDS copy, or global memory (the streamed kernels).
 template <bool SINGLE, int H, int LAYERS>
 __device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &r, const TileLds &l, float *s_act,
                                                 const float *s_theta, float *s_h, bool pair_tile, int64_t base, int u,
@@ -297,18 +299,22 @@ __device__ __forceinline__ void evo_policy_unit(const Params &p, const EvoArgs &
 // done flag is known.  Tiles: pair tiles [0, pair_tiles) hold PB mirrored pairs (2 PB envs), the rest EB = 2 PB
 // consecutive eval envs.  At two layers and H = 128 theta is above half the LDS from W = 5 on, so one workgroup per CU
 // is resident there whatever the registers allow.
-template <bool SINGLE, int H, int LAYERS>
+// STREAMED: theta stays in global memory (every workgroup reads the same <= 256 KiB + 5W KiB, which lives in L2) and the
+// policy's row loads go there, one float4 per lane and row next to that row's Philox chain; the LDS then holds no theta
+// (evo_lds with P = 0) and does not grow with W.  Loading the rows one or two trips ahead into registers was measured and
+// is slower at every H (profiles/evo_streamed_bench.txt).
+template <bool SINGLE, int H, int LAYERS, bool STREAMED = false>
 __device__ __forceinline__ void evo_rollout_body(const Params &p, const EvoArgs &r) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int A = SINGLE ? 1 : p.A;
     const int EB = p.EB;
     const int S = EB * A;
-    const int64_t P = evo_num_params(LAYERS, p.W, H);
+    const int64_t P = STREAMED ? 0 : evo_num_params(LAYERS, p.W, H);
     const TileLds l = carve_lds(smem, EB, S);
     const EvoLds o = evo_lds(LAYERS, EB, A, P, H);
     int64_t *l_idx = reinterpret_cast<int64_t *>(smem + o.idx);
     float *s_act = reinterpret_cast<float *>(smem + o.act);
-    float *s_theta = reinterpret_cast<float *>(smem + o.theta);
+    const float *s_theta = r.theta;
     const int tid = threadIdx.x;
     const int e = SINGLE ? tid : (int)fdiv((uint32_t)tid, p.div_A);
     const int a = SINGLE ? 0 : tid - e * A;
@@ -317,7 +323,11 @@ __device__ __forceinline__ void evo_rollout_body(const Params &p, const EvoArgs 
     if constexpr (LAYERS == 2) s_h = reinterpret_cast<float *>(smem + o.xchg) + (size_t)wave * 2 * H;
     const int64_t NA = p.N * A;
     const int PB = r.PB;
-    for (int64_t i = tid; i < P; i += kBlock) s_theta[i] = r.theta[i];
+    if constexpr (!STREAMED) {
+        float *copy = reinterpret_cast<float *>(smem + o.theta);
+        for (int64_t i = tid; i < P; i += kBlock) copy[i] = r.theta[i];
+        s_theta = copy;
+    }
 
     for (int64_t tile = blockIdx.x; tile < p.num_tiles; tile += gridDim.x) {
         const bool pair_tile = tile < r.pair_tiles;
@@ -396,6 +406,13 @@ __global__ __launch_bounds__(kBlock, 2) void fe_evo_rollout_kernel(const Params 
 template <bool SINGLE, int H>
 __global__ __launch_bounds__(kBlock, 2) void fe_evo2_rollout_kernel(const Params p, const EvoArgs r) {
     evo_rollout_body<SINGLE, H, 2>(p, r);
+}
+
+// The streamed two-layer entry (fe_evo2_rollout_streamed, H = 32 / 64 / 128 / 256; include/finenvs_amd_evo2_streamed.h):
+// fe_evo2_rollout_kernel with theta read through L2.  Instantiated by fe_evo_streamed.hip only.
+template <bool SINGLE, int H>
+__global__ __launch_bounds__(kBlock, 2) void fe_evo2_streamed_rollout_kernel(const Params p, const EvoArgs r) {
+    evo_rollout_body<SINGLE, H, 2, true>(p, r);
 }
 
 // First pass of the gradient: partial[b][j] = sum over the pairs of block b (ascending) of diffed[p] * z_{g,p,j}, in f64.

@@ -3,7 +3,8 @@ finenvs/agents/networks/parallel_mlp.py) with the per-env networks never materia
 
 ``FusedPopulationMLPRollout`` runs K env steps of the whole population per launch (C ABI ``fe_evo_rollout``,
 include/finenvs_amd_evo.h; ``FusedPopulationMLP2Rollout`` is the same with the reference's default two hidden layers,
-``fe_evo2_rollout``, include/finenvs_amd_evo2.h): every training env acts with ``theta + s * sigma * z`` of its mirrored
+``fe_evo2_rollout``, include/finenvs_amd_evo2.h, or with ``streamed=True`` ``fe_evo2_rollout_streamed``,
+include/finenvs_amd_evo2_streamed.h, which reads theta through L2 and runs the reference's H = 256): every training env acts with ``theta + s * sigma * z`` of its mirrored
 pair, the noise ``z`` generated inside the kernel; finished episodes land in per-env slots on the device, so ``agent.store``'s per-step
 ``nonzero()`` / ``.item()`` host syncs are gone.  ``FusedEvoAgent`` is the EvoAgent loop on top of it.  The rank transform,
 fitness, gradient and Adam step are small torch functions below (pinned against the reference by
@@ -301,24 +302,36 @@ class FusedPopulationMLP2Rollout(FusedPopulationMLPRollout):
     """``FusedPopulationMLPRollout`` with the reference's default two hidden layers (H, H): the network is
     ``tanh(W3^T tanh(W2^T tanh(W1^T x + b1) + b2) + b3)`` (include/finenvs_amd_evo2.h, ``fe_evo2_rollout``); members, noise
     streams, episode state, ``noise`` and ``gradient`` are the one-layer class's, at ``num_params = 5WH + H^2 + 3H + 1``.
-    theta lives in the LDS: H <= 128, and a window that cannot fit is refused here, before any launch."""
+    theta lives in the LDS: H <= 128, and a window that cannot fit is refused here, before any launch.
+
+    ``streamed=True`` reads theta through L2 instead (``fe_evo2_rollout_streamed``, include/finenvs_amd_evo2_streamed.h):
+    the reference's H = 256 and any window run, and wherever both forms take the shape they give the same bits."""
 
     HIDDEN = (32, 64, 128)
+    STREAMED_HIDDEN = (32, 64, 128, 256)
     LAYERS = 2
     LDS_BYTES = 160 * 1024
     _ENTRY = "fe_evo2_rollout"
 
     def _hidden_message(self) -> str:
+        if self.streamed:
+            return f"hidden_dim must be one of {self.HIDDEN} (the streamed two-hidden-layer kernels)"
         return (f"hidden_dim must be one of {self.HIDDEN} (theta lives in the 160 KiB LDS: the middle layer of the reference's "
                 "256 alone is 256 KiB)")
 
     def __init__(self, env, num_eval_envs: int, hidden_dim: int, noise_std_dev: float, seed: int,
-                 action_noise_std: float = 0.01, max_episodes: int = 8):
+                 action_noise_std: float = 0.01, max_episodes: int = 8, streamed: bool = False):
+        self.streamed = bool(streamed)
+        if self.streamed:
+            self.HIDDEN, self._ENTRY = self.STREAMED_HIDDEN, "fe_evo2_rollout_streamed"
         super().__init__(env, num_eval_envs, hidden_dim, noise_std_dev, seed, action_noise_std=action_noise_std,
                          max_episodes=max_episodes)
         W, A = env.num_intervals, env.num_assets
         if A > 128:
             raise ValueError(f"the ES population runs at most 128 assets per env (got {A})")
+        if self.streamed:
+            assert self.num_params == int(env._lib.fe_evo2_streamed_num_params(W, self.H))
+            return
         need = int(env._lib.fe_evo2_lds_bytes(W, A, self.H))
         assert self.num_params == int(env._lib.fe_evo2_num_params(W, self.H))
         if need > self.LDS_BYTES:
@@ -333,17 +346,28 @@ class FusedEvoAgent:
 
     def __init__(self, env, hidden_dim: int = 64, hidden_layers: int = 1, learning_rate: float = 0.01, noise_std_dev: float = 0.02,
                  l2_coefficient: float = 0.005, num_eval_envs: Optional[int] = None, seed: int = 0,
-                 action_noise_std: float = 0.01, max_episodes: int = 8):
+                 action_noise_std: float = 0.01, max_episodes: int = 8, streamed: Optional[bool] = None):
+        """``streamed`` (two hidden layers only): None takes the streamed population where the LDS-resident one cannot take
+        the shape (H = 256, or a window ``fe_evo2_lds_bytes`` puts above 160 KiB); True / False force the choice."""
         if num_eval_envs is None:
             num_eval_envs = 2 if env.num_envs % 2 == 0 else 1
         self.env = env
         self.learning_rate, self.l2_coefficient = float(learning_rate), float(l2_coefficient)
         if hidden_layers not in (1, 2):
             raise ValueError("hidden_layers must be 1 or 2")
-        population = FusedPopulationMLPRollout if hidden_layers == 1 else FusedPopulationMLP2Rollout
         self.hidden_layers = int(hidden_layers)
-        self.population = population(env, num_eval_envs, hidden_dim, noise_std_dev, seed,
-                                     action_noise_std=action_noise_std, max_episodes=max_episodes)
+        if hidden_layers == 1:
+            if streamed:
+                raise ValueError("streamed=True needs hidden_layers=2 (there is no one-layer streamed population)")
+            self.population = FusedPopulationMLPRollout(env, num_eval_envs, hidden_dim, noise_std_dev, seed,
+                                                        action_noise_std=action_noise_std, max_episodes=max_episodes)
+        else:
+            if streamed is None:
+                need = int(env._lib.fe_evo2_lds_bytes(env.num_intervals, min(env.num_assets, 128), int(hidden_dim)))
+                streamed = (int(hidden_dim) == 256 or need > FusedPopulationMLP2Rollout.LDS_BYTES)
+            self.population = FusedPopulationMLP2Rollout(env, num_eval_envs, hidden_dim, noise_std_dev, seed,
+                                                         action_noise_std=action_noise_std, max_episodes=max_episodes,
+                                                         streamed=bool(streamed))
         pop = self.population
         w, b = init_parameters(pop.num_observations, pop.H, torch.Generator().manual_seed(int(seed)), self.hidden_layers)
         pop.set_parameters(w, b)
