@@ -102,6 +102,39 @@ def evo_action_noise_reference(seed, g, step, n, a):
     return np.take_along_axis(z, (a % 4)[..., None], axis=-1)[..., 0]
 
 
+PPO_PERM_SALT = 0x50504F5045524D31  # FE_PPO_PERM_SALT of include/finenvs_amd_ppo.h (pinned by tests/test_ppo_update_host.py)
+PHILOX_U32_DOMAIN = 0x46454E56      # word c2 of the project's one-word generator (pinned by tests/test_evo_streams_host.py)
+
+
+def ppo_permute_reference(seed, epoch, n, positions):
+    """``pi_epoch`` of include/finenvs_amd_ppo.h on a whole array of positions, written from the header's text on
+    ``philox4x32_10``; neither ``rng.ppo_permute`` nor the device code is consulted.  One pass of the four-round Feistel
+    network over all positions, then again over those whose value is still ``>= n`` only, until none is left.  Returns
+    ``(samples int64 of positions' shape, passes)``, ``passes`` the number of passes the longest walk took."""
+    n, m64 = int(n), (1 << 64) - 1
+    x = np.array(positions, dtype=np.int64)
+    if not 1 <= n < 1 << 32 or x.size == 0 or int(x.min()) < 0 or int(x.max()) >= n:
+        raise ValueError(f"need 1 <= n < 2**32 and positions in [0, n) (got n = {n})")
+    shape, x = x.shape, x.reshape(-1).astype(np.uint64)
+    hb = (max(1, (n - 1).bit_length()) + 1) // 2
+    shift, mask = np.uint64(hb), np.uint64((1 << hb) - 1)
+    key = (int(seed) ^ PPO_PERM_SALT) & m64
+    rounds = [(((int(epoch) * 4 + r) & m64) << 16) & m64 for r in range(4)]  # 64-bit arithmetic, as the device's
+    walking, passes = np.arange(x.size), 0
+    while walking.size:
+        if passes >= 1 << (2 * hb):
+            raise AssertionError("a walk longer than the domain: the pass is no bijection")
+        passes += 1
+        left, right = x[walking] >> shift, x[walking] & mask
+        for base in rounds:  # right < 2^16 and base's low 16 bits are clear: the counter's low word is (base | right) & 2^32 - 1
+            low = np.uint64(base & 0xFFFFFFFF) | right
+            word = philox4x32_10(key, low, base >> 32, PHILOX_U32_DOMAIN, 0)[0].astype(np.uint64)
+            left, right = right, left ^ (word & mask)
+        x[walking] = (left << shift) | right
+        walking = walking[x[walking] >= np.uint64(n)]
+    return x.astype(np.int64).reshape(shape), passes
+
+
 def crafted_descriptors(D, L, W, B, seed, pos_scale=0.5):
     """``(src int64 (B,), pos float64 (B, 1))`` on the CPU: B observation descriptors of a one-asset log-return table of D
     days x L rows (``row_elems = 4``), drawn without an env -- windows the env's own reset states never hold, and

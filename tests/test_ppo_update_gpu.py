@@ -4,7 +4,10 @@ Shapes are the smallest at which these paths can still go wrong: H = 32, W = 4, 
 mini-batches drops three samples, N = 24 x T = 5 gives B = 30 (no multiple of a wavefront) from a chunk of capacity
 32 > N (the row stride), n = 1 is the smallest permutation; the losses run at B = 61 (odd, one workgroup), B = 4 096
 (16 workgroups: the partials, the ticket and the last workgroup's sum) and B = 70 001 (above 65 536 the grid is capped
-at 256 workgroups and strides); the heads' backward at B = 30 runs a partial tile.
+at 256 workgroups and strides); the heads' backward at B = 30 runs a partial tile; N = 70 x T = 8 in M = 2 gives
+B = 280: two loss workgroups (the ticket, inside a captured graph too) and more than one tile of the heads' backward.
+The draw beyond one asset and one workgroup is tests/test_ppo_draw_gpu.py, the losses' edges under a derived bound
+tests/test_ppo_loss_edges_gpu.py; both import this file's helpers.
 
 * ``fe_ppo_minibatch`` against the host mirror bit for bit, its memory contract, the epoch counter;
 * the two loss kernels against torch autograd in float64, with the float32 torch expression's own error as the bound;
@@ -55,28 +58,36 @@ FIELDS = ("indices", "obs_src", "obs_pos", "actions", "col0", "col1", "col2", "c
 GUARD = 512
 
 
-def _banded(B):
+def _window(k, B, A):
+    return B * A if k in ("obs_pos", "actions") else B  # the two per-asset outputs are (B, A)
+
+
+def _banded(B, A=1):
     dtypes = {"indices": torch.int64, "obs_src": torch.int64, "obs_pos": torch.float64}
-    big = {k: torch.full((GUARD + B + GUARD,), -7, dtype=dtypes.get(k, torch.float32), device="cuda") for k in FIELDS}
-    return big, {k: v[GUARD:GUARD + B] for k, v in big.items()}
+    big = {k: torch.full((GUARD + _window(k, B, A) + GUARD,), -7, dtype=dtypes.get(k, torch.float32), device="cuda")
+           for k in FIELDS}
+    return big, {k: v[GUARD:GUARD + _window(k, B, A)] for k, v in big.items()}
 
 
-def _bands_intact(big, B, skip=()):
+def _bands_intact(big, B, skip=(), A=1):
     for k, v in big.items():
-        lo, hi = (GUARD, GUARD + B) if k not in skip else (GUARD + B, GUARD + B)  # a skipped output is untouched as a whole
+        n = _window(k, B, A)
+        lo, hi = (GUARD, GUARD + n) if k not in skip else (GUARD + n, GUARD + n)  # a skipped output is untouched as a whole
         assert bool((v[:lo] == -7).all()) and bool((v[hi:] == -7).all()), f"{k}: written outside its window"
 
 
-def _draw(lib, traj, columns, cursor, seed, offset, M, m, win, skip=()):
+def _draw(lib, traj, columns, cursor, seed, offset, M, m, win, skip=(), A=1, num_columns=4, columns_out=True):
+    """``skip``: outputs passed as null.  ``num_columns`` < 4 leaves the tail of both pointer arrays as it is (the launch
+    must not look at it); ``columns_out=False`` passes the array itself as null."""
     from finenvs_amd import _lib
 
     ptr = lambda k: None if k in skip else win[k].data_ptr()  # noqa: E731
     cols = (ct.c_void_p * 4)(*(c.data_ptr() for c in columns))
-    outs = (ct.c_void_p * 4)(*(ptr(f"col{i}") for i in range(4)))
+    outs = (ct.c_void_p * 4)(*(ptr(f"col{i}") for i in range(4))) if columns_out else None
     _lib.check(lib.fe_ppo_minibatch(
-        traj.obs_src.data_ptr(), traj.obs_pos.data_ptr(), traj.actions.data_ptr(), traj.T, traj.N, traj.C, 1, cols, outs, 4,
-        cursor.data_ptr(), seed, offset, M, m, win["indices"].data_ptr(), ptr("obs_src"), ptr("obs_pos"), ptr("actions"),
-        torch.cuda.current_stream().cuda_stream), lib)
+        traj.obs_src.data_ptr(), traj.obs_pos.data_ptr(), traj.actions.data_ptr(), traj.T, traj.N, traj.C, A, cols, outs,
+        num_columns, cursor.data_ptr(), seed, offset, M, m, win["indices"].data_ptr(), ptr("obs_src"), ptr("obs_pos"),
+        ptr("actions"), torch.cuda.current_stream().cuda_stream), lib)
 
 
 def _expected(traj, columns, seed, epoch, M, m):
@@ -404,8 +415,14 @@ def test_fused_loss_backward_accumulates(fe):
         assert_bits(p.grad.cpu().numpy(), (g + g).cpu().numpy(), "accumulated critic gradient")
 
 
-@pytest.mark.parametrize("capacity", [None, 32])
-def test_eager_train_equals_the_hand_written_loop(fe, capacity):
+# (N, T, M): B = 30 is one loss workgroup and a partial first tile of the heads' backward; N = 70, T = 8, M = 2 gives
+# n = 560, B = 280: two loss workgroups (the ticket publishes a partial, inside a captured graph too) and more than one
+# tile in the heads' backward
+UPDATE_SHAPES = [(24, 5, 4), (70, 8, 2)]
+
+
+@pytest.mark.parametrize("N,T,M,capacity", [(24, 5, 4, None), (24, 5, 4, 32), (70, 8, 2, None)], ids=["None", "32", "70-8-2"])
+def test_eager_train_equals_the_hand_written_loop(fe, N, T, M, capacity):
     """``PPOUpdate(fused_loss=False).train()`` against the example's loop on ``minibatch_descriptors`` /
     ``ppo_actor_loss`` / ``ppo_critic_loss`` / ``FusedAdam.step``, driven by the host mirror's indices.  With capacity
     32 > N = 24 the chunk's rows are strided: ``prepare()`` then takes its dense copies of rewards and dones."""
@@ -414,14 +431,15 @@ def test_eager_train_equals_the_hand_written_loop(fe, capacity):
     from finenvs_amd.lstm_head import ppo_actor_loss, ppo_critic_loss
     from finenvs_amd.ppo import minibatch_indices
 
-    E, M = 2, 4
-    a, b = (Arm(fe, capacity=capacity, epochs=E, minibatches=M, fused_loss=False) for _ in range(2))
+    E = 2
+    a, b = (Arm(fe, N=N, T=T, capacity=capacity, epochs=E, minibatches=M, fused_loss=False) for _ in range(2))
+    assert a.update.B == {24: 30, 70: 280}[N]
     means_a, means_b = a.rollout(), b.rollout()
     assert_bits(means_a.cpu().numpy(), means_b.cpu().numpy(), "the two arms' rollouts")
     loss_a, loss_c = a.update.train()
     assert a.update.cursor.tolist() == [E, 0] and a.update.epochs_drawn == E
     # the loop of examples/ppo_lstm_fused.py on the second arm
-    T, N, traj = b.T, b.N, b.traj
+    traj = b.traj
     total = T * N
     with torch.no_grad():
         old_logp = Normal(means_b, b.log_std.exp()).log_prob(traj.actions)
@@ -449,10 +467,10 @@ def test_eager_train_equals_the_hand_written_loop(fe, capacity):
     assert a.opt_a.step_count() == E * M
 
 
-def _three_updates(fe, graphed, fused_loss):
+def _three_updates(fe, graphed, fused_loss, N=24, T=5, M=4):
     from finenvs_amd.graphed import GraphedUpdate
 
-    arm = Arm(fe, epochs=2, minibatches=4, fused_loss=fused_loss)
+    arm = Arm(fe, N=N, T=T, epochs=2, minibatches=M, fused_loss=fused_loss)
     drawn = []
     arm.rollout()
     if graphed:
@@ -472,10 +490,16 @@ def _three_updates(fe, graphed, fused_loss):
     return state, drawn
 
 
-@pytest.mark.parametrize("fused_loss", [True, False])
-def test_graphed_train_equals_the_eager_one(fe, fused_loss):
-    eager, drawn_eager = _three_updates(fe, False, fused_loss)
-    graphed, drawn = _three_updates(fe, True, fused_loss)
+@pytest.mark.parametrize("fused_loss,N,T,M", [(f, *shape) for shape in UPDATE_SHAPES for f in (True, False)],
+                         ids=["True", "False", "True-70-8-2", "False-70-8-2"])  # (the first two: the ids they always had)
+def test_graphed_train_equals_the_eager_one(fe, fused_loss, N, T, M):
+    eager, drawn_eager = _three_updates(fe, False, fused_loss, N, T, M)
+    graphed, drawn = _three_updates(fe, True, fused_loss, N, T, M)
+    assert drawn[0].numel() == (N * T) // M
+    if fused_loss:  # the loss launches of this shape: one workgroup, or two with the ticket between them
+        from finenvs_amd import _lib
+
+        assert int(_lib.load().fe_ppo_loss_workspace_doubles(drawn[0].numel())) == {24: 3, 70: 5}[N]
     assert eager["cursor"].tolist() == [6, 0]  # three train() of two epochs each, no walk without an end
     print({k: float(eager[k]) for k in ("actor_loss", "critic_loss")})
     _assert_same(eager, graphed)
